@@ -20,8 +20,13 @@ Batches are pipelined (default; --no-pipeline runs them back to back): the seed 
 Since round 5 consecutive steps search DIFFERENT memory (N = 1, one block per rank): the config's database block and a second one
 holding the same sequences in reverse order alternate, so that no step finds its letters in the 256 MiB Infinity Cache from the step
 before (--same-block: the old behaviour); `ms_per_step` is the mean over the timed region, `ms_per_step_median` the median over
-windows of steps. After the timed steps the step of the DEFAULT command line (tantan + motif masking of both blocks inside the step)
-is timed too and reported as `masked_step`, with its own parity check (--no-masked-step skips it).
+windows of steps. With --full, after the timed steps the step of the DEFAULT command line (tantan + motif masking of both blocks
+inside the step) is timed too and reported as `masked_step`, with its own parity check (--no-masked-step skips it).
+
+A plain run (no --full) sets up, warms up, times the steps, writes the records of the last timed step if --dump-outputs DIR is
+given, and prints the line. --full adds everything else after the timed steps: the stage latencies of one batch on an idle GPU
+(`alone`), `masked_step`, the roofline figures (a copy of its own for `measured_copy_gbs`, the committed PMC passes), the scaling
+model, and the reference runs (`cpu_baseline`, `e2e`, `parity_checked`; --no-cpu-baseline / --no-e2e skip them).
 
 value   = GCUPS on the DP cells the device SWEEPS (DpTarget::cells, dp/dp.h:121-124, of every round-1 target; round 2 walks
           the kept traces and sweeps nothing) / wall seconds of the K timed steps, whole job. The reference's own count (both
@@ -32,6 +37,8 @@ N > 1   : STRONG scaling of the fixed job, database-sharded (SURVEY.md 8e option
           (dmnd_join_blocks_device = the reference's block join) and gathered on rank 0 (multigpu.query_range_join_device; --host-join:
           the host merge of rounds 3-4). --shard query: every rank holds the whole block and 1/N of the queries, no collective on the
           data path (records are concatenated).
+
+--dump-outputs DIR: the match records of the last timed step, one float64 array per field (DIR/records_<field>.npy, see dump_outputs).
 
 Prints ONE JSON line on rank 0.
 """
@@ -188,6 +195,33 @@ def sweep_roofline(config, ext):
         o["frac_of_packed_issue_peak"] = o["kernels"][best[0]]["frac_of_packed_issue_peak"]
     o["source"] = "%s (SQ_INSTS_VALU per launch) / %s (average launch time)" % (os.path.relpath(pmc, ROOT), os.path.relpath(st, ROOT))
     return o
+
+
+DUMP_CAP_BYTES = 60 << 20        # --dump-outputs writes at most this much (a fixed sample of the records beyond it)
+
+
+def dump_outputs(records, d, cap=DUMP_CAP_BYTES):
+    """--dump-outputs: what the timed path returned in its last step -- the match records -- as DIR/records_<field>.npy, one float64
+    array per field (hsp fields as records_hsp_<field>; every integer field is exact in float64), and DIR/records_count.npy. The
+    hsp's transcript_off, a position in the library's trace buffer rather than a result, is left out. Should the arrays exceed `cap`
+    bytes, a fixed sample of the records is written instead (seeded, in record order; its indices in records_sample_index.npy).
+    Returns the names written."""
+    records = np.asarray(records)
+    fields = [(n,) for n in records.dtype.names if n != "hsp"] + [("hsp", n) for n in records.dtype["hsp"].names if n != "transcript_off"]
+    n = len(records)
+    os.makedirs(d, exist_ok=True)
+    written = {"records_count": np.array([n], dtype=np.float64)}
+    if n * 8 * len(fields) > cap:
+        keep = max(0, (cap - 16) // (8 * (len(fields) + 1)))
+        idx = np.sort(np.random.default_rng(20260923).choice(n, size=keep, replace=False))
+        written["records_sample_index"] = idx.astype(np.float64)
+        records = records[idx]
+    for f in fields:
+        a = records[f[0]] if len(f) == 1 else records[f[0]][f[1]]
+        written["records_" + "_".join(f)] = np.ascontiguousarray(a, dtype=np.float64)
+    for name, a in written.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+    return sorted(written)
 
 
 def cgroup_cpus():
@@ -395,14 +429,17 @@ def main():
     ap.add_argument("--seed-contexts", type=int, default=None, help="seed stages in flight at the same time (own context and stream each; one with several database blocks per rank)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-e2e", action="store_true", help="skip the whole-process comparison (diamond-hip against the reference binary on files)")
-    ap.add_argument("--with-masking", action="store_true", help="(default since round 5; kept for old command lines) time the step of the default command line too")
-    ap.add_argument("--no-masked-step", action="store_true", help="skip `masked_step`: after the timed steps the step of the default command line is timed as well (N=1, one database "
+    ap.add_argument("--with-masking", action="store_true", help="(kept for old command lines) time the step of the default command line too: part of --full")
+    ap.add_argument("--no-masked-step", action="store_true", help="skip `masked_step`: with --full, after the timed steps the step of the default command line is timed as well (N=1, one database "
                     "block, blastp): block copies as loaded -> tantan + motif masking of both blocks on the device -> seed stage -> extension, back to back on one context")
     ap.add_argument("--same-block", action="store_true", help="search the SAME database block in every step. Default (N=1, one block per rank): two database blocks at different "
                     "places of HBM alternate between steps -- the block of the config and the same sequences in reverse order -- so that no step finds its 301 MB of "
                     "letters in the 256 MiB Infinity Cache from the step before")
     ap.add_argument("--host-join", action="store_true", help="join the records of several database blocks / ranks on the host (dmnd_join_blocks) instead of on the device")
     ap.add_argument("--no-pipeline", action="store_true", help="run seed stage and extension stage of a batch back to back on one context")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also measure and check everything besides the headline figure: stage latencies "
+                    "alone, masked_step, roofline figures, scaling model, the reference runs (cpu_baseline, e2e, parity_checked). Off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the match records of the last timed step to DIR/records_<field>.npy (float64)")
     args = ap.parse_args()
 
     # `python bench.py --gpus N` launches its own N ranks (one process per GPU over RCCL); under torchrun / torch.distributed.run
@@ -775,6 +812,9 @@ def main():
     dt = time.perf_counter() - t0
     cpu_ms_per_step = (time.process_time() - cpu0) * 1e3 / args.steps      # CPU time of all threads of this process
     thr1 = thread_cpu_ms()
+    timed_records = state["records"]                         # the last timed step's (the serial steps of --full replace state["records"])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(timed_records, args.dump_outputs)
     xstats = dict(multigpu.STATS)                          # the exchanges of the timed steps (the serial steps below exchange again)
     cpu_by_thread = {k: round((v - thr0.get(k, 0.0)) / args.steps, 2) for k, v in sorted(thr1.items()) if v - thr0.get(k, 0.0) > 0}
     stream_ms, stream_launches = state["stream_ms"], state["stream_launches"]
@@ -787,25 +827,26 @@ def main():
            "note": "wall time of the calls inside the timed, pipelined region (per database block for the seed stage, per batch for the extension): with "
                    "several batches in flight a batch's latency is several steps long; ms_per_step is the throughput figure"}
     pipe_ext = dict(state["ext"])
-    # stage latencies of one batch on an otherwise idle GPU, after the timed region
+    # stage latencies of one batch on an otherwise idle GPU, after the timed region (--full)
     serial, alone = [], {}
-    for _ in range(3):
+    for _ in range(3 if args.full else 0):
         t_s = time.perf_counter()
         hs = [seed_stage(b) for b in range(NB)]
         t_m = time.perf_counter()
         step(prefetched=hs)
         drain()
         serial.append(((time.perf_counter() - t_s) * 1e3, (t_m - t_s) * 1e3))
-    alone = {"batch_latency_ms": min(x[0] for x in serial), "seed_stage_call_ms": min(x[1] for x in serial),
-             "extension_call_ms": state["ext_wall_ms"], "finish_ms": state["finish_wall_ms"], "seed_kernel_ms": list(state["seed_ms"]),
-             "extension": dict(state["ext"])}
+    if serial:
+        alone = {"batch_latency_ms": min(x[0] for x in serial), "seed_stage_call_ms": min(x[1] for x in serial),
+                 "extension_call_ms": state["ext_wall_ms"], "finish_ms": state["finish_wall_ms"], "seed_kernel_ms": list(state["seed_ms"]),
+                 "extension": dict(state["ext"])}
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=coll_device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
 
     masked_step, masked_records = None, None
-    if not args.no_masked_step and world == 1 and NB == 1 and w.contexts == 1:
+    if args.full and not args.no_masked_step and world == 1 and NB == 1 and w.contexts == 1:
         # The step of `diamond blastp --algo 0` with masking at its default (tantan on both blocks, motif soft masking for seed
         # generation; cli.cpp does the same calls per block pair). dmnd_mask_block works in place, so every step starts from the
         # letters as loaded: a device-to-device copy from a context that keeps them (it stands in for the block upload -- inputs
@@ -979,7 +1020,7 @@ def main():
                                             "timed region (what `value` is defined on), this is the median window" % (WIN, E)},
             "database_blocks_alternated": bool(alternate),
             "latency_in_pipeline": lat,
-            "alone": alone,
+            **({"alone": alone} if alone else {}),
             "host_cpu_ms_per_step": cpu_ms_per_step,
             "host_cpu_ms_per_step_by_thread": cpu_by_thread,      # by OS thread name (10 ms clock ticks): bench-* = this script's stage threads incl. the library calls they make, dmnd-pool = the library's host workers
             "host_cpu_quota": cgroup_cpus(),
@@ -996,107 +1037,108 @@ def main():
             "block_upload_ms": upload_ms,
             "pcie_inclusive_gcups": cells_swept / ((dt / args.steps + upload_ms * 1e-3)) / 1e9,
         }
-        # dominant kernel = the reference stream of the seed stage (seed_stream_fast_kernel), one launch per shape and step.
-        # ALGORITHMIC bytes per launch = SURVEY.md 8(d)'s per-unit figure x the units of one launch: the reference side of
-        # bytes_seed = S (L 1 + N 8 2 + ...) is 1 B (residue read once) + 16 B (one 8-byte (key32, loc32) seed entry written and
-        # read back) per reference letter, N = L for the reference block. Our formulation never materialises the entries: it needs
-        # 1 B per letter (design_bytes). Durations: HIP events around the launches on the seed stream (dmnd_seed_search).
-        k_ms = stream_ms / max(stream_launches, 1)
-        ref_letters = sum(int(b[3][-1] - b[3][0]) for b in w.blocks) // NB          # letters of one launch = one database block
-        alg_bytes = 17 * ref_letters
-        achieved = alg_bytes / (k_ms * 1e-3) / 1e9
-        k_alone = alone["seed_kernel_ms"][1] / (seed_params.n_shapes * NB)       # the serial step runs one launch per shape and database block
-        buf_a = torch.empty(1 << 30, dtype=torch.uint8, device=device)
-        buf_b = torch.empty_like(buf_a)
-        buf_b.copy_(buf_a)
-        torch.cuda.synchronize()
-        t_c = time.perf_counter()
-        for _ in range(5):
+        if args.full:                                        # figures that take runs or files of their own
+            # dominant kernel = the reference stream of the seed stage (seed_stream_fast_kernel), one launch per shape and step.
+            # ALGORITHMIC bytes per launch = SURVEY.md 8(d)'s per-unit figure x the units of one launch: the reference side of
+            # bytes_seed = S (L 1 + N 8 2 + ...) is 1 B (residue read once) + 16 B (one 8-byte (key32, loc32) seed entry written and
+            # read back) per reference letter, N = L for the reference block. Our formulation never materialises the entries: it needs
+            # 1 B per letter (design_bytes). Durations: HIP events around the launches on the seed stream (dmnd_seed_search).
+            k_ms = stream_ms / max(stream_launches, 1)
+            ref_letters = sum(int(b[3][-1] - b[3][0]) for b in w.blocks) // NB          # letters of one launch = one database block
+            alg_bytes = 17 * ref_letters
+            achieved = alg_bytes / (k_ms * 1e-3) / 1e9
+            k_alone = alone["seed_kernel_ms"][1] / (seed_params.n_shapes * NB)       # the serial step runs one launch per shape and database block
+            buf_a = torch.empty(1 << 30, dtype=torch.uint8, device=device)
+            buf_b = torch.empty_like(buf_a)
             buf_b.copy_(buf_a)
-        torch.cuda.synchronize()
-        copy_gbs = 5 * 2 * (1 << 30) / (time.perf_counter() - t_c) / 1e9
-        del buf_a, buf_b
-        out["roofline"] = {
-            "bound": "hbm", "kernel": "seed_stream_fast_kernel (reference block streamed once per shape against the query seed table)",
-            "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-            "traffic": None,      # PMC bytes cannot be collected inside a timed run: filled below from the committed rocprofv3 --pmc pass
-            "measured_copy_gbs": copy_gbs, "algorithmic_bytes_per_launch": alg_bytes, "algorithmic_bytes_per_unit": 17, "units_per_launch": ref_letters,
-            "launches_per_step": seed_params.n_shapes, "kernel_ms": k_ms, "kernel_ms_alone": k_alone,
-            "frac_alone": alg_bytes / (k_alone * 1e-3) / 1e9 / HBM_PEAK_GBS,
-            "design_bytes_per_launch": ref_letters, "frac_design_bytes": ref_letters / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-            "note": "achieved = SURVEY 8(d) algorithmic bytes of the join's reference side (17 B per reference letter: residue + one 8-byte seed entry "
-                    "written and read back) / average launch duration in the timed region. The kernel reads every letter once (design_bytes = 1 B per "
-                    "letter) and probes a query-side table instead of materialising reference seed entries; it is bound by one L2 request per reference "
-                    "position, not by HBM bytes (DESIGN.md 5)"}
-        # HBM traffic of the dominant kernel per launch: FETCH_SIZE of a separate `rocprofv3 --pmc FETCH_SIZE` pass over this same
-        # command (tools/profile_r03.sh), doubled as MI355X_MICROARCH.md prescribes for gfx950, plus WRITE_SIZE; only quoted for the
-        # configuration and kernel variant it was measured on
-        pmc_path = next((q for q in (os.path.join(ROOT, "profiles", "r%02d_pmc_summary_%s.json" % (r, args.config)) for r in (6, 5, 4, 3, 2)) if os.path.exists(q)), None)
-        full_size = args.queries == CONFIGS[args.config].get("queries", 10_000) and args.families == CONFIGS[args.config].get("families", 100_000)
-        if not (world == 1 and full_size and pmc_path):
-            out["roofline"]["traffic_source"] = "no committed PMC pass applies (N = %d, full size: %s, file: %s)" % (world, full_size, pmc_path)
-        if world == 1 and full_size and pmc_path:
-            pmc = json.load(open(pmc_path))
-            # the stream kernel's entry: of several instantiations the one with the most launches (the config's own)
-            k = sorted([v for name, v in pmc.items() if "seed_stream_fast_kernel" in name and "FETCH_SIZE_x2_bytes_per_launch" in v], key=lambda v: -v.get("launches", 0))[:1]
-            if len(k) == 1 and "FETCH_SIZE_x2_bytes_per_launch" in k[0]:
-                rl = out["roofline"]
-                rl["traffic"] = k[0]["FETCH_SIZE_x2_bytes_per_launch"] + k[0].get("WRITE_SIZE_bytes_per_launch", 0.0)
-                rl["traffic_source"] = "%s: FETCH_SIZE x 2 (gfx950 correction) + WRITE_SIZE, bytes per launch" % os.path.relpath(pmc_path, ROOT)
-                # three different HBM figures, named for what they are
-                rl["hbm_measured"] = {"bytes_per_launch": rl["traffic"], "gbs": rl["traffic"] / (k_alone * 1e-3) / 1e9, "frac": rl["traffic"] / (k_alone * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                                      "note": "what the kernel really moves over the fabric (PMC) / its launch time alone; `achieved` above is the SURVEY 8(d) MODEL of the "
-                                              "reference's seed-array traffic (17 B per letter), which this kernel never moves"}
-                if "TCC_REQ_sum_per_launch" in k[0]:
-                    L2_REQ_PEAK = 2.7e11      # 34.5 TB/s of L2 bandwidth (MI355X_MICROARCH.md) / 128-byte lines
-                    rl["l2_requests"] = {"bound": "l2 request rate", "requests_per_launch": k[0]["TCC_REQ_sum_per_launch"],
-                                         "hits": k[0].get("TCC_HIT_sum_per_launch"), "misses": k[0].get("TCC_MISS_sum_per_launch"),
-                                         "achieved": k[0]["TCC_REQ_sum_per_launch"] / (k_alone * 1e-3), "peak": L2_REQ_PEAK, "unit": "requests/s",
-                                         "frac": k[0]["TCC_REQ_sum_per_launch"] / (k_alone * 1e-3) / L2_REQ_PEAK,
-                                         "note": "the kernel's real limit: one 4-byte probe of the L2-resident query-seed bitmap per reference position = one L2 "
-                                                 "request per letter (TCC_REQ of the committed PMC pass / launch time alone)"}
-                # ... and as plain fields of the roofline object, for readers that do not descend into the sub-objects
-                rl["hbm_measured_frac"] = rl["hbm_measured"]["frac"]
-                if "l2_requests" in rl:
-                    rl["l2_requests_frac"] = rl["l2_requests"]["frac"]
-        out["sweep_roofline"] = sweep_roofline(args.config, ext)
-        # SURVEY 8(d)'s whole-pipeline figure: bytes_total = bytes_seed + bytes_sw over the step's wall time
-        S = seed_params.n_shapes
-        L = ref_letters * NB + int(w.ql[-1] - w.ql[0]) * NB
-        bytes_seed = S * (L * 1 + L * 16 + int(n_hits_all) * 15)
-        bytes_sw = int((r1_targets + r2_targets) * w.db_letters / w.n_db) + int(w.ql[-1] - w.ql[0]) * 32 + int(r1_targets + r2_targets) * 72      # T ~ DpTargets x mean target length
-        out["roofline"]["pipeline_hbm_model"] = {"bytes_per_step": bytes_seed + bytes_sw, "gbs": (bytes_seed + bytes_sw) / (dt / args.steps) / 1e9,
-                                                 "frac": (bytes_seed + bytes_sw) / (dt / args.steps) / 1e9 / HBM_PEAK_GBS / max(world, 1),
-                                                 "note": "SURVEY 8(d): (bytes_seed + bytes_sw of the reference's data layout) / wall time of a step / (N x 8 TB/s); the joined-position "
-                                                         "fingerprint term (P x 48 B) is left out (P is not counted on the device in --fast)"}
-        if world == 1:
-            out["scaling_model"] = scaling_model(out, ext, cpu_ms_per_step, cgroup_cpus(), dt / args.steps * 1e3, int(n_matches_all), w.n_blocks_total, E, threads)
-        if seed_params.n_shapes > 2:
-            out["roofline"]["note"] += ("; with short seeds (weight < 10) this kernel also runs the Hamming filter of every joined (query, reference) "
-                                        "position pair, so its launch time covers the join AND the stage-1 filter")
-        if not args.no_cpu_baseline and world == 1:          # reported on rank 0 at N=1 only
-            # the whole-process runs get the GPU to themselves: this process's contexts (resident blocks, trace arenas) go first
-            qids = ["%s%d" % ("r" if w.contexts == 6 else "q", i) for i in range(w.n_queries)]
-            tids = ["t%d" % i for i in range(w.n_db)]
-            text = hip.format_tab(state["records"], qids, tids, w.source_lens)
-            masked_text = hip.format_tab(masked_records, qids, tids, w.source_lens) if masked_records is not None else None
-            for c in (ctxs_seed if ctxs_seed is not ctxs else []) + [x for cs in ext_ctxs for x in cs] + (alt_ext_ctxs + seed_ctxs_alt if alternate else []) + ([join_ctx] if join_ctx else []) + (set_join_ctxs or []):
-                c.close()
-            closed = True
-            torch.cuda.empty_cache()
-            ref, ref_md5, e2e = cpu_baseline_reference(w, cgroup_cpus(), e2e=not args.no_e2e)
-            if ref is not None:
-                out["cpu_baseline"] = ref
-                if e2e is not None:
-                    out["e2e"] = e2e
-                # parity of THIS run: the records of the last timed step, formatted as the reference's tabular output
-                ours = hashlib.md5(text.encode()).hexdigest()
-                out["parity_checked"] = ours == ref_md5
-                out["parity"] = {"records_md5": ours, "reference_output_md5": ref_md5, "lines": text.count("\n")}
-                if masked_text is not None and e2e is not None:
-                    want = e2e["runs"]["default_masking"]["reference_md5"]
-                    got = hashlib.md5(masked_text.encode()).hexdigest()
-                    out["masked_step"]["parity"] = {"records_md5": got, "reference_output_md5": want, "matches": got == want}
+            torch.cuda.synchronize()
+            t_c = time.perf_counter()
+            for _ in range(5):
+                buf_b.copy_(buf_a)
+            torch.cuda.synchronize()
+            copy_gbs = 5 * 2 * (1 << 30) / (time.perf_counter() - t_c) / 1e9
+            del buf_a, buf_b
+            out["roofline"] = {
+                "bound": "hbm", "kernel": "seed_stream_fast_kernel (reference block streamed once per shape against the query seed table)",
+                "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                "traffic": None,      # PMC bytes cannot be collected inside a timed run: filled below from the committed rocprofv3 --pmc pass
+                "measured_copy_gbs": copy_gbs, "algorithmic_bytes_per_launch": alg_bytes, "algorithmic_bytes_per_unit": 17, "units_per_launch": ref_letters,
+                "launches_per_step": seed_params.n_shapes, "kernel_ms": k_ms, "kernel_ms_alone": k_alone,
+                "frac_alone": alg_bytes / (k_alone * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                "design_bytes_per_launch": ref_letters, "frac_design_bytes": ref_letters / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                "note": "achieved = SURVEY 8(d) algorithmic bytes of the join's reference side (17 B per reference letter: residue + one 8-byte seed entry "
+                        "written and read back) / average launch duration in the timed region. The kernel reads every letter once (design_bytes = 1 B per "
+                        "letter) and probes a query-side table instead of materialising reference seed entries; it is bound by one L2 request per reference "
+                        "position, not by HBM bytes (DESIGN.md 5)"}
+            # HBM traffic of the dominant kernel per launch: FETCH_SIZE of a separate `rocprofv3 --pmc FETCH_SIZE` pass over this same
+            # command (tools/profile_r03.sh), doubled as MI355X_MICROARCH.md prescribes for gfx950, plus WRITE_SIZE; only quoted for the
+            # configuration and kernel variant it was measured on
+            pmc_path = next((q for q in (os.path.join(ROOT, "profiles", "r%02d_pmc_summary_%s.json" % (r, args.config)) for r in (6, 5, 4, 3, 2)) if os.path.exists(q)), None)
+            full_size = args.queries == CONFIGS[args.config].get("queries", 10_000) and args.families == CONFIGS[args.config].get("families", 100_000)
+            if not (world == 1 and full_size and pmc_path):
+                out["roofline"]["traffic_source"] = "no committed PMC pass applies (N = %d, full size: %s, file: %s)" % (world, full_size, pmc_path)
+            if world == 1 and full_size and pmc_path:
+                pmc = json.load(open(pmc_path))
+                # the stream kernel's entry: of several instantiations the one with the most launches (the config's own)
+                k = sorted([v for name, v in pmc.items() if "seed_stream_fast_kernel" in name and "FETCH_SIZE_x2_bytes_per_launch" in v], key=lambda v: -v.get("launches", 0))[:1]
+                if len(k) == 1 and "FETCH_SIZE_x2_bytes_per_launch" in k[0]:
+                    rl = out["roofline"]
+                    rl["traffic"] = k[0]["FETCH_SIZE_x2_bytes_per_launch"] + k[0].get("WRITE_SIZE_bytes_per_launch", 0.0)
+                    rl["traffic_source"] = "%s: FETCH_SIZE x 2 (gfx950 correction) + WRITE_SIZE, bytes per launch" % os.path.relpath(pmc_path, ROOT)
+                    # three different HBM figures, named for what they are
+                    rl["hbm_measured"] = {"bytes_per_launch": rl["traffic"], "gbs": rl["traffic"] / (k_alone * 1e-3) / 1e9, "frac": rl["traffic"] / (k_alone * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                          "note": "what the kernel really moves over the fabric (PMC) / its launch time alone; `achieved` above is the SURVEY 8(d) MODEL of the "
+                                                  "reference's seed-array traffic (17 B per letter), which this kernel never moves"}
+                    if "TCC_REQ_sum_per_launch" in k[0]:
+                        L2_REQ_PEAK = 2.7e11      # 34.5 TB/s of L2 bandwidth (MI355X_MICROARCH.md) / 128-byte lines
+                        rl["l2_requests"] = {"bound": "l2 request rate", "requests_per_launch": k[0]["TCC_REQ_sum_per_launch"],
+                                             "hits": k[0].get("TCC_HIT_sum_per_launch"), "misses": k[0].get("TCC_MISS_sum_per_launch"),
+                                             "achieved": k[0]["TCC_REQ_sum_per_launch"] / (k_alone * 1e-3), "peak": L2_REQ_PEAK, "unit": "requests/s",
+                                             "frac": k[0]["TCC_REQ_sum_per_launch"] / (k_alone * 1e-3) / L2_REQ_PEAK,
+                                             "note": "the kernel's real limit: one 4-byte probe of the L2-resident query-seed bitmap per reference position = one L2 "
+                                                     "request per letter (TCC_REQ of the committed PMC pass / launch time alone)"}
+                    # ... and as plain fields of the roofline object, for readers that do not descend into the sub-objects
+                    rl["hbm_measured_frac"] = rl["hbm_measured"]["frac"]
+                    if "l2_requests" in rl:
+                        rl["l2_requests_frac"] = rl["l2_requests"]["frac"]
+            out["sweep_roofline"] = sweep_roofline(args.config, ext)
+            # SURVEY 8(d)'s whole-pipeline figure: bytes_total = bytes_seed + bytes_sw over the step's wall time
+            S = seed_params.n_shapes
+            L = ref_letters * NB + int(w.ql[-1] - w.ql[0]) * NB
+            bytes_seed = S * (L * 1 + L * 16 + int(n_hits_all) * 15)
+            bytes_sw = int((r1_targets + r2_targets) * w.db_letters / w.n_db) + int(w.ql[-1] - w.ql[0]) * 32 + int(r1_targets + r2_targets) * 72      # T ~ DpTargets x mean target length
+            out["roofline"]["pipeline_hbm_model"] = {"bytes_per_step": bytes_seed + bytes_sw, "gbs": (bytes_seed + bytes_sw) / (dt / args.steps) / 1e9,
+                                                     "frac": (bytes_seed + bytes_sw) / (dt / args.steps) / 1e9 / HBM_PEAK_GBS / max(world, 1),
+                                                     "note": "SURVEY 8(d): (bytes_seed + bytes_sw of the reference's data layout) / wall time of a step / (N x 8 TB/s); the joined-position "
+                                                             "fingerprint term (P x 48 B) is left out (P is not counted on the device in --fast)"}
+            if world == 1:
+                out["scaling_model"] = scaling_model(out, ext, cpu_ms_per_step, cgroup_cpus(), dt / args.steps * 1e3, int(n_matches_all), w.n_blocks_total, E, threads)
+            if seed_params.n_shapes > 2:
+                out["roofline"]["note"] += ("; with short seeds (weight < 10) this kernel also runs the Hamming filter of every joined (query, reference) "
+                                            "position pair, so its launch time covers the join AND the stage-1 filter")
+            if not args.no_cpu_baseline and world == 1:          # reported on rank 0 at N=1 only
+                # the whole-process runs get the GPU to themselves: this process's contexts (resident blocks, trace arenas) go first
+                qids = ["%s%d" % ("r" if w.contexts == 6 else "q", i) for i in range(w.n_queries)]
+                tids = ["t%d" % i for i in range(w.n_db)]
+                text = hip.format_tab(state["records"], qids, tids, w.source_lens)
+                masked_text = hip.format_tab(masked_records, qids, tids, w.source_lens) if masked_records is not None else None
+                for c in (ctxs_seed if ctxs_seed is not ctxs else []) + [x for cs in ext_ctxs for x in cs] + (alt_ext_ctxs + seed_ctxs_alt if alternate else []) + ([join_ctx] if join_ctx else []) + (set_join_ctxs or []):
+                    c.close()
+                closed = True
+                torch.cuda.empty_cache()
+                ref, ref_md5, e2e = cpu_baseline_reference(w, cgroup_cpus(), e2e=not args.no_e2e)
+                if ref is not None:
+                    out["cpu_baseline"] = ref
+                    if e2e is not None:
+                        out["e2e"] = e2e
+                    # parity of THIS run: the records of the last timed step, formatted as the reference's tabular output
+                    ours = hashlib.md5(text.encode()).hexdigest()
+                    out["parity_checked"] = ours == ref_md5
+                    out["parity"] = {"records_md5": ours, "reference_output_md5": ref_md5, "lines": text.count("\n")}
+                    if masked_text is not None and e2e is not None:
+                        want = e2e["runs"]["default_masking"]["reference_md5"]
+                        got = hashlib.md5(masked_text.encode()).hexdigest()
+                        out["masked_step"]["parity"] = {"records_md5": got, "reference_output_md5": want, "matches": got == want}
         if world > 1:
             pending_line = out                               # printed below, behind the teardown of the process group
         else:
@@ -1109,7 +1151,7 @@ def main():
         dist.destroy_process_group()                         # all ranks together: rank 0 is about to spend seconds on the reference run
     if pending_line is not None:
         out = pending_line
-        if not args.no_cpu_baseline and state.get("records") is not None:
+        if args.full and not args.no_cpu_baseline and state.get("records") is not None:
             # N > 1: the job's records (rank 0 holds them all) against the reference run with the same database block cut (-b as the
             # workload cut its blocks); the reference's own timing is an N = 1 matter and not taken here
             qids = ["%s%d" % ("r" if w.contexts == 6 else "q", i) for i in range(w.n_queries)]
@@ -1128,8 +1170,9 @@ def print_line(out):
     """the last thing on the line (what a tail of the output shows): the figures of this run in one place"""
     out["summary"] = {"ms_per_step": out["ms_per_step"], "value": out["value"], "unit": out["unit"], "parity_checked": out.get("parity_checked"),
                       "masked_step_ms_per_step": (out.get("masked_step") or {}).get("ms_per_step"), "host_cpu_ms_per_step": out["host_cpu_ms_per_step"],
-                      "roofline_frac": out["roofline"]["frac"], "roofline_traffic_bytes": out["roofline"].get("traffic"),
-                      "sweep_valu_issue_frac": out["sweep_roofline"].get("frac"), "sweep_frac_of_packed_issue_peak": out["sweep_roofline"].get("frac_of_packed_issue_peak"), "sweep_lane_use": out["sweep_roofline"].get("lane_use"),
+                      "roofline_frac": out.get("roofline", {}).get("frac"), "roofline_traffic_bytes": out.get("roofline", {}).get("traffic"),
+                      "sweep_valu_issue_frac": out.get("sweep_roofline", {}).get("frac"), "sweep_frac_of_packed_issue_peak": out.get("sweep_roofline", {}).get("frac_of_packed_issue_peak"),
+                      "sweep_lane_use": out.get("sweep_roofline", {}).get("lane_use"),
                       "e2e_speedup_min": (out.get("e2e") or {}).get("speedup_min"), "rccl_world_size": out["rccl"]["world_size"]}
     print(json.dumps(out), flush=True)
 

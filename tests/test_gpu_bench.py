@@ -1,5 +1,5 @@
-"""-m gpu: bench.py itself, at reduced size: the JSON contract (metric/value/roofline/cpu_baseline on one line), parity_checked
-against the reference binary inside the same run, the multi-block configuration (C5: database blocks processed one after the other
+"""-m gpu: bench.py itself, at reduced size: the JSON contract of a plain run (the headline figure, --dump-outputs) and of --full
+(metric/value/roofline/cpu_baseline on one line), parity_checked against the reference binary inside the same run, the multi-block configuration (C5: database blocks processed one after the other
 and joined as the reference joins reference blocks) and the two-rank database-sharded path (both ranks on the one GPU of the box,
 records exchanged over gloo: DMND_BENCH_SHARE_GPU=1)."""
 import json
@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -27,7 +28,7 @@ def _bench(args, env=None, launcher=None):
 def test_bench_line_and_parity_at_reduced_size(cfg):
     if not os.path.exists(REF):
         pytest.fail("oracle/_ref/diamond_tap is missing: under -m gpu the reference binary is the checker, its absence is a failure")
-    d = _bench(["--config", cfg, "--queries", "1500", "--families", "3000", "--steps", "2", "--warmup", "1"])
+    d = _bench(["--config", cfg, "--queries", "1500", "--families", "3000", "--steps", "2", "--warmup", "1", "--full"])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
                 "roofline", "cpu_baseline"):
         assert key in d, key
@@ -49,7 +50,7 @@ def test_c5_full_size_parity():
     bench run itself. The other full-size configurations are byte-compared in test_gpu_fullscale.py."""
     if not os.path.exists(REF):
         pytest.fail("oracle/_ref/diamond_tap is missing: under -m gpu the reference binary is the checker, its absence is a failure")
-    d = _bench(["--config", "C5", "--steps", "2", "--warmup", "1", "--no-e2e"])
+    d = _bench(["--config", "C5", "--steps", "2", "--warmup", "1", "--no-e2e", "--full"])
     assert d["config"]["queries"] == 100000 and d["config"]["db_seqs"] == 5000000
     assert d["parity_checked"] is True, d.get("parity")
     assert d["parity"]["lines"] > 100000 and d["parity"]["records_md5"] == d["parity"]["reference_output_md5"]
@@ -84,7 +85,7 @@ def test_bench_four_ranks_two_query_halves_times_two_database_shards():
         pytest.fail("oracle/_ref/diamond_tap is missing: under -m gpu the reference binary is the checker, its absence is a failure")
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--shard", "2d", "--queries", "1500", "--families", "3000", "--steps", "2", "--warmup", "1",
-           "--no-e2e", "--no-masked-step"]
+           "--no-e2e", "--no-masked-step", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=dict(env, DMND_BENCH_SHARE_GPU="1"), cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -100,7 +101,7 @@ def test_bench_e2e_and_hot_path_baselines():
     (the reference's seed-stage + extension task timers) are on the bench line, md5-equal outputs for all three command lines."""
     if not os.path.exists(REF):
         pytest.fail("oracle/_ref/diamond_tap is missing: under -m gpu the reference binary is the checker, its absence is a failure")
-    d = _bench(["--queries", "1500", "--families", "3000", "--steps", "2", "--warmup", "1", "--with-masking"])
+    d = _bench(["--queries", "1500", "--families", "3000", "--steps", "2", "--warmup", "1", "--with-masking", "--full"])
     # --with-masking: the step of the default command line (masking on the device inside the step); its records = the reference's default output
     m = d["masked_step"]
     assert m["ms_per_step"] > 0 and m["stages_back_to_back"]["parts_ms"]["mask_target"] > 0 and m["masked_letters"]["database"] > 0
@@ -112,3 +113,25 @@ def test_bench_e2e_and_hot_path_baselines():
     assert e["parity"] is True, {k: v["parity"] for k, v in e["runs"].items()}
     assert all(v["ours_s"] > 0 and v["reference_s"] > 0 for v in e["runs"].values())
     assert all(0 < v["speedup_min"] <= v["speedup"] for v in e["runs"].values()) and e["speedup_min"] > 0
+
+
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run (no --full): the headline figure only -- no reference run, no roofline or masked step -- and --dump-outputs writes
+    the records of the last timed step; two runs with the same arguments write the same arrays."""
+    args = ["--queries", "1500", "--families", "3000", "--steps", "3", "--warmup", "1"]
+    d = _bench(args + ["--dump-outputs", str(tmp_path / "a")])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "n_gpus"):
+        assert key in d, key
+    assert d["steps"] == 3 and len(d["ms_each_step"]) == 3 and d["unit"] == "GCUPS" and d["higher_is_better"] is True and d["value"] > 0
+    assert d["ms_per_step"] > 0
+    for key in ("cpu_baseline", "e2e", "masked_step", "roofline", "alone", "parity_checked"):
+        assert key not in d, key
+    _bench(args + ["--dump-outputs", str(tmp_path / "b")])
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and "records_query.npy" in names and "records_hsp_score.npy" in names
+    n = int(np.load(tmp_path / "a" / "records_count.npy")[0])
+    assert n > 100 and len(np.load(tmp_path / "a" / "records_query.npy")) == n
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in names) <= 64 * 10 ** 6
+    for f in names:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f

@@ -5,7 +5,7 @@ OUT="$ROOT/gpurun_out/c3"; mkdir -p "$OUT"
 cd "$ROOT"
 [ -n "$SKIP_TESTS" ] || timeout 900 python -m pytest tests/test_gpu_seed.py tests/test_gpu_bench.py -m gpu -x -q -k "not two_ranks and not c5_full and not e2e" 2>&1 | tail -4
 for cls in ${CLS:-1 0}; do
-  DMND_SEED_CLASSES=$cls timeout 600 python bench.py --config C3 --steps 4 --warmup 2 --no-e2e > "$OUT/bench_C3_classes$cls.json" 2> "$OUT/err$cls.txt"
+  DMND_SEED_CLASSES=$cls timeout 600 python bench.py --config C3 --steps 4 --warmup 2 --no-e2e --full > "$OUT/bench_C3_classes$cls.json" 2> "$OUT/err$cls.txt"
   python - "$OUT/bench_C3_classes$cls.json" $cls <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][0])

@@ -11,7 +11,7 @@ PMC_SHORT=1 timeout 900 "$ROOT/tools/pmc_passes.sh" $cfg "$OUT/pmc_summary_$cfg.
 cp "$OUT/kernel_stats_$cfg.csv" "$ROOT/profiles/r06_kernel_stats_$cfg.csv"; cp "$OUT/pmc_summary_$cfg.json" "$ROOT/profiles/r06_pmc_summary_$cfg.json"
 cd "$ROOT"
 extra=""; [ $cfg = C2skew ] && extra="--no-e2e"
-timeout 900 python bench.py --config $cfg --steps 30 --warmup 10 $extra > "$OUT/bench_$cfg.json" 2> "$OUT/bench_$cfg.err"
+timeout 900 python bench.py --config $cfg --steps 30 --warmup 10 --full $extra > "$OUT/bench_$cfg.json" 2> "$OUT/bench_$cfg.err"
 python - <<PY
 import json
 d=json.loads(open("$OUT/bench_$cfg.json").read().strip().splitlines()[-1])

@@ -13,7 +13,7 @@ if [[ " $* " == *" bench "* ]]; then
 for cfg in C2 C4 C5 C3 C2skew; do
   steps=50; [ $cfg = C3 ] && steps=30; [ $cfg = C5 ] && steps=32; [ $cfg = C2skew ] && steps=30
   extra=""; [ $cfg = C2skew ] && extra="--no-e2e"
-  timeout 900 python "$ROOT/bench.py" --config $cfg --steps $steps --warmup 10 $extra > "$OUT/bench_$cfg.json" 2> "$OUT/bench_$cfg.err"
+  timeout 900 python "$ROOT/bench.py" --config $cfg --steps $steps --warmup 10 --full $extra > "$OUT/bench_$cfg.json" 2> "$OUT/bench_$cfg.err"
   tail -c 300 "$OUT/bench_$cfg.err"
 done
 fi

@@ -394,7 +394,7 @@ static int seed_reserve(dmnd_ctx* c, const SeedParams& sp, const SeedSizes& z, i
 	if (int rc = c->mask_time.ensure((size_t)q_block_len + 256)) return rc;
 	if (int rc = c->seed_keys.ensure((size_t)z.SB * (z.slots << z.slot_shift))) return rc;
 	if (int rc = c->seed_need.ensure((size_t)(z.slots / 32 + SEED_NEED_FOLD_WORDS) * sizeof(uint32_t))) return rc;      // the map and, behind it, its folded copy (launch_seed_collect)
-	if (int rc = c->seed_next.ensure((size_t)z.SB * nq_pos * sizeof(uint32_t))) return rc;        // qslot
+	if (int rc = c->seed_next.ensure((size_t)seed_build_work_words(nq_pos) * sizeof(uint32_t))) return rc;        // the build's work area (launch_seed_build)
 	if (int rc = c->seed_qlist.ensure((size_t)z.SB * nq_pos * sizeof(uint32_t))) return rc;
 	if (int rc = c->seed_qkeys.ensure((size_t)nq_pos * sizeof(uint32_t))) return rc;
 	// (c->counters is shared with the masking calls that may run beside a reservation: the search allocates it itself)
@@ -477,8 +477,10 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 	const size_t slot_bytes = (size_t)slots << z.slot_shift;      // one shape's table
 	const bool fused = z.fused, reuse = z.reuse;
 	const size_t bm_total = z.bm_total;
-	int list_key_bits = 1;                                // of the list sort's keys: log2(slots) + 1 (launch_seed_lists)
-	while (((uint64_t)1 << list_key_bits) <= slots) ++list_key_bits;
+	int slot_bits = 0;                                    // log2(slots): the sort key of the build (SeedArgs::order)
+	while (((uint64_t)1 << slot_bits) < slots) ++slot_bits;
+	int bm_log2 = 0;
+	while (((uint64_t)1 << bm_log2) < bm_words) ++bm_log2;
 	// key classes (seed_core.h seed_class): the short-seed pipeline, when the geometry allows eighths (DMND_SEED_CLASSES=0: one range)
 	static const bool classes_env = [] { const char* e = getenv("DMND_SEED_CLASSES"); return !e || atoi(e) != 0; }();
 	// ... and (round 5) long seeds against a query block whose level-1 filter has outgrown an XCD's L2 (above 2^24 query positions the
@@ -503,7 +505,7 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 	const bool counters_new = c->counters.cap < (size_t)(S + 16) * sizeof(unsigned long long);
 	if (int rc = c->counters.ensure((size_t)(S + 16) * sizeof(unsigned long long))) return rc;      // [S] hits, [S+1] deferred pairs, [S+2] collected positions, [S+3] Hamming survivors, [S+4] scored survivors
 	// everything a search starts from, in ONE launch (launch_seed_clear): the counters, the mask times, the need map and -- unless the
-	// query side is kept from the last call -- bitmaps, slots-of-positions and table
+	// query side is kept from the last call -- bitmaps and table
 	{
 		SeedClear z;
 		z.add(c->counters.p, (size_t)((phases || counters_new) ? S + 16 : S + 5) * sizeof(unsigned long long), 0);
@@ -511,7 +513,6 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 		z.add(c->seed_need.p, (size_t)(slots / 32) * sizeof(uint32_t), 0);
 		if (!index_ready) {
 			z.add(c->seed_bitmap.p, bm_total, 0);
-			z.add(c->seed_next.p, (size_t)SB * nq_pos * sizeof(uint32_t), 0xff);
 			z.add(c->seed_keys.p, (size_t)SB * slot_bytes, 0xff);
 		}
 		HIP_TRY(launch_seed_clear(z, st));
@@ -561,15 +562,16 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 		a.qid_of = c->qid_of.as<uint32_t>(); a.mask_time = c->mask_time.as<uint8_t>();
 		a.slots = reinterpret_cast<SeedSlot*>(c->seed_keys.as<char>() + (size_t)own * slot_bytes);
 		a.slot_shift = z.slot_shift;
-		a.qslot = c->seed_next.as<uint32_t>() + (size_t)own * nq_pos;
 		a.qlist = c->seed_qlist.as<uint32_t>() + (size_t)own * nq_pos;
 		a.slot_mask = slots - 1;
 		a.classes = classes;
+		a.slot_bits = slot_bits;
+		a.bm1_hmask = bm1_hmask_of(slot_bits, classes);
+		a.bitmap_log2 = bm_log2;
 		a.phase_ticks = phases ? c->counters.as<unsigned long long>() + S + 8 : nullptr;
 		a.tclass = classes ? c->seed_tclass.as<uint16_t>() : nullptr; a.tclass_stride = (seed_code_groups(t_begin, t_end) + 3) & ~(int64_t)3;
 		a.tcodes = classes ? c->seed_tcodes.as<uint64_t>() : nullptr; a.tflags = classes ? c->seed_tflags.as<uint32_t>() : nullptr; a.tplanes = classes ? c->seed_tplanes.as<uint64_t>() : nullptr;
 		a.bitmap = c->seed_bitmap.as<uint32_t>() + (size_t)own * (bm_words + bm1_words);
-		a.bitmap_mask = (uint32_t)(bm_words - 1);
 		a.bitmap1 = a.bitmap + bm_words;
 		a.bitmap1_words = (uint32_t)bm1_words; a.bitmap1_k3 = bm1_k3; a.stream_nt = stream_nt; a.probe_policy = probe_policy;
 		a.matched_slot = c->matched_slot.as<uint32_t>() + matched_off;
@@ -596,8 +598,8 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 	// the query side of one shape: built (table, position lists, bitmaps), or -- kept from an earlier call -- its marks reset
 	auto query_side = [&](const SeedArgs& a, int sid, bool build) -> int {
 		if (build) {
-			HIP_TRY(launch_seed_index(a, sid, st));
-			HIP_TRY(launch_seed_lists(a, sid, c->seed_qkeys.as<uint32_t>(), c->seed_qlist.as<uint32_t>() + (size_t)(sid % SB) * nq_pos, list_key_bits, &c->sort_tmp, &c->sort_tmp_bytes, st));
+			HIP_TRY(launch_seed_build(a, sid, c->seed_qlist.as<uint32_t>() + (size_t)(sid % SB) * nq_pos, c->seed_next.as<uint32_t>(), c->seed_qkeys.as<uint32_t>(),
+				&c->sort_tmp, &c->sort_tmp_bytes, st));
 		}
 		else HIP_TRY(launch_seed_reset(a, sid, st));
 		return DMND_OK;
@@ -685,13 +687,12 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 			SeedArgs a = args_for(sid, 0, 0);
 			tm.start();
 			if (sid > 0) {
-				// the survivor counter and, where a buffer set is used again, its table, slots-of-positions and bitmaps -- one launch
+				// the survivor counter and, where a buffer set is used again, its table and bitmaps -- one launch
 				SeedClear z;
 				z.add(ctr + S + 3, sizeof(unsigned long long), 0);
 				if (recycle && sid >= SB) {
 					const size_t own = (size_t)(sid % SB);
 					z.add(c->seed_keys.as<char>() + own * slot_bytes, slot_bytes, 0xff);
-					z.add(c->seed_next.as<char>() + own * (size_t)nq_pos * sizeof(uint32_t), (size_t)nq_pos * sizeof(uint32_t), 0xff);
 					z.add(c->seed_bitmap.as<char>() + own * (size_t)(bm_words + bm1_words) * sizeof(uint32_t), (size_t)(bm_words + bm1_words) * sizeof(uint32_t), 0);
 				}
 				HIP_TRY(launch_seed_clear(z, st));
@@ -748,7 +749,6 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 			HIP_TRY(hipMemsetAsync(c->counters.p, 0, (size_t)(S + 5) * sizeof(unsigned long long), st));
 			HIP_TRY(hipMemsetAsync(c->seed_keys.p, 0xff, (size_t)S * slot_bytes, st));
 			HIP_TRY(hipMemsetAsync(c->seed_bitmap.p, 0, bm_total, st));
-			HIP_TRY(hipMemsetAsync(c->seed_next.p, 0xff, (size_t)S * nq_pos * sizeof(uint32_t), st));
 		}
 		bool overflow = false;
 		int64_t off = 0;

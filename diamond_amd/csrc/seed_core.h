@@ -448,6 +448,24 @@ DMND_HD uint32_t seed_class(uint64_t key)
 	x ^= x >> 4;
 	return (x ^ (x >> 3)) & 7u;
 }
+// Layout of the query side (SeedArgs, seed_kernels.h): a key's 32-bit order value u, whose top slot_bits bits t
+// are the sort key of the build. The home slot (t), the level-1 word and the level-2 word are non-decreasing functions of t, and
+// with classes the top three bits of u are the class: class c owns the c-th eighth of the slots and of both filters.
+DMND_HD uint32_t seed_order(uint32_t h, uint64_t key, int classes) { return classes ? seed_class(key) << 29 | h >> 3 : h; }
+// bits of hash a that the level-1 word depends on: those of t
+DMND_HD uint32_t bm1_hmask_of(int slot_bits, int classes) { return ~0u << (32 - slot_bits + (classes ? 3 : 0)); }
+// level-1 word of t: the scaled word of u with its bits below t cleared
+DMND_HD uint32_t bm1_word_of_top(uint32_t t, int slot_bits, uint32_t words) { return bm1_word(t << (32 - slot_bits), words); }
+// ... in the form the stream evaluates per window (h = seed_hash_a(key)): one AND more than the plain scaled word. Equal to
+// bm1_word_of_top(t) when words is a multiple of 8 (the class eighth w8 = words / 8 then splits off exactly).
+DMND_HD uint32_t bm1_word_of_key(uint32_t h, uint64_t key, int classes, uint32_t hmask, uint32_t words)
+{
+	if (!classes) return bm1_word(h & hmask, words);
+	const uint32_t w8 = words >> 3;
+	return seed_class(key) * w8 + bm1_word(h & hmask, w8);
+}
+// level-2 word of t (2^bm_log2 words); its bit is seed_hash_b >> 27
+DMND_HD uint32_t bm2_word_of_top(uint32_t t, int slot_bits, int bm_log2) { return (uint32_t)(((uint64_t)t << bm_log2) >> slot_bits); }
 DMND_HD uint32_t bm1_bits(uint32_t h, uint32_t k3)
 {
 	const uint32_t two = (1u << (h & 31)) | (1u << ((h >> 5) & 31));

@@ -46,8 +46,7 @@ struct SeedArgs {
 	                              // read -- the 512 MB table no longer fits the 256 MB Infinity Cache and the stream + filter kernel of C3
 	                              // went from 124 to 137 ms per 16 shapes (L2 misses 3.15e8 -> 4.05e8 per launch)
 	__host__ __device__ SeedSlot& slot(uint64_t i) const { return *reinterpret_cast<SeedSlot*>(reinterpret_cast<char*>(slots) + (i << slot_shift)); }
-	uint32_t* qslot;                              // per query position: slot of its seed (LIST_END: no seed); input of the list sort
-	const uint32_t* qlist;                        // query positions grouped by slot (SeedSlot::head = start, count in flags >> 8)
+	const uint32_t* qlist;                        // query positions grouped by seed, ascending in each group (SeedSlot::head = start, count in flags >> 8)
 	uint64_t slot_mask;
 	int classes;                                  // 8: slots and level-1 words are partitioned by seed_class(key) (short-seed pipeline); 0: one range
 	// ... and then the reference letters as the stream wants them, made once per search by seed_codes_kernel: per group of 16
@@ -56,26 +55,29 @@ struct SeedArgs {
 	const uint64_t* tplanes;                      // the same class nibbles bit-sliced: bits [16 b, 16 b + 16) = bit b of the group's 16 nibbles (seed_classify_kernel)
 	const uint16_t* tclass; int64_t tclass_stride;  // per shape (seed_classify_kernel): plane c = the valid windows of class c, 16 per entry; plane 8 (hashed seeds): the special ones
 	unsigned long long* phase_ticks;              // DMND_SEED_PHASES=1: 8 counters (seed_stream_fast_kernel PHASE_MARK), else NULL
+	// Layout of the query side (seed_core.h seed_order). Every key has a 32-bit order value u = seed_hash_a(key), or
+	// class << 29 | a >> 3 with classes; its top slot_bits bits t are the sort key of the build (launch_seed_build), and the home
+	// slot, the level-1 word and the level-2 word are all non-decreasing functions of t -- so that ONE sort of the query positions
+	// by t lays out the table, the filters and the lists in the same order, and the build writes them with plain stores. Class c
+	// owns the c-th eighth of the slots and of both filters. The level-1 bits stay the low bits of a, the level-2 bit comes from
+	// seed_hash_b.
+	int slot_bits;                                // log2(slot_mask + 1)
+	uint32_t bm1_hmask;                           // bits of hash a that choose the level-1 word (bm1_hmask_of)
+	int bitmap_log2;                              // log2 of the level-2 word count
+	__host__ __device__ uint32_t order(uint32_t h, uint64_t key) const { return seed_order(h, key, classes); }
 	// home slot of a key (hh = seed_hash(key)) and word of its level-1 bits (h = seed_hash_a(key))
-	__host__ __device__ uint64_t home(uint64_t hh, uint64_t key) const
-	{
-		if (!classes) return hh & slot_mask;
-		const uint64_t low = slot_mask >> 3;
-		return (uint64_t)seed_class(key) * (low + 1) | (hh & low);
-	}
-	__host__ __device__ uint32_t bm1_index(uint32_t h, uint64_t key) const
-	{
-		if (!classes) return bm1_word(h, bitmap1_words);
-		const uint32_t w8 = bitmap1_words >> 3;
-		return seed_class(key) * w8 + bm1_word(h, w8);
-	}
+	__host__ __device__ uint64_t home(uint64_t hh, uint64_t key) const { return order((uint32_t)hh, key) >> (32 - slot_bits); }
+	__host__ __device__ uint32_t bm1_index(uint32_t h, uint64_t key) const { return bm1_word_of_key(h, key, classes, bm1_hmask, bitmap1_words); }
+	__host__ __device__ uint32_t bm1_of_top(uint32_t t) const { return bm1_word_of_top(t, slot_bits, bitmap1_words); }
+	__host__ __device__ uint32_t bm2_of_top(uint32_t t) const { return bm2_word_of_top(t, slot_bits, bitmap_log2); }
+	__host__ __device__ uint32_t bm2_index(uint32_t h, uint64_t key) const { return bm2_of_top(order(h, key) >> (32 - slot_bits)); }
 	// two one-hash bitmaps of the query seeds: level 1 is sized to stay resident in every XCD's 4 MB L2 (the reference
 	// stream probes it once per position), level 2 (>= 16 bits per query seed) filters level-1 false positives before
 	// the open-addressing table is touched
 	uint32_t* bitmap1; uint32_t bitmap1_words, bitmap1_k3;      // level-1 filter (seed_core.h bm1_word / bm1_bits)
 	int probe_policy;                                           // cache policy of the level-1 probes (seed_kernels.hip bm1_probe)
 	int stream_nt;                                              // reference letters are loaded non-temporally (they are read once)
-	uint32_t* bitmap; uint32_t bitmap_mask;
+	uint32_t* bitmap;                                           // level 2: word bm2_index, bit seed_hash_b >> 27
 	// joined reference positions of this shape
 	uint32_t* matched_slot; int64_t* matched_loc; unsigned long long* matched_count; int64_t matched_cap;
 	SeedDeferred* deferred; unsigned long long* deferred_count; int64_t deferred_cap;
@@ -92,7 +94,7 @@ struct SeedArgs {
 	const uint8_t* qfold;                         // fused pipeline: the query block with 4 bits per letter (letter & 15), or NULL: pre-filter of the Hamming test
 	const uint8_t* tfold;                         // by-class stream: the reference block folded the same way, or NULL (the window is folded from the letters)
 	int level2;                                   // the level-2 bitmap is filled and consulted (long seeds)
-	int fused;                                    // short-seed pipeline: seed_lists_kernel decides SLOT_LOWC for every group (the stream needs it)
+	int fused;                                    // short-seed pipeline: seed_build_kernel decides SLOT_LOWC for every group (the stream needs it)
 };
 
 // Up to 8 byte ranges set to a byte value each by ONE kernel launch. A search used to start with six hipMemsetAsync calls and add
@@ -109,12 +111,13 @@ hipError_t launch_seed_qid(const int64_t* limits, int64_t n_seqs, uint32_t* qid_
 // room for the folded need map that seed_collect's workgroups keep in LDS (2^13 words = 32 KB by default, up to 2^15); it lies behind
 // SeedArgs::need_bits
 enum { SEED_NEED_FOLD_WORDS = 32768 };
-hipError_t launch_seed_index(const SeedArgs& a, int sid, hipStream_t st);
 // query seed positions whose shape window touches a soft-masked stretch get their mask time (MaskingTable::remove's bit mask)
 hipError_t launch_seed_soft_time(const SeedArgs& a, hipStream_t st);
-// groups the query positions by slot: stable radix sort of (qslot, position) into (sorted_slot, qlist_out), then the list
-// start/size of every occupied slot is written into the table
-hipError_t launch_seed_lists(const SeedArgs& a, int sid, uint32_t* sorted_slot, uint32_t* qlist_out, int slot_bits, void** tmp, size_t* tmp_bytes, hipStream_t st);
+// Builds the query side of shape sid -- table, position lists (qlist_out, which a.qlist reads) and both filters -- from ONE stable radix sort of the
+// query positions by their order value's top slot_bits bits. work: seed_build_work_words(n) words; sorted_top: n
+// words; the table must be all ones and the filters zero.
+inline int64_t seed_build_work_words(int64_t n) { return 5 * n + 66; }
+hipError_t launch_seed_build(const SeedArgs& a, int sid, uint32_t* qlist_out, uint32_t* work, uint32_t* sorted_top, void** tmp, size_t* tmp_bytes, hipStream_t st);
 // fused = true (short seeds, where a third of the reference positions join): the stream kernel also runs the Hamming filter on
 // every joined pair while the reference letters are at hand, and fills a.survivors; a.matched_* then only serve the deferred pass
 // a table kept from an earlier search of the same query block: clears the per-reference-block marks (joined, erased) of every slot

@@ -3,8 +3,9 @@
 //
 // Data flow (per-thread arithmetic in seed_core.h):
 //   seed_qid_kernel     query position -> query id (for Hit::query_ and the seed offset)
-//   seed_index_kernel   every query position: seed in registers -> open-addressing table in HBM
-//                       (keys[], heads[]) + per-position `next` links = per-seed lists of query positions
+//   launch_seed_build   the query side from ONE sort: every query position's seed in registers -> its sort key (top bits of
+//                       its hash); a stable radix sort; then the open-addressing table in HBM, the per-seed lists of query
+//                       positions and both filters of the stream are written in sorted order with plain stores
 //   seed_stream_kernel  the reference block is streamed ONCE, coalesced; every position's seed is computed in
 //                       registers and probed; a probe hit marks the slot "joined" and appends (slot, position)
 //                       -- no reference seed array, no radix passes, no 9-byte scatter (the reference's #1 cost)
@@ -20,6 +21,9 @@
 #include <cstdio>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
+#include <rocprim/iterator/transform_iterator.hpp>
+#include <rocprim/iterator/transform_output_iterator.hpp>
+#include <rocprim/device/device_scan.hpp>
 #include "seed_kernels.h"
 #include "tuning.h"
 
@@ -72,29 +76,231 @@ __global__ void seed_qid_kernel(const int64_t* __restrict__ limits, int64_t n_se
 		qid_of[p] = (uint32_t)seq;
 }
 
-__global__ void seed_index_kernel(SeedArgs a, int sid)
+// ---- query side: one sort, then plain stores ---------------------------------------------------------------
+// The work area of launch_seed_build (32-bit words): [0, n) sort keys, later the placement scan's output (and the long runs'
+// scratch before it); [n, 2n) list sizes by sorted index; [2n, 2n + 64) counters; [2n + 64, 3n + 64) the sorted indices of the keys
+// placed past the last slot; then, 8-byte aligned, every query position's table key. The kernels behind the sort find a position's
+// key there with ONE 8-byte load: recomputed from the letters at positions in hash order it took ~28 byte loads to as many random
+// lines per element (0.38 ms per C2 build, bound by L2 requests).
+enum { BUILD_SHORT = 8 };                     // runs of equal sort key up to this length are regrouped in one thread's registers
+static const uint32_t BUILD_CONSUMED = 0xffffffffu;
+
+// Per query position: its sort key t (top slot_bits bits of the order value), or 1 << slot_bits -- sorting last -- for a position
+// without a seed. The query-indexed algorithm drops a low-complexity query seed and masks it when the query seeds are enumerated
+// (enum_seeds_hashed, enum_seeds.h:141-145), whether or not it joins; one position per thread and shape: no race.
+__global__ void seed_order_kernel(SeedArgs a, int sid, uint32_t* __restrict__ skey, uint64_t* __restrict__ keys, uint32_t* __restrict__ ctr)
 {
-	const int64_t p = a.q_begin + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i < 4) ctr[i] = 0;
+	const int64_t p = a.q_begin + i;
 	if (p >= a.q_end) return;
+	uint32_t k = 1u << a.slot_bits;
 	uint64_t seed;                                     // table key (seed_key_at)
-	if (!seed_key_at(a.params, sid, a.qseed + p, seed)) return;
-	if (a.params.seed_encoding == SEED_HASHED && !seed_is_complex(a.params, sid, a.qseed + p)) {
-		// query-indexed algorithm: a low-complexity query seed is dropped and masked when the query seeds are enumerated
-		// (enum_seeds_hashed, enum_seeds.h:141-145), whether or not it joins; one position per thread and shape: no race
-		const uint8_t t = (uint8_t)(sid * a.params.index_chunks);
-		if (t < a.mask_time[p]) a.mask_time[p] = t;
-		return;
+	if (seed_key_at(a.params, sid, a.qseed + p, seed)) {
+		if (a.params.seed_encoding == SEED_HASHED && !seed_is_complex(a.params, sid, a.qseed + p)) {
+			const uint8_t t = (uint8_t)(sid * a.params.index_chunks);
+			if (t < a.mask_time[p]) a.mask_time[p] = t;
+		}
+		else {
+			k = a.order(seed_hash_a(seed), seed) >> (32 - a.slot_bits);
+			keys[i] = seed;
+		}
 	}
-	const uint64_t h = seed_hash(seed);
-	if (a.level2) atomicOr(&a.bitmap[(h >> 32) & a.bitmap_mask], 1u << (h >> 59));      // level 2: only consulted for long seeds (launch_seed_stream)
-	atomicOr(&a.bitmap1[a.bm1_index((uint32_t)h, seed)], bm1_bits((uint32_t)h, a.bitmap1_k3));        // K bits, one word; bits of hash a only
-	uint64_t slot = a.home(h, seed);
-	for (;;) {
-		const unsigned long long old = atomicCAS((unsigned long long*)&a.slot(slot).key, (unsigned long long)SEED_EMPTY, (unsigned long long)seed);
-		if (old == SEED_EMPTY || old == seed) break;
-		slot = (slot + 1) & a.slot_mask;
+	skey[i] = k;
+}
+
+
+// After the stable sort by t (positions ascending within a run of equal t): a run holds the positions of every key whose t it is,
+// interleaved. Its first thread regroups them in place into one position-ascending list per key, the keys in the order of their
+// smallest positions, and writes every list's size at its start (0 elsewhere). Runs longer than BUILD_SHORT -- a seed repeated
+// many times, mostly -- are regrouped by the whole wavefront, one pass over the run per distinct key.
+__global__ __launch_bounds__(256) void seed_group_kernel(SeedArgs a, const uint64_t* __restrict__ keys, const uint32_t* __restrict__ top, uint32_t* __restrict__ qlist,
+	uint32_t* __restrict__ len, uint32_t* __restrict__ scratch, int64_t n)
+{
+	const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	const uint32_t none = 1u << a.slot_bits;
+	const uint32_t t = j < n ? top[j] : none;
+	const bool head = t != none && (j == 0 || top[j - 1] != t);
+	int64_t e = j + 1;
+	if (head) {
+		while (e < n && e - j <= BUILD_SHORT && top[e] == t) ++e;
+		if (e - j > BUILD_SHORT && e < n && top[e] == t) {      // long run: the end by galloping, then bisection
+			int64_t lo = e, step = 1, hi = e + 1;                 // top[lo] == t
+			while (hi < n && top[hi] == t) { lo = hi; step *= 2; hi = lo + step; }
+			if (hi > n) hi = n;                                   // the end lies in (lo, hi]
+			while (hi - lo > 1) { const int64_t mid = (lo + hi) / 2; if (top[mid] == t) lo = mid; else hi = mid; }
+			e = hi;
+		}
 	}
-	a.qslot[p - a.q_begin] = (uint32_t)slot;            // the per-seed position lists are built by a sort on this (seed_lists_kernel)
+	else if (t == none && j < n) len[j] = 0;
+	const bool is_long = head && e - j > BUILD_SHORT;
+	if (head && !is_long) {
+		const int m = (int)(e - j);
+		if (m == 1) len[j] = 1;
+		else {
+			uint32_t x[BUILD_SHORT];
+			uint64_t k[BUILD_SHORT];
+#pragma unroll
+			for (int i = 0; i < BUILD_SHORT; ++i) {
+				x[i] = i < m ? qlist[j + i] : 0u;
+				k[i] = i < m ? keys[x[i]] : 0u;
+			}
+			uint32_t done = 0;                                    // bit i: element i is written
+			int out = 0;
+#pragma unroll
+			for (int i = 0; i < BUILD_SHORT; ++i) {
+				if (i >= m || ((done >> i) & 1u)) continue;
+				const int start = out;
+#pragma unroll
+				for (int r = i; r < BUILD_SHORT; ++r)
+					if (r < m && k[r] == k[i]) {
+						qlist[j + out] = x[r];
+						if (out != start) len[j + out] = 0;
+						++out;
+						done |= 1u << r;
+					}
+				len[j + start] = (uint32_t)(out - start);
+			}
+		}
+	}
+	// the long runs of this wavefront, one after the other by all its lanes; a lane always handles the run indices = its lane number
+	// mod 64, so that it reads back only what it wrote itself
+	uint64_t longs = __ballot(is_long);
+	const int lane = threadIdx.x & 63;
+	while (longs) {
+		const int src = __builtin_ctzll(longs);
+		longs &= longs - 1;
+		const int64_t s = __shfl(j, src), m = __shfl(e, src) - s;
+		for (int64_t i = lane; i < m; i += 64) scratch[s + i] = qlist[s + i];
+		int64_t out = 0, first = 0;
+		for (;;) {
+			// the smallest unconsumed index: its key is the next list's
+			int64_t c = first & ~(int64_t)63;
+			uint64_t av = 0;
+			uint32_t v = BUILD_CONSUMED;
+			for (; c < m; c += 64) {
+				v = c + lane < m ? scratch[s + c + lane] : BUILD_CONSUMED;
+				av = __ballot(v != BUILD_CONSUMED);
+				if (av) break;
+			}
+			if (c >= m) break;
+			first = c + __builtin_ctzll(av);
+			const uint64_t key = keys[(uint32_t)__shfl((int)v, __builtin_ctzll(av))];
+			const int64_t start = out;
+			for (; c < m; c += 64) {
+				const int64_t i = c + lane;
+				const uint32_t x = i < m ? scratch[s + i] : BUILD_CONSUMED;
+				const bool mine = x != BUILD_CONSUMED && keys[x] == key;
+				const uint64_t mb = __ballot(mine);
+				if (mine) {
+					const int64_t o = out + __builtin_popcountll(mb & ((1ull << lane) - 1));
+					qlist[s + o] = x;
+					if (o != start) len[s + o] = 0;
+					scratch[s + i] = BUILD_CONSUMED;
+				}
+				out += __builtin_popcountll(mb);
+			}
+			if (lane == 0) len[s + start] = (uint32_t)(out - start);
+		}
+	}
+}
+
+// Placement of the distinct keys in table order (linear probing): slot = max(home, slot of the key before + 1). Over a stretch of
+// the sorted array this is x -> max(A, x + B) of the slot x of the key before it; the scan composes these functions. A value holds
+// B (keys) in its high word and A + 1 in its low word -- 0: no key, saturated: past every slot.
+struct SeedPlaceOp {
+	__host__ __device__ uint64_t operator()(uint64_t x, uint64_t y) const
+	{
+		const uint32_t ax = (uint32_t)x, ay = (uint32_t)y, by = (uint32_t)(y >> 32);
+		uint32_t v = ax == 0 ? 0u : (ax + by < ax ? 0xffffffffu : ax + by);
+		v = v > ay ? v : ay;
+		return (((x >> 32) + (uint64_t)by) << 32) | v;
+	}
+};
+struct SeedPlaceIn {
+	const uint32_t* len; const uint32_t* top;
+	__host__ __device__ uint64_t operator()(uint32_t j) const { return len[j] ? ((uint64_t)1 << 32) | (uint64_t)(top[j] + 1u) : 0ull; }
+};
+struct SeedPlaceOut {
+	__host__ __device__ uint32_t operator()(uint64_t v) const { return (uint32_t)v; }
+};
+
+// (word, bits) of the sorted elements of a workgroup: every word is OR-reduced over its elements and stored once -- with an atomic
+// only where its elements continue into the workgroup before or after
+__device__ __forceinline__ void build_words(uint32_t* bm, uint32_t w, uint32_t bits, bool edge_lo, bool edge_hi, uint32_t* sw, uint32_t* sb)
+{
+	const int i = threadIdx.x;
+	__syncthreads();
+	sw[i] = w; sb[i] = bits;
+	__syncthreads();
+	if (w == 0xffffffffu || (i > 0 && sw[i - 1] == w)) return;
+	int r = i + 1;
+	uint32_t v = bits;
+	for (; r < (int)blockDim.x && sw[r] == w; ++r) v |= sb[r];
+	const bool shared = (i == 0 && edge_lo) || (r == (int)blockDim.x && edge_hi);
+	if (!shared) bm[w] = v;
+	else if (v) atomicOr(&bm[w], v);
+}
+
+// Per list start of the regrouped order: the key's slot (key, list head, size | LOWC) with plain stores, or -- past the last slot --
+// a note for seed_wrap_kernel; its filter bits, reduced per word
+__global__ __launch_bounds__(256) void seed_build_kernel(SeedArgs a, int sid, const uint64_t* __restrict__ keys, const uint32_t* __restrict__ top, const uint32_t* __restrict__ qlist,
+	const uint32_t* __restrict__ len, const uint32_t* __restrict__ place, uint32_t* __restrict__ ctr, uint32_t* __restrict__ wrap, int64_t n)
+{
+	__shared__ uint32_t sw[256], sb[256];
+	const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	const uint32_t none = 1u << a.slot_bits;
+	const uint32_t t = j < n ? top[j] : none;
+	const uint32_t L = t != none ? len[j] : 0u;
+	uint32_t b1 = 0, b2 = 0;
+	if (L) {
+		const uint32_t x = qlist[j];                      // the list's smallest position
+		const uint64_t key = keys[x];
+		const uint64_t h = seed_hash(key);
+		b1 = bm1_bits((uint32_t)h, a.bitmap1_k3);
+		b2 = 1u << (uint32_t)(h >> 59);
+		// a list of one query position (most seeds): head IS the position -- the probe that finds the slot has it without a second
+		// dependent random read. Search::mask_seeds evaluates the first query position of a joined group (seed_complexity.cpp:97-99):
+		// the smallest. Whether that seed is complex does not depend on the join, so it is decided once here (only the fused stream
+		// needs the answer before the join is known; otherwise seed_mask_kernel asks for the few joined groups).
+		const bool lowc = a.fused && a.params.seed_encoding == SEED_SPACED && !seed_is_complex(a.params, sid, a.qdata + a.q_begin + x);
+		const uint32_t pos = place[j] - 1u;
+		if ((uint64_t)pos <= a.slot_mask) {
+			SeedSlot sl;
+			sl.key = key; sl.head = L == 1 ? x : (uint32_t)j; sl.flags = (L << 8) | (lowc ? SLOT_LOWC : 0u);
+			a.slot(pos) = sl;
+		}
+		else wrap[atomicAdd(&ctr[1], 1u)] = (uint32_t)j;
+	}
+	const int64_t blk0 = (int64_t)blockIdx.x * blockDim.x, blk1 = blk0 + blockDim.x;
+	const bool in = t != none;
+	const uint32_t t_lo = blk0 > 0 ? top[blk0 - 1] : none, t_hi = blk1 < n ? top[blk1] : none;
+	{
+		const uint32_t w = in ? a.bm1_of_top(t) : 0xffffffffu;
+		build_words(a.bitmap1, w, b1, t_lo != none && a.bm1_of_top(t_lo) == w, t_hi != none && a.bm1_of_top(t_hi) == w, sw, sb);
+	}
+	if (a.level2) {
+		const uint32_t w = in ? a.bm2_of_top(t) : 0xffffffffu;
+		build_words(a.bitmap, w, b2, t_lo != none && a.bm2_of_top(t_lo) == w, t_hi != none && a.bm2_of_top(t_hi) == w, sw, sb);
+	}
+}
+
+// The keys whose placement ran past the last slot go in by the linear-probing insertion from slot 0 (every slot from their home to
+// the last one is taken); none at the default sizes
+__global__ __launch_bounds__(256) void seed_wrap_kernel(SeedArgs a, int sid, const uint64_t* __restrict__ keys, const uint32_t* __restrict__ qlist, const uint32_t* __restrict__ len,
+	const uint32_t* __restrict__ ctr, const uint32_t* __restrict__ wrap)
+{
+	const uint32_t nw = ctr[1];
+	for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < nw; k += gridDim.x * blockDim.x) {
+		const uint32_t j = wrap[k], L = len[j], x = qlist[j];
+		const uint64_t key = keys[x];
+		const bool lowc = a.fused && a.params.seed_encoding == SEED_SPACED && !seed_is_complex(a.params, sid, a.qdata + a.q_begin + x);
+		uint64_t slot = 0;
+		while (atomicCAS((unsigned long long*)&a.slot(slot).key, (unsigned long long)SEED_EMPTY, (unsigned long long)key) != (unsigned long long)SEED_EMPTY)
+			slot = (slot + 1) & a.slot_mask;
+		a.slot(slot).head = L == 1 ? x : j;
+		a.slot(slot).flags = (L << 8) | (lowc ? SLOT_LOWC : 0u);
+	}
 }
 
 __global__ void seed_fold_kernel(const int8_t* __restrict__ data, int64_t n, uint8_t* __restrict__ out)
@@ -143,26 +349,6 @@ __global__ void seed_soft_time_kernel(SeedArgs a)
 			if (t < a.mask_time[p]) a.mask_time[p] = t;
 			return;
 		}
-}
-
-// After the query positions have been sorted by slot (stable: ascending position inside a seed): the first element of every
-// group writes the group's start and size into its slot. state = 0 (occupied, not joined), count in bits 8..31.
-__global__ void seed_lists_kernel(SeedArgs a, int sid, const uint32_t* sorted_slot, const uint32_t* qlist, int64_t n)
-{
-	const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= n) return;
-	const uint32_t k = sorted_slot[i];
-	if (k == LIST_END || (i > 0 && sorted_slot[i - 1] == k)) return;
-	int64_t e = i + 1;
-	while (e < n && sorted_slot[e] == k) ++e;
-	// a list of one query position (most seeds): head IS the position -- the probe that finds the slot has it without a second
-	// dependent random read
-	a.slot(k).head = e - i == 1 ? qlist[i] : (uint32_t)i;
-	// Search::mask_seeds evaluates the first query position of a joined group (seed_complexity.cpp:97-99) -- the smallest
-	// position here: the sort is stable. Whether that seed is complex does not depend on the join, so it is decided once here.
-	// (only the fused stream needs the answer before the join is known; otherwise seed_mask_kernel asks for the few joined groups)
-	const bool lowc = a.fused && a.params.seed_encoding == SEED_SPACED && !seed_is_complex(a.params, sid, a.qdata + a.q_begin + qlist[i]);
-	a.slot(k).flags = ((uint32_t)(e - i) << 8) | (lowc ? SLOT_LOWC : 0u);
 }
 
 // Wave-aggregated append: the lanes of the wavefront that have an element reserve their slots with ONE atomic on the
@@ -420,7 +606,7 @@ __global__ __launch_bounds__(256) void seed_stream_fast_kernel(SeedArgs a, int s
 	};
 	auto probe_table = [&](uint64_t seed, int64_t pos) {
 		const uint64_t hh = seed_hash(seed);
-		if (LEVEL2 && !((a.bitmap[(uint32_t)(hh >> 32) & a.bitmap_mask] >> (uint32_t)(hh >> 59)) & 1u)) return;
+		if (LEVEL2 && !((a.bitmap[a.bm2_index((uint32_t)hh, seed)] >> (uint32_t)(hh >> 59)) & 1u)) return;
 		const uint64_t slot = a.home(hh, seed);
 		table_chain(seed, pos, slot, a.slot(slot));
 	};
@@ -1482,23 +1668,27 @@ hipError_t launch_seed_reset(const SeedArgs& a, int sid, hipStream_t st)
 	return hipGetLastError();
 }
 
-hipError_t launch_seed_index(const SeedArgs& a, int sid, hipStream_t st)
-{
-	hipLaunchKernelGGL(seed_index_kernel, dim3(blocks_for(a.q_end - a.q_begin, 256)), dim3(256), 0, st, a, sid);
-	return hipGetLastError();
-}
-
-hipError_t launch_seed_lists(const SeedArgs& a, int sid, uint32_t* sorted_slot, uint32_t* qlist_out, int slot_bits, void** tmp, size_t* tmp_bytes, hipStream_t st)
+hipError_t launch_seed_build(const SeedArgs& a, int sid, uint32_t* qlist, uint32_t* work, uint32_t* top, void** tmp, size_t* tmp_bytes, hipStream_t st)
 {
 	const int64_t n = a.q_end - a.q_begin;
 	if (n <= 0) return hipSuccess;
-	// LIST_END (all ones) must sort last. slot_bits = log2(slots) + 1: every slot number has bit log2(slots) clear, LIST_END has it
-	// set, so the sort may stop there (C2: 24 key bits = three radix passes instead of four)
-	const unsigned end_bit = (unsigned)std::min(32, std::max(1, slot_bits));
-	size_t need = 0;
+	uint32_t* skey = work;                      // sort keys; then the long runs' scratch; then the placement
+	uint32_t* len = work + n;
+	uint32_t* ctr = work + 2 * n;
+	uint32_t* wrap = work + 2 * n + 64;
+	uint64_t* keys = reinterpret_cast<uint64_t*>(work + ((3 * n + 65) & ~(int64_t)1));
+	hipLaunchKernelGGL(seed_order_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, st, a, sid, skey, keys, ctr);
+	// the sentinel 1 << slot_bits must sort last: slot_bits + 1 key bits (C2: 24 = three radix passes)
+	const unsigned end_bit = (unsigned)(a.slot_bits + 1);
 	rocprim::counting_iterator<uint32_t> iota(0);
-	hipError_t e = rocprim::radix_sort_pairs(nullptr, need, a.qslot, sorted_slot, iota, qlist_out, (size_t)n, 0, end_bit, st);
+	rocprim::transform_iterator<rocprim::counting_iterator<uint32_t>, SeedPlaceIn, uint64_t> place_in(iota, SeedPlaceIn{ len, top });
+	rocprim::transform_output_iterator<uint32_t*, SeedPlaceOut> place_out(skey, SeedPlaceOut());
+	size_t need_sort = 0, need_scan = 0;
+	hipError_t e = rocprim::radix_sort_pairs(nullptr, need_sort, skey, top, iota, qlist, (size_t)n, 0, end_bit, st);
 	if (e != hipSuccess) return e;
+	e = rocprim::inclusive_scan(nullptr, need_scan, place_in, place_out, (size_t)n, SeedPlaceOp(), st);
+	if (e != hipSuccess) return e;
+	const size_t need = std::max(need_sort, need_scan);
 	if (need > *tmp_bytes) {
 		if (*tmp) (void)hipFree(*tmp);
 		*tmp = nullptr; *tmp_bytes = 0;
@@ -1506,9 +1696,14 @@ hipError_t launch_seed_lists(const SeedArgs& a, int sid, uint32_t* sorted_slot, 
 		if (e != hipSuccess) return e;
 		*tmp_bytes = need;
 	}
-	e = rocprim::radix_sort_pairs(*tmp, need, a.qslot, sorted_slot, iota, qlist_out, (size_t)n, 0, end_bit, st);
+	e = rocprim::radix_sort_pairs(*tmp, need_sort, skey, top, iota, qlist, (size_t)n, 0, end_bit, st);
 	if (e != hipSuccess) return e;
-	hipLaunchKernelGGL(seed_lists_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, st, a, sid, (const uint32_t*)sorted_slot, (const uint32_t*)qlist_out, n);
+	hipLaunchKernelGGL(seed_group_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, st, a, (const uint64_t*)keys, (const uint32_t*)top, qlist, len, skey, n);
+	e = rocprim::inclusive_scan(*tmp, need_scan, place_in, place_out, (size_t)n, SeedPlaceOp(), st);
+	if (e != hipSuccess) return e;
+	hipLaunchKernelGGL(seed_build_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, st, a, sid, (const uint64_t*)keys, (const uint32_t*)top, (const uint32_t*)qlist,
+		(const uint32_t*)len, (const uint32_t*)skey, ctr, wrap, n);
+	hipLaunchKernelGGL(seed_wrap_kernel, dim3(16), dim3(256), 0, st, a, sid, (const uint64_t*)keys, (const uint32_t*)qlist, (const uint32_t*)len, (const uint32_t*)ctr, (const uint32_t*)wrap);
 	return hipGetLastError();
 }
 

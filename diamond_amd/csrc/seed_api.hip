@@ -282,10 +282,7 @@ struct Timer {
 		(void)hipEventRecord(b, st);
 		spans.push_back(Span{ open, b, &into });
 		open = nullptr;
-		if (waits()) collect();
 	}
-	// DMND_SEED_TIMER_WAITS=1: the clock of rounds 1-4 (a host wait behind every phase), for A/B runs
-	static bool waits() { static const bool v = [] { const char* e = std::getenv("DMND_SEED_TIMER_WAITS"); return e && e[0] == '1'; }(); return v; }
 	// a phase that runs again after an overflow: the spans of the abandoned attempt do not count
 	void discard(const double* into)
 	{
@@ -314,7 +311,7 @@ struct Timer {
 struct SeedSizes {
 	uint64_t slots, bm_words, bm1_words;
 	uint32_t bm1_k3;
-	int stream_nt, probe_policy, SB, slot_shift;
+	int SB, slot_shift;
 	bool fused, reuse;
 	size_t bm_total;
 };
@@ -345,13 +342,11 @@ static SeedSizes seed_sizes(const dmnd_ctx* c, const SeedParams& sp, int64_t nq_
 	int bm1_log2 = 24;
 	if (nq_pos > ((int64_t)1 << 24))
 		while (bm1_log2 < 27 && ((uint64_t)1 << bm1_log2) < (uint64_t)nq_pos * 4) ++bm1_log2;
-	if (tuning().seed_bitmap1_log2) bm1_log2 = tuning().seed_bitmap1_log2;      // word index = 22 bits of hash a
 	uint64_t bm1_words = ((uint64_t)1 << bm1_log2) / 32;
 	if (bm1_words > bm_words) bm1_words = bm_words;
 	uint32_t bm1_k3 = 0;
-	int stream_nt = 0;
 	// Long seeds (level-2 path: nearly every level-1 positive is a false one) with a query block that the default size serves:
-	// 3 MB and three bits per seed. Measured on C2 (3e6 query seeds, tools/stream_sweep.py): the stream kernel takes the same
+	// 3 MB and three bits per seed. Measured on C2 (3e6 query seeds): the stream kernel takes the same
 	// 1.45 ms as with 2 MB / two bits -- its bound is the rate at which the L2s serve 4-byte probes, not the misses behind
 	// them -- but the false positives drop from 9.7 % to 3.1 %, and with them the level-2 / table lines fetched over the fabric
 	// (4 MB: 1.53 ms, 8 MB: 2.56 ms -- the filter has to fit an XCD's 4 MB L2 beside the stream)
@@ -362,12 +357,7 @@ static SeedSizes seed_sizes(const dmnd_ctx* c, const SeedParams& sp, int64_t nq_
 	}
 	// Short seeds by class (round 5 sweep on C3, tools/gpu_r05b.sh): 4 MB / three bits -- half a megabyte per XCD -- instead of 2 MB / two:
 	// stream + filter 103.9 -> 102.6 ms per 16 shapes (8 MB: 103.4; fewer false positives = fewer slot lines fetched over the fabric)
-	if (!long_seeds && bm1_log2 == 24 && !tuning().seed_bitmap1_log2 && bm_words >= 2 * bm1_words) { bm1_words *= 2; bm1_k3 = 1u; }
-	if (tuning().seed_bm1_kb) bm1_words = (uint64_t)tuning().seed_bm1_kb * 256;       // (tuning.h: the sweeps' overrides)
-	if (tuning().seed_bm1_k) bm1_k3 = tuning().seed_bm1_k == 3 ? 1u : 0u;
-	if (tuning().seed_stream_nt >= 0) stream_nt = tuning().seed_stream_nt != 0;
-	int probe_policy = 0;
-	if (tuning().seed_probe_policy >= 0) probe_policy = tuning().seed_probe_policy;
+	if (!long_seeds && bm1_log2 == 24 && bm_words >= 2 * bm1_words) { bm1_words *= 2; bm1_k3 = 1u; }
 	// The fused pipeline finishes a shape before it starts the next one: its table, lists and bitmaps are ONE shape's, reused
 	// (64 shapes of --ultra-sensitive would otherwise hold 8 GB of tables for a 10k-query block)
 	bool fused = seed_stream_can_fuse(sp);
@@ -380,7 +370,7 @@ static SeedSizes seed_sizes(const dmnd_ctx* c, const SeedParams& sp, int64_t nq_
 	const bool reuse = c->reuse_query_index && set_bytes * (size_t)S <= ((size_t)64 << 30) && !getenv("DMND_SEED_MATCHED_CAP");
 	const int SB = (fused && !reuse) ? 1 : S;            // shapes that own buffers at the same time
 	const size_t bm_total = (size_t)SB * (bm_words + bm1_words) * sizeof(uint32_t);
-	z.bm_words = bm_words; z.bm1_words = bm1_words; z.bm1_k3 = bm1_k3; z.stream_nt = stream_nt; z.probe_policy = probe_policy;
+	z.bm_words = bm_words; z.bm1_words = bm1_words; z.bm1_k3 = bm1_k3;
 	z.fused = fused; z.reuse = reuse; z.SB = SB; z.bm_total = bm_total;
 	return z;
 }
@@ -420,6 +410,32 @@ extern "C" int dmnd_seed_reserve(dmnd_ctx* c, const dmnd_seed_params* params, in
 	HIP_TRY(hipSetDevice(c->device));
 	const int64_t nq_pos = query_block_len - 512;             // a SequenceSet block: 256 padding letters on either side
 	return seed_reserve(c, sp, seed_sizes(c, sp, nq_pos), nq_pos, query_block_len - 256, query_block_len, true);
+}
+
+// The tests' hooks that force the overflow / retry paths (DMND_SEED_MATCHED_CAP, _SURVIVOR_CAP, _HIT_CAP, _DEFERRED_CAP): the
+// capacity a buffer starts from, instead of the one computed. Read per call: the tests set them per search.
+static int64_t seed_cap(const char* hook, int64_t computed)
+{
+	const char* e = getenv(hook);
+	return e ? std::max<int64_t>(1, atoll(e)) : computed;
+}
+
+// Pairs scoring above 255 (rare): the second pass that resolves the reference's SIMD-batch saturation rule for the nd deferred
+// pairs of shape sid. The joined positions of the seeds that own one (of the n_matched in a.matched_*) are collected, sorted by
+// (slot, position), and scored again.
+static int seed_deferred_pass(dmnd_ctx* c, SeedArgs a, int sid, int64_t n_matched, int64_t nd, hipStream_t st)
+{
+	if (int rc = c->seed_eslot.ensure((size_t)n_matched * sizeof(uint64_t))) return rc;      // unsorted keys
+	if (int rc = c->seed_eloc.ensure((size_t)n_matched * sizeof(uint64_t))) return rc;       // sorted keys
+	a.e_key = c->seed_eslot.as<uint64_t>();
+	HIP_TRY(launch_seed_collect(a, n_matched, st));
+	unsigned long long ne = 0;
+	HIP_TRY(copy_now(st, &ne, a.e_count, sizeof(ne), hipMemcpyDeviceToHost));
+	HIP_TRY(sort_keys_u64(c->seed_eslot.as<uint64_t>(), c->seed_eloc.as<uint64_t>(), (int64_t)ne, &c->sort_tmp, &c->sort_tmp_bytes, st));
+	a.e_key = c->seed_eloc.as<uint64_t>();
+	a.e_n = (int64_t)ne;
+	HIP_TRY(launch_seed_deferred(a, sid, nd, st));
+	return DMND_OK;
 }
 
 extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int64_t* n_hits)
@@ -473,7 +489,7 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 	if (z.slots > ((uint64_t)1 << 31)) return fail(DMND_E_ARG, "dmnd_seed_search: query block too large for 32-bit slot numbers (more than 1.7 G seed positions): cut it into smaller blocks");
 	const uint64_t slots = z.slots, bm_words = z.bm_words, bm1_words = z.bm1_words;
 	const uint32_t bm1_k3 = z.bm1_k3;
-	const int stream_nt = z.stream_nt, probe_policy = z.probe_policy, SB = z.SB;
+	const int SB = z.SB;
 	const size_t slot_bytes = (size_t)slots << z.slot_shift;      // one shape's table
 	const bool fused = z.fused, reuse = z.reuse;
 	const size_t bm_total = z.bm_total;
@@ -481,15 +497,16 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 	while (((uint64_t)1 << slot_bits) < slots) ++slot_bits;
 	int bm_log2 = 0;
 	while (((uint64_t)1 << bm_log2) < bm_words) ++bm_log2;
-	// key classes (seed_core.h seed_class): the short-seed pipeline, when the geometry allows eighths (DMND_SEED_CLASSES=0: one range)
-	static const bool classes_env = [] { const char* e = getenv("DMND_SEED_CLASSES"); return !e || atoi(e) != 0; }();
+	// key classes (seed_core.h seed_class): the short-seed pipeline, whose stream has no form without them ...
 	// ... and (round 5) long seeds against a query block whose level-1 filter has outgrown an XCD's L2 (above 2^24 query positions the
 	// filter is 4-16 MB: C5's 100 000 queries): by class every XCD probes its own eighth of it. DMND_SEED_CLASSES_LONG=0/1 forces it.
 	const int classes_long_env = [] { const char* e = getenv("DMND_SEED_CLASSES_LONG"); return e ? atoi(e) : -1; }();      // (read per call: the tests switch it)
 	bool nibble_shapes = true;
 	for (int i = 0; i < S; ++i) nibble_shapes = nibble_shapes && seed_nibble_mode(sp, i);
 	const bool classes_long = !fused && nibble_shapes && (classes_long_env >= 0 ? classes_long_env != 0 : SEED_CLASSES_LONG_DEFAULT && bm1_words * 32 >= ((uint64_t)1 << 25));      // (C2's 3 MB filter stays on the plain stream: by class it took 2.57 ms against 1.46)
-	const int classes = (fused ? classes_env : classes_long) && slots >= 64 && bm1_words % 8 == 0 && bm1_words >= 64 ? 8 : 0;
+	const int classes = (fused || classes_long) && slots >= 64 && bm1_words % 8 == 0 && bm1_words >= 64 ? 8 : 0;
+	// (seed_sizes gives every fused search at least 1024 slots and a level-1 filter of 2^k >= 2^15 words)
+	if (fused && !classes) return fail(DMND_E_ARG, "dmnd_seed_search: fused seed search without key classes (table or level-1 filter too small for eighths)");
 	std::string signature;
 	if (reuse) {
 		signature.assign(reinterpret_cast<const char*>(&sp), sizeof(sp));
@@ -520,22 +537,13 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 	bool pristine = true;                                // the counters and the need map are as the clear above left them
 	HIP_TRY(launch_seed_qid(c->d_limits[DMND_QUERY].as<int64_t>(), (int64_t)ql.size() - 1, c->qid_of.as<uint32_t>(), st));
 
-	// fused pipeline: 4-bit copy of the query block for the Hamming pre-filter (DMND_SEED_FOLD=0 switches it off)
-	static const bool fold_env = [] { const char* e = getenv("DMND_SEED_FOLD"); return !e || atoi(e) != 0; }();
-	const bool use_fold = fused && fold_env;
-	if (use_fold) {
-		const int64_t n = c->block_len[DMND_QUERY];
-		if (int rc = c->seed_qfold.ensure((size_t)(n + 1) / 2 + 64)) return rc;
-		HIP_TRY(launch_seed_fold(c->block[DMND_QUERY].as<int8_t>(), n, c->seed_qfold.as<uint8_t>(), st));
-	}
-	// ... and of the reference block for the by-class stream (round 5): eight workgroups on eight XCDs read the letters around the
-	// joins of every tile, each through its own L2 -- from the folded copy that is half the lines (DMND_SEED_TFOLD=0: from the letters)
-	static const bool tfold_env = [] { const char* e = getenv("DMND_SEED_TFOLD"); return !e || atoi(e) != 0; }();
-	const bool use_tfold = use_fold && classes && tfold_env;
-	if (use_tfold) {
-		const int64_t n = c->block_len[DMND_TARGET];
-		if (int rc = c->seed_tfold.ensure((size_t)(n + 1) / 2 + 64)) return rc;
-		HIP_TRY(launch_seed_fold(c->block[DMND_TARGET].as<int8_t>(), n, c->seed_tfold.as<uint8_t>(), st));
+	// fused pipeline: 4-bit copies of the query and the reference block for the Hamming pre-filter
+	if (fused) {
+		const int64_t nq = c->block_len[DMND_QUERY], nt = c->block_len[DMND_TARGET];
+		if (int rc = c->seed_qfold.ensure((size_t)(nq + 1) / 2 + 64)) return rc;
+		if (int rc = c->seed_tfold.ensure((size_t)(nt + 1) / 2 + 64)) return rc;
+		HIP_TRY(launch_seed_fold(c->block[DMND_QUERY].as<int8_t>(), nq, c->seed_qfold.as<uint8_t>(), st));
+		HIP_TRY(launch_seed_fold(c->block[DMND_TARGET].as<int8_t>(), nt, c->seed_tfold.as<uint8_t>(), st));
 	}
 	if (classes) {
 		const int8_t* tseed = (c->soft_valid[DMND_TARGET] && sp.seed_encoding == SEED_SPACED) ? c->soft[DMND_TARGET].as<int8_t>() : c->block[DMND_TARGET].as<int8_t>();
@@ -546,8 +554,6 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 		if (int rc = c->seed_tclass.ensure((size_t)9 * (size_t)((n + 3) & ~(int64_t)3) * sizeof(uint16_t))) return rc;      // planes of a stride that is a multiple of four groups: 8-byte stores
 		HIP_TRY(launch_seed_codes(sp, tseed, t_begin, t_end, c->seed_tcodes.as<uint64_t>(), c->seed_tflags.as<uint32_t>(), c->seed_tplanes.as<uint64_t>(), st));
 	}
-	const int level2_env = [] { const char* e = getenv("DMND_SEED_LEVEL2"); return e ? atoi(e) : -1; }();
-	auto level2_of = [&](int sid) { return level2_env >= 0 ? level2_env : (sp.shape_weight[sid] >= 10 ? 1 : 0); };
 	auto args_for = [&](int sid, int64_t matched_cap, int64_t matched_off) {
 		const int own = sid % SB;                          // which of the SB buffer sets the shape uses
 		SeedArgs a;
@@ -573,7 +579,7 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 		a.tcodes = classes ? c->seed_tcodes.as<uint64_t>() : nullptr; a.tflags = classes ? c->seed_tflags.as<uint32_t>() : nullptr; a.tplanes = classes ? c->seed_tplanes.as<uint64_t>() : nullptr;
 		a.bitmap = c->seed_bitmap.as<uint32_t>() + (size_t)own * (bm_words + bm1_words);
 		a.bitmap1 = a.bitmap + bm_words;
-		a.bitmap1_words = (uint32_t)bm1_words; a.bitmap1_k3 = bm1_k3; a.stream_nt = stream_nt; a.probe_policy = probe_policy;
+		a.bitmap1_words = (uint32_t)bm1_words; a.bitmap1_k3 = bm1_k3;
 		a.matched_slot = c->matched_slot.as<uint32_t>() + matched_off;
 		a.matched_loc = c->matched_loc.as<int64_t>() + matched_off;
 		a.matched_count = c->counters.as<unsigned long long>() + sid;
@@ -586,9 +592,9 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 		a.matrix = c->matrix.as<int8_t>();
 		a.hits = c->seed_hits.as<dmnd_seed_hit>(); a.hit_count = c->counters.as<unsigned long long>() + S; a.hit_cap = 0;
 		a.fused = fused ? 1 : 0;
-		a.level2 = level2_of(sid);
-		a.qfold = use_fold ? c->seed_qfold.as<uint8_t>() : nullptr;
-		a.tfold = use_tfold ? c->seed_tfold.as<uint8_t>() : nullptr;
+		a.level2 = sp.shape_weight[sid] >= 10 ? 1 : 0;
+		a.qfold = fused ? c->seed_qfold.as<uint8_t>() : nullptr;
+		a.tfold = fused ? c->seed_tfold.as<uint8_t>() : nullptr;
 		return a;
 	};
 
@@ -614,12 +620,9 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 	// deferred pairs. A shape's masks only depend on this and earlier shapes, and so does the left-most rule (t_now).
 	if (fused) {
 		unsigned long long* ctr = c->counters.as<unsigned long long>();
-		int64_t m_cap = std::max<int64_t>(std::max<int64_t>((int64_t)1 << 22, 4 * nq_pos), (int64_t)(std::min(c->matched_loc.cap / sizeof(int64_t), c->matched_slot.cap / sizeof(uint32_t))));
-		if (const char* e = getenv("DMND_SEED_MATCHED_CAP")) m_cap = std::max<int64_t>(1, atoll(e));
-		int64_t surv_cap = std::max<int64_t>((int64_t)1 << 20, (int64_t)(c->seed_survivors.cap / sizeof(SeedSurvivor)));
-		if (const char* e = getenv("DMND_SEED_SURVIVOR_CAP")) surv_cap = std::max<int64_t>(1, atoll(e));
-		int64_t hit_cap = std::max<int64_t>((int64_t)1 << 20, (int64_t)(c->seed_hits.cap / sizeof(dmnd_seed_hit)));
-		if (const char* e = getenv("DMND_SEED_HIT_CAP")) hit_cap = std::max<int64_t>(1, atoll(e));
+		int64_t m_cap = seed_cap("DMND_SEED_MATCHED_CAP", std::max<int64_t>(std::max<int64_t>((int64_t)1 << 22, 4 * nq_pos), (int64_t)(std::min(c->matched_loc.cap / sizeof(int64_t), c->matched_slot.cap / sizeof(uint32_t)))));
+		int64_t surv_cap = seed_cap("DMND_SEED_SURVIVOR_CAP", std::max<int64_t>((int64_t)1 << 20, (int64_t)(c->seed_survivors.cap / sizeof(SeedSurvivor))));
+		int64_t hit_cap = seed_cap("DMND_SEED_HIT_CAP", std::max<int64_t>((int64_t)1 << 20, (int64_t)(c->seed_hits.cap / sizeof(dmnd_seed_hit))));
 		if (int rc = c->seed_hits.ensure((size_t)hit_cap * sizeof(dmnd_seed_hit))) return rc;
 		c->seed_trace.assign((size_t)2 * S, 0);
 		int64_t hits_bound = 0;                              // every survivor gives at most one hit
@@ -667,18 +670,8 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 			const unsigned long long nd = both[1];
 			c->seed_trace[S + sid] = nd;
 			if (nd == 0) { hits_seen = both[0]; hits_fresh = true; return DMND_OK; }
-			if (int rc = c->seed_eslot.ensure((size_t)n * sizeof(uint64_t))) return rc;
-			if (int rc = c->seed_eloc.ensure((size_t)n * sizeof(uint64_t))) return rc;
-			a.e_key = c->seed_eslot.as<uint64_t>();
 			tmb.start();
-			HIP_TRY(launch_seed_collect(a, (int64_t)n, sb));
-			unsigned long long ne = 0;
-			HIP_TRY(hipMemcpyAsync(&ne, a.e_count, sizeof(ne), hipMemcpyDeviceToHost, sb));
-			HIP_TRY(sync_stream(sb));
-			HIP_TRY(sort_keys_u64(c->seed_eslot.as<uint64_t>(), c->seed_eloc.as<uint64_t>(), (int64_t)ne, &c->sort_tmp, &c->sort_tmp_bytes, sb));
-			a.e_key = c->seed_eloc.as<uint64_t>();
-			a.e_n = (int64_t)ne;
-			HIP_TRY(launch_seed_deferred(a, sid, (int64_t)nd, sb));
+			if (int rc = seed_deferred_pass(c, a, sid, (int64_t)n, (int64_t)nd, sb)) return rc;
 			tmb.stop(c->seed_ms[3]);
 			return DMND_OK;
 		};
@@ -740,8 +733,7 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 	// phase 1: index + stream + mask, every shape. The joined-position lists of all shapes share one buffer.
 	std::vector<int64_t> m_off((size_t)S + 1, 0);
 	// start from what earlier calls already grew the buffers to: a repeated search of the same scale never takes the overflow path
-	int64_t cap_total = std::max<int64_t>(std::max<int64_t>((int64_t)1 << 22, 4 * nq_pos), (int64_t)std::min(c->matched_loc.cap / sizeof(int64_t), c->matched_slot.cap / sizeof(uint32_t)));
-	if (const char* e = getenv("DMND_SEED_MATCHED_CAP")) cap_total = std::max<int64_t>(1, atoll(e));      // tests: force the overflow/retry path
+	int64_t cap_total = seed_cap("DMND_SEED_MATCHED_CAP", std::max<int64_t>(std::max<int64_t>((int64_t)1 << 22, 4 * nq_pos), (int64_t)std::min(c->matched_loc.cap / sizeof(int64_t), c->matched_slot.cap / sizeof(uint32_t))));
 	for (int attempt = 0;; ++attempt) {
 		if (int rc = c->matched_slot.ensure((size_t)cap_total * sizeof(uint32_t))) return rc;
 		if (int rc = c->matched_loc.ensure((size_t)cap_total * sizeof(int64_t))) return rc;
@@ -790,10 +782,8 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 	}
 	lap("phase 1 done (index, stream, mask of every shape)");
 	// phase 2: pair filter per shape; hit and deferred-pair buffers grow on overflow
-	int64_t hit_cap = std::max<int64_t>(std::max<int64_t>((int64_t)1 << 20, m_off[S] / 8), (int64_t)(c->seed_hits.cap / sizeof(dmnd_seed_hit)));
-	if (const char* e = getenv("DMND_SEED_HIT_CAP")) hit_cap = std::max<int64_t>(1, atoll(e));
-	int64_t def_cap = std::max<int64_t>((int64_t)1 << 18, (int64_t)(c->seed_deferred.cap / sizeof(SeedDeferred)));
-	if (const char* e = getenv("DMND_SEED_DEFERRED_CAP")) def_cap = std::max<int64_t>(1, atoll(e));
+	int64_t hit_cap = seed_cap("DMND_SEED_HIT_CAP", std::max<int64_t>(std::max<int64_t>((int64_t)1 << 20, m_off[S] / 8), (int64_t)(c->seed_hits.cap / sizeof(dmnd_seed_hit))));
+	int64_t def_cap = seed_cap("DMND_SEED_DEFERRED_CAP", std::max<int64_t>((int64_t)1 << 18, (int64_t)(c->seed_deferred.cap / sizeof(SeedDeferred))));
 	for (int attempt = 0;; ++attempt) {
 		if (int rc = c->seed_hits.ensure((size_t)hit_cap * sizeof(dmnd_seed_hit))) return rc;
 		if (int rc = c->seed_deferred.ensure((size_t)def_cap * sizeof(SeedDeferred))) return rc;
@@ -831,8 +821,7 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 			}
 			// Hamming filter -> survivor list -> stage-2 kernels
 			{
-				int64_t surv_cap = std::max<int64_t>(std::max<int64_t>((int64_t)1 << 20, tiled ? 2 * (int64_t)counts[sid] : (int64_t)counts[sid]), (int64_t)(c->seed_survivors.cap / sizeof(SeedSurvivor)));
-				if (const char* e = getenv("DMND_SEED_SURVIVOR_CAP")) surv_cap = std::max<int64_t>(1, atoll(e));
+				int64_t surv_cap = seed_cap("DMND_SEED_SURVIVOR_CAP", std::max<int64_t>(std::max<int64_t>((int64_t)1 << 20, tiled ? 2 * (int64_t)counts[sid] : (int64_t)counts[sid]), (int64_t)(c->seed_survivors.cap / sizeof(SeedSurvivor))));
 				unsigned long long ns = 0;
 				for (int pass = 0;; ++pass) {
 					if (int rc = c->seed_survivors.ensure((size_t)surv_cap * sizeof(SeedSurvivor))) return rc;
@@ -865,18 +854,8 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 			if (nd == 0) { hits_seen = both[0]; hits_fresh = true; continue; }
 			def_max = std::max(def_max, nd);
 			if ((int64_t)nd > def_cap) { def_overflow = true; continue; }
-			if (int rc = c->seed_eslot.ensure((size_t)counts[sid] * sizeof(uint64_t))) return rc;      // unsorted keys
-			if (int rc = c->seed_eloc.ensure((size_t)counts[sid] * sizeof(uint64_t))) return rc;       // sorted keys
-			a.e_key = c->seed_eslot.as<uint64_t>();
 			tm.start();
-			HIP_TRY(launch_seed_collect(a, (int64_t)counts[sid], st));
-			unsigned long long ne = 0;
-			HIP_TRY(hipMemcpyAsync(&ne, a.e_count, sizeof(ne), hipMemcpyDeviceToHost, st));
-			HIP_TRY(sync_stream(st));
-			HIP_TRY(sort_keys_u64(c->seed_eslot.as<uint64_t>(), c->seed_eloc.as<uint64_t>(), (int64_t)ne, &c->sort_tmp, &c->sort_tmp_bytes, st));
-			a.e_key = c->seed_eloc.as<uint64_t>();
-			a.e_n = (int64_t)ne;
-			HIP_TRY(launch_seed_deferred(a, sid, (int64_t)nd, st));
+			if (int rc = seed_deferred_pass(c, a, sid, (int64_t)counts[sid], (int64_t)nd, st)) return rc;
 			tm.stop(c->seed_ms[3]);
 		}
 		unsigned long long nh = hits_seen;

@@ -48,7 +48,7 @@ struct SeedArgs {
 	__host__ __device__ SeedSlot& slot(uint64_t i) const { return *reinterpret_cast<SeedSlot*>(reinterpret_cast<char*>(slots) + (i << slot_shift)); }
 	const uint32_t* qlist;                        // query positions grouped by seed, ascending in each group (SeedSlot::head = start, count in flags >> 8)
 	uint64_t slot_mask;
-	int classes;                                  // 8: slots and level-1 words are partitioned by seed_class(key) (short-seed pipeline); 0: one range
+	int classes;                                  // 8: slots and level-1 words are partitioned by seed_class(key) (always when fused); 0: one range
 	// ... and then the reference letters as the stream wants them, made once per search by seed_codes_kernel: per group of 16
 	// letters (from t_begin rounded down to 16) their class nibbles, and delimiter / no-class maps (low / high 16 bits)
 	const uint64_t* tcodes; const uint32_t* tflags;
@@ -75,8 +75,6 @@ struct SeedArgs {
 	// stream probes it once per position), level 2 (>= 16 bits per query seed) filters level-1 false positives before
 	// the open-addressing table is touched
 	uint32_t* bitmap1; uint32_t bitmap1_words, bitmap1_k3;      // level-1 filter (seed_core.h bm1_word / bm1_bits)
-	int probe_policy;                                           // cache policy of the level-1 probes (seed_kernels.hip bm1_probe)
-	int stream_nt;                                              // reference letters are loaded non-temporally (they are read once)
 	uint32_t* bitmap;                                           // level 2: word bm2_index, bit seed_hash_b >> 27
 	// joined reference positions of this shape
 	uint32_t* matched_slot; int64_t* matched_loc; unsigned long long* matched_count; int64_t matched_cap;
@@ -91,9 +89,9 @@ struct SeedArgs {
 	const int8_t* matrix;                         // 32x32 int8 substitution matrix (HBM) for the stage-2 ungapped window score
 	// output
 	dmnd_seed_hit* hits; unsigned long long* hit_count; int64_t hit_cap;
-	const uint8_t* qfold;                         // fused pipeline: the query block with 4 bits per letter (letter & 15), or NULL: pre-filter of the Hamming test
-	const uint8_t* tfold;                         // by-class stream: the reference block folded the same way, or NULL (the window is folded from the letters)
-	int level2;                                   // the level-2 bitmap is filled and consulted (long seeds)
+	const uint8_t* qfold;                         // fused pipeline: the query block with 4 bits per letter (letter & 15), pre-filter of the Hamming test; else NULL
+	const uint8_t* tfold;                         // fused pipeline: the reference block folded the same way; else NULL
+	int level2;                                   // the level-2 bitmap is filled and consulted (long seeds: shape weight >= 10)
 	int fused;                                    // short-seed pipeline: seed_build_kernel decides SLOT_LOWC for every group (the stream needs it)
 };
 
@@ -108,9 +106,8 @@ struct SeedClear {
 };
 hipError_t launch_seed_clear(const SeedClear& z, hipStream_t st);
 hipError_t launch_seed_qid(const int64_t* limits, int64_t n_seqs, uint32_t* qid_of, hipStream_t st);
-// room for the folded need map that seed_collect's workgroups keep in LDS (2^13 words = 32 KB by default, up to 2^15); it lies behind
-// SeedArgs::need_bits
-enum { SEED_NEED_FOLD_WORDS = 32768 };
+// the folded need map that seed_collect's workgroups keep in LDS (2^13 words = 32 KB); it lies behind SeedArgs::need_bits
+enum { SEED_NEED_FOLD_WORDS = 8192 };
 // query seed positions whose shape window touches a soft-masked stretch get their mask time (MaskingTable::remove's bit mask)
 hipError_t launch_seed_soft_time(const SeedArgs& a, hipStream_t st);
 // Builds the query side of shape sid -- table, position lists (qlist_out, which a.qlist reads) and both filters -- from ONE stable radix sort of the

@@ -17,6 +17,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "seed_core.h"
+#include <algorithm>
+#include <cstdlib>
 #include <cstring>
 #include <cstdio>
 #include <rocprim/device/device_radix_sort.hpp>
@@ -25,7 +27,6 @@
 #include <rocprim/iterator/transform_output_iterator.hpp>
 #include <rocprim/device/device_scan.hpp>
 #include "seed_kernels.h"
-#include "tuning.h"
 
 namespace dmnd {
 
@@ -426,52 +427,15 @@ __device__ __forceinline__ uint32_t reduce4(uint32_t letter, uint64_t map_lo, ui
 // start and size) in LDS; then every thread takes staged joins in turn and filters their lists -- all lanes busy and as many
 // independent loads in flight as there are lanes, instead of a chain of dependent loads in the few lanes that found a join.
 // Lists longer than LIGHT are filtered by the whole workgroup. Pairs of a non-complex seed (SLOT_LOWC) are dropped: the seed
-// only gets its JOINED mark for seed_mask_kernel.
-// One probe of the level-1 filter. What bounds the stream is not the number of probes but the bytes they pull out of L2: a
-// plain load of a 4-byte word fills a whole 128-byte line of the CU's vector L1 (3e8 probes = 38 GB per launch, 3/4 of what
-// the L2s can deliver), and the line is never used again. POLICY selects the cache policy of the buffer load (aux bits:
-// 1 = sc0, 2 = nt, 16 = sc1; sc1 / nt loads are served by L2 without an L1 fill).
-template<int POLICY>
-__device__ __forceinline__ uint32_t bm1_probe(__amdgpu_buffer_rsrc_t rsrc, const uint32_t* base, uint32_t word)
-{
-	if (POLICY == 0) return base[word];
-	return (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rsrc, word * 4u, 0, POLICY);
-}
-__device__ __forceinline__ uint32_t bm1_probe_any(int policy, __amdgpu_buffer_rsrc_t rsrc, const uint32_t* base, uint32_t word)
-{
-	switch (policy) {
-	case 1: return bm1_probe<1>(rsrc, base, word);
-	case 2: return bm1_probe<2>(rsrc, base, word);
-	case 3: return bm1_probe<3>(rsrc, base, word);
-	case 16: return bm1_probe<16>(rsrc, base, word);
-	case 17: return bm1_probe<17>(rsrc, base, word);
-	case 18: return bm1_probe<18>(rsrc, base, word);
-	default: return bm1_probe<0>(rsrc, base, word);
-	}
-}
-
-// Loads of data that a workgroup reads once (the reference letters, their class nibbles and window maps) with the non-temporal
-// hint: the lines are still filled, but first in line for eviction -- the L2's capacity is wanted for the query side, which every
-// workgroup of an XCD comes back to (SeedArgs::stream_nt, DMND_SEED_STREAM_NT)
-template<typename T>
-__device__ __forceinline__ T stream_load(const T* p, int nt) { return nt ? __builtin_nontemporal_load(p) : *p; }
-__device__ __forceinline__ void window_load(uint32_t (&tw)[12], const int8_t* p, int nt)
-{
-	if (!nt) { __builtin_memcpy(tw, p, 48); return; }
-	typedef uint32_t u32x4_u __attribute__((ext_vector_type(4), aligned(1)));
-#pragma unroll
-	for (int k = 0; k < 3; ++k) {
-		const u32x4_u v = __builtin_nontemporal_load(reinterpret_cast<const u32x4_u*>(p + 16 * k));
-		tw[4 * k] = v.x; tw[4 * k + 1] = v.y; tw[4 * k + 2] = v.z; tw[4 * k + 3] = v.w;
-	}
-}
-
+// only gets its JOINED mark for seed_mask_kernel. FUSED implies BYCLASS: seed_api.hip fails a fused search whose geometry
+// has no key classes.
 enum { SEED_CLASS_TILES = 4 };      // tiles of 4096 window starts per class workgroup (kernel and launch)
 // DMND_SEED_PHASES=1 (SeedArgs::phase_ticks): thread 0 of every workgroup adds the 100 MHz ticks between its phase boundaries
 #define PHASE_MARK(i) do { if (a.phase_ticks && threadIdx.x == 0) { const uint64_t now_ = wall_clock64(); atomicAdd(&a.phase_ticks[i], (unsigned long long)(now_ - phase_t_)); phase_t_ = now_; } } while (0)
 template<bool LEVEL2, bool HASHED, bool FUSED, bool BYCLASS = false>
 __global__ __launch_bounds__(256) void seed_stream_fast_kernel(SeedArgs a, int sid, uint64_t map_lo, uint64_t map_hi, int64_t base, uint64_t care64)
 {
+	static_assert(!FUSED || BYCLASS, "the fused stream runs by key class");
 	// Joined positions are staged in LDS and flushed with ONE atomic on the shared counter per workgroup: an atomicAdd per
 	// match on a single address serialises at ~4.5 ns each (measured: 3.3 M matches = 14.8 ms per shape in default mode,
 	// 22 M = 98 ms per shape in --sensitive), which dwarfed the 1.6 ms stream itself.
@@ -479,13 +443,13 @@ __global__ __launch_bounds__(256) void seed_stream_fast_kernel(SeedArgs a, int s
 	// (the direct-append fallback cost more than the whole rest of the kernel); positions are staged as 16-bit offsets.
 	// (BYCLASS: a workgroup time is spent waiting for memory, phase after phase, and the kernel's time is the sum of the workgroup times
 	// over the workgroups a CU holds -- which LDS decides: 58 KB allowed 2, these sizes allow 8, as many as the 62 VGPRs do)
-	constexpr unsigned STAGE = BYCLASS ? 768 : LEVEL2 ? 1024 : (FUSED ? 2048 : 4096);
+	constexpr unsigned STAGE = BYCLASS ? 768 : LEVEL2 ? 1024 : 4096;
 	__shared__ uint32_t st_slot[STAGE];
 	__shared__ uint16_t st_loc[STAGE];
 	__shared__ unsigned st_n;
 	__shared__ unsigned long long st_base;
 	constexpr uint32_t LIGHT = 8;
-	constexpr unsigned SURV = FUSED ? (BYCLASS ? 128 : 512) : 1, HEAVY = FUSED ? (BYCLASS ? 64 : 128) : 1, FSTAGE = FUSED ? STAGE : 1;
+	constexpr unsigned SURV = FUSED ? 128 : 1, HEAVY = FUSED ? 64 : 1, FSTAGE = FUSED ? STAGE : 1;
 	__shared__ uint32_t st_head[FSTAGE];
 	__shared__ uint16_t st_count[FSTAGE];                    // saturated: a list that long is read back from its slot
 	__shared__ uint32_t sv_slot[SURV], sv_x[SURV];
@@ -502,8 +466,7 @@ __global__ __launch_bounds__(256) void seed_stream_fast_kernel(SeedArgs a, int s
 	if (threadIdx.x == 0) { st_n = 0; sv_n = 0; hv_n = 0; cq_n = 0; pq_n = 0; pr_n = 0; }
 	__syncthreads();
 	PHASE_MARK(0);
-	const __amdgpu_buffer_rsrc_t bm1_rsrc = __builtin_amdgcn_make_buffer_rsrc(a.bitmap1, 0, (int)(a.bitmap1_words * 4u), 0x00020000);
-	// (FUSED, a.classes: eight workgroups per tile of 4096 positions, each looking at the windows of one key class only -- its own:
+	// (BYCLASS: eight workgroups per tile of 4096 positions, each looking at the windows of one key class only -- its own:
 	// workgroup w is dispatched to XCD w mod 8, which is all the affinity there is; the result does not depend on it)
 	constexpr bool by_class = BYCLASS;
 	const uint32_t my_class = by_class ? blockIdx.x & 7u : 0u;
@@ -521,61 +484,41 @@ __global__ __launch_bounds__(256) void seed_stream_fast_kernel(SeedArgs a, int s
 			if (idx < (unsigned long long)a.survivor_cap) a.survivors[idx] = SeedSurvivor{ slot, x, pos };
 		}
 	};
-	// Hamming filter of the reference window at pos against the entries first, first + step, ... of a list of query positions
+	// Hamming filter of the reference window at pos against the entries first, first + step, ... of a list of query positions.
+	// Pre-filter on letters folded to 4 bits (letter & 15: equal letters stay equal, so the folded identity count is an upper
+	// bound of the real one): the query side is read from a 1.5 MB array with two 16-byte requests per pair instead of three
+	// from the 3 MB block, which is what this kernel is short of (L2 capacity and fabric reads); the reference side from its
+	// folded copy too, half the lines of the letters for the eight class workgroups that read around every tile's joins. The
+	// ~2 % of the pairs that pass are counted exactly on the letters.
 	auto filter_list = [&](uint32_t slot, uint32_t head, uint32_t count, int64_t pos, uint32_t first, uint32_t step) {
-		uint32_t tw[12];
-		const bool folded_ref = BYCLASS && a.qfold && a.tfold;      // the letters themselves are only read for the pairs that pass the pre-filter
-		if (!folded_ref) window_load(tw, a.tdata + pos - 16, BYCLASS ? a.stream_nt : 0);
-		if (a.qfold) {
-			// Pre-filter on letters folded to 4 bits (letter & 15: equal letters stay equal, so the folded identity count is an upper
-			// bound of the real one): the query side is read from a 1.5 MB array with two 16-byte requests per pair instead of three
-			// from the 3 MB block, which is what this kernel is short of (L2 capacity and fabric reads); the ~2 % that pass are
-			// counted exactly on the letters.
-			uint32_t tf[6];
-			if (folded_ref) {
-				const int64_t t0 = pos - 16;
-				typedef uint32_t u32x4_u __attribute__((ext_vector_type(4), aligned(1)));
-				const u32x4_u* src = reinterpret_cast<const u32x4_u*>(a.tfold + (t0 >> 1));
-				const u32x4_u r0 = a.stream_nt ? __builtin_nontemporal_load(src) : src[0], r1 = a.stream_nt ? __builtin_nontemporal_load(src + 1) : src[1];
-				const uint32_t raw[8] = { r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w };
-				const uint32_t sh = (uint32_t)(t0 & 1) * 4;
+		uint32_t tw[12], tf[6];
+		{
+			const int64_t t0 = pos - 16;
+			typedef uint32_t u32x4_u __attribute__((ext_vector_type(4), aligned(1)));
+			const u32x4_u* src = reinterpret_cast<const u32x4_u*>(a.tfold + (t0 >> 1));
+			const u32x4_u r0 = src[0], r1 = src[1];
+			const uint32_t raw[8] = { r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w };
+			const uint32_t sh = (uint32_t)(t0 & 1) * 4;
 #pragma unroll
-				for (int w = 0; w < 6; ++w) tf[w] = __builtin_amdgcn_alignbit(raw[w + 1], raw[w], sh);
-			}
-			else {
-#pragma unroll
-				for (int w = 0; w < 6; ++w) {
-					uint32_t lo = tw[2 * w] & 0x0f0f0f0fu, hi = tw[2 * w + 1] & 0x0f0f0f0fu;
-					lo = (lo | (lo >> 4)) & 0x00ff00ffu; lo = (lo | (lo >> 8)) & 0xffffu;
-					hi = (hi | (hi >> 4)) & 0x00ff00ffu; hi = (hi | (hi >> 8)) & 0xffffu;
-					tf[w] = lo | (hi << 16);
-				}
-			}
-			for (uint32_t i = first; i < count; i += step) {
-				const uint32_t x = count == 1 ? head : a.qlist[head + i];
-				const int64_t x0 = a.q_begin + (int64_t)x - 16;
-				uint32_t raw[8];
-				__builtin_memcpy(raw, a.qfold + (x0 >> 1), 32);
-				const uint32_t sh = (uint32_t)(x0 & 1) * 4;
-				int mism = 0;
-#pragma unroll
-				for (int w = 0; w < 6; ++w) {
-					const uint32_t qf = __builtin_amdgcn_alignbit(raw[w + 1], raw[w], sh);
-					const uint32_t d = tf[w] ^ qf;
-					mism += __builtin_popcount((((d & 0x77777777u) + 0x77777777u) | d) & 0x88888888u);
-				}
-				if (48 - mism < a.params.hamming_filter_id) continue;
-				uint32_t qw[12];
-				__builtin_memcpy(qw, a.qdata + x0, 48);
-				if (folded_ref) __builtin_memcpy(tw, a.tdata + pos - 16, 48);
-				if (window_identity(tw, qw) >= a.params.hamming_filter_id) survive(slot, x, pos);
-			}
-			return;
+			for (int w = 0; w < 6; ++w) tf[w] = __builtin_amdgcn_alignbit(raw[w + 1], raw[w], sh);
 		}
 		for (uint32_t i = first; i < count; i += step) {
 			const uint32_t x = count == 1 ? head : a.qlist[head + i];
+			const int64_t x0 = a.q_begin + (int64_t)x - 16;
+			uint32_t raw[8];
+			__builtin_memcpy(raw, a.qfold + (x0 >> 1), 32);
+			const uint32_t sh = (uint32_t)(x0 & 1) * 4;
+			int mism = 0;
+#pragma unroll
+			for (int w = 0; w < 6; ++w) {
+				const uint32_t qf = __builtin_amdgcn_alignbit(raw[w + 1], raw[w], sh);
+				const uint32_t d = tf[w] ^ qf;
+				mism += __builtin_popcount((((d & 0x77777777u) + 0x77777777u) | d) & 0x88888888u);
+			}
+			if (48 - mism < a.params.hamming_filter_id) continue;
 			uint32_t qw[12];
-			__builtin_memcpy(qw, a.qdata + a.q_begin + x - 16, 48);
+			__builtin_memcpy(qw, a.qdata + x0, 48);
+			__builtin_memcpy(tw, a.tdata + pos - 16, 48);
 			if (window_identity(tw, qw) >= a.params.hamming_filter_id) survive(slot, x, pos);
 		}
 	};
@@ -621,7 +564,7 @@ __global__ __launch_bounds__(256) void seed_stream_fast_kernel(SeedArgs a, int s
 			const int64_t p = wg_base + off;
 			const int64_t g = (p - base) >> 4;
 			const int sh = (int)(p & 15) * 4;                             // base and wg_base are multiples of 16
-			const uint64_t c0 = stream_load(a.tcodes + g, a.stream_nt), c1 = stream_load(a.tcodes + g + 1, a.stream_nt);
+			const uint64_t c0 = a.tcodes[g], c1 = a.tcodes[g + 1];
 			return (sh == 0 ? c0 : (c0 >> sh) | (c1 << (64 - sh))) & care64;
 		};
 		// which of a group's 16 windows are valid and of this class: seed_classify_kernel's answer for this shape (one bit per window);
@@ -631,7 +574,7 @@ __global__ __launch_bounds__(256) void seed_stream_fast_kernel(SeedArgs a, int s
 		for (int sub = 0; sub < CLASS_TILES; ++sub) {
 			const int64_t p0 = wg_base + ((int64_t)sub * 256 + threadIdx.x) * 16;
 			const int64_t g = (p0 - base) >> 4;
-			maps[sub] = p0 < a.t_end ? stream_load(a.tclass + (int64_t)my_class * a.tclass_stride + g, a.stream_nt) : 0u;
+			maps[sub] = p0 < a.t_end ? a.tclass[(int64_t)my_class * a.tclass_stride + g] : 0u;
 			specials[sub] = HASHED && p0 < a.t_end && ((uint32_t)g & 7u) == my_class ? a.tclass[8 * a.tclass_stride + g] : 0u;
 		}
 #pragma unroll
@@ -681,7 +624,7 @@ __global__ __launch_bounds__(256) void seed_stream_fast_kernel(SeedArgs a, int s
 				if (k < n_cq) {
 					const uint64_t key = key_at(off[j]);
 					const uint32_t h = seed_hash_a(key);
-					bw[j] = bm1_probe_any(a.probe_policy, bm1_rsrc, a.bitmap1, a.bm1_index(h, key));
+					bw[j] = a.bitmap1[a.bm1_index(h, key)];
 					need[j] = bm1_bits(h, a.bitmap1_k3);
 				}
 			}
@@ -716,15 +659,7 @@ __global__ __launch_bounds__(256) void seed_stream_fast_kernel(SeedArgs a, int s
 	}
 	else if (in_range) {
 	typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-	u32x4 v0, v1;
-	if (a.stream_nt) {
-		v0 = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(a.tseed + p0));
-		v1 = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(a.tseed + p0 + 16));
-	}
-	else {
-		v0 = *reinterpret_cast<const u32x4*>(a.tseed + p0);
-		v1 = *reinterpret_cast<const u32x4*>(a.tseed + p0 + 16);
-	}
+	const u32x4 v0 = *reinterpret_cast<const u32x4*>(a.tseed + p0), v1 = *reinterpret_cast<const u32x4*>(a.tseed + p0 + 16);
 	const uint32_t w[8] = { v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w };
 	uint64_t codes[2] = { 0, 0 };
 	uint32_t delim = 0, bad = 0;
@@ -761,7 +696,7 @@ __global__ __launch_bounds__(256) void seed_stream_fast_kernel(SeedArgs a, int s
 			const bool ok = inside && ((bad >> w0) & (HASHED ? span : care)) == 0;
 			if (HASHED && inside && !ok) special |= 1u << w0;
 			const uint32_t h = seed_hash_a(key[i]);                              // hash b is only needed past level 1
-			const uint32_t bw = ok ? bm1_probe_any(a.probe_policy, bm1_rsrc, a.bitmap1, a.bm1_index(h, key[i])) : 0u;
+			const uint32_t bw = ok ? a.bitmap1[a.bm1_index(h, key[i])] : 0u;
 			const uint32_t need = bm1_bits(h, a.bitmap1_k3);
 			word[i] = (bw & need) == need ? 1u : 0u;
 		}
@@ -803,7 +738,6 @@ __global__ __launch_bounds__(256) void seed_stream_fast_kernel(SeedArgs a, int s
 				filter_list(st_slot[k], st_head[k], count, wg_base + st_loc[k], 0, 1);
 				continue;
 			}
-			if (!BYCLASS) { filter_list(st_slot[k], st_head[k], count, wg_base + st_loc[k], 0, 1); continue; }
 			const unsigned at = atomicAdd(&pr_n, count);
 			if (at + count <= PAIRS) for (uint32_t i = 0; i < count; ++i) pr[at + i] = (uint16_t)((k << 3) | i);
 			else {                                                    // no room: on the spot (the slots of the reservation that exist are voided)
@@ -1714,10 +1648,18 @@ bool seed_stream_can_fuse(const SeedParams& c)
 	return true;
 }
 
+// seed_stream_fast_kernel<LEVEL2, HASHED, FUSED, BYCLASS> for either seed encoding
+template<bool LEVEL2, bool FUSED, bool BYCLASS>
+static void launch_stream_fast(const SeedArgs& a, int sid, dim3 grid, hipStream_t st, uint64_t lo, uint64_t hi, int64_t base, uint64_t care64)
+{
+	if (a.params.seed_encoding == SEED_HASHED) hipLaunchKernelGGL((seed_stream_fast_kernel<LEVEL2, true, FUSED, BYCLASS>), grid, dim3(256), 0, st, a, sid, lo, hi, base, care64);
+	else hipLaunchKernelGGL((seed_stream_fast_kernel<LEVEL2, false, FUSED, BYCLASS>), grid, dim3(256), 0, st, a, sid, lo, hi, base, care64);
+}
+
 hipError_t launch_seed_stream(const SeedArgs& a, int sid, hipStream_t st, bool fused)
 {
 	const SeedParams& c = a.params;
-	if (fused && !(seed_nibble_mode(c, sid) && c.shape_weight[sid] < 10)) return hipErrorInvalidValue;
+	if (fused && !(seed_nibble_mode(c, sid) && c.shape_weight[sid] < 10 && a.classes)) return hipErrorInvalidValue;
 	if (seed_nibble_mode(c, sid)) {
 		// 4-bit class map: 15 = invalid (X, '*'); every other letter code -> its reduced class
 		uint64_t lo = 0, hi = 0;
@@ -1730,7 +1672,7 @@ hipError_t launch_seed_stream(const SeedArgs& a, int sid, hipStream_t st, bool f
 		uint64_t care64 = 0;
 		for (int k = 0; k < c.shape_weight[sid]; ++k) care64 |= (uint64_t)15 << (4 * c.shape_pos[sid][k]);
 		const bool level2 = a.level2 != 0, hashed = c.seed_encoding == SEED_HASHED;
-		const dim3 grid(a.classes ? blocks_for(threads, 256 * SEED_CLASS_TILES) * 8u : blocks_for(threads, 256)), block(256);
+		const dim3 grid(a.classes ? blocks_for(threads, 256 * SEED_CLASS_TILES) * 8u : blocks_for(threads, 256));
 		const bool by_class = a.classes != 0;               // the fused pipeline, or long seeds against a large query block (seed_api.hip)
 		if (by_class) {
 			const int64_t n_groups = seed_code_groups(a.t_begin, a.t_end);
@@ -1768,18 +1710,13 @@ hipError_t launch_seed_stream(const SeedArgs& a, int sid, hipStream_t st, bool f
 			}
 			hipLaunchKernelGGL(seed_classify_kernel, dim3(blocks_for((n_groups + 3) / 4, 256)), dim3(256), 0, st, a, sid, base, n_groups, cc, hashed ? 1 : 0, const_cast<uint16_t*>(a.tclass));
 		}
-		if (fused && a.classes && hashed) hipLaunchKernelGGL((seed_stream_fast_kernel<false, true, true, true>), grid, block, 0, st, a, sid, lo, hi, base, care64);
-		else if (fused && a.classes) hipLaunchKernelGGL((seed_stream_fast_kernel<false, false, true, true>), grid, block, 0, st, a, sid, lo, hi, base, care64);
-		else if (fused && hashed) hipLaunchKernelGGL((seed_stream_fast_kernel<false, true, true>), grid, block, 0, st, a, sid, lo, hi, base, care64);
-		else if (fused) hipLaunchKernelGGL((seed_stream_fast_kernel<false, false, true>), grid, block, 0, st, a, sid, lo, hi, base, care64);
-		else if (by_class && level2 && hashed) hipLaunchKernelGGL((seed_stream_fast_kernel<true, true, false, true>), grid, block, 0, st, a, sid, lo, hi, base, care64);
-		else if (by_class && level2) hipLaunchKernelGGL((seed_stream_fast_kernel<true, false, false, true>), grid, block, 0, st, a, sid, lo, hi, base, care64);
-		else if (by_class && hashed) hipLaunchKernelGGL((seed_stream_fast_kernel<false, true, false, true>), grid, block, 0, st, a, sid, lo, hi, base, care64);
-		else if (by_class) hipLaunchKernelGGL((seed_stream_fast_kernel<false, false, false, true>), grid, block, 0, st, a, sid, lo, hi, base, care64);
-		else if (level2 && hashed) hipLaunchKernelGGL((seed_stream_fast_kernel<true, true, false>), grid, block, 0, st, a, sid, lo, hi, base, care64);
-		else if (level2) hipLaunchKernelGGL((seed_stream_fast_kernel<true, false, false>), grid, block, 0, st, a, sid, lo, hi, base, care64);
-		else if (hashed) hipLaunchKernelGGL((seed_stream_fast_kernel<false, true, false>), grid, block, 0, st, a, sid, lo, hi, base, care64);
-		else hipLaunchKernelGGL((seed_stream_fast_kernel<false, false, false>), grid, block, 0, st, a, sid, lo, hi, base, care64);
+		// the fused pipeline (short seeds: by class, no level 2); by class without the fusion (long seeds against a large query
+		// block, or short seeds with DMND_SEED_FUSED=0); the plain stream
+		if (fused) launch_stream_fast<false, true, true>(a, sid, grid, st, lo, hi, base, care64);
+		else if (by_class && level2) launch_stream_fast<true, false, true>(a, sid, grid, st, lo, hi, base, care64);
+		else if (by_class) launch_stream_fast<false, false, true>(a, sid, grid, st, lo, hi, base, care64);
+		else if (level2) launch_stream_fast<true, false, false>(a, sid, grid, st, lo, hi, base, care64);
+		else launch_stream_fast<false, false, false>(a, sid, grid, st, lo, hi, base, care64);
 		return hipGetLastError();
 	}
 	hipLaunchKernelGGL(seed_stream_kernel, dim3(blocks_for(a.t_end - a.t_begin, 256)), dim3(256), 0, st, a, sid);
@@ -1863,14 +1800,10 @@ hipError_t launch_seed_collect(const SeedArgs& a, int64_t n_matched, hipStream_t
 	if (n_matched >= folded_from) {
 		const uint64_t words = (a.slot_mask + 1) / 32;
 		uint32_t* fold = a.need_bits + words;              // (seed_api.hip sizes the map's buffer for it)
-		const uint32_t fold_words = 1u << std::min(15, std::max(8, tuning().seed_need_fold_log2 ? tuning().seed_need_fold_log2 : 13));      // <= SEED_NEED_FOLD_WORDS
+		const uint32_t fold_words = SEED_NEED_FOLD_WORDS;
 		hipLaunchKernelGGL(seed_need_fold_kernel, dim3(fold_words / 256), dim3(256), 0, st, (const uint32_t*)a.need_bits, words, fold, fold_words);
 		const unsigned tiles = blocks_for(n_matched, 256 * 16);
 		const unsigned per_cu = std::max(1u, std::min(4u, (150u * 1024u) / (fold_words * 4u + 64u)));
-		if (fold_words * sizeof(uint32_t) > 48 * 1024) {
-			const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(seed_collect_folded_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(fold_words * sizeof(uint32_t)));
-			if (e != hipSuccess) return e;
-		}
 		hipLaunchKernelGGL(seed_collect_folded_kernel, dim3(std::min(tiles, 256u * per_cu)), dim3(256), fold_words * sizeof(uint32_t), st, a, n_matched, (const uint32_t*)fold, fold_words);
 		return hipGetLastError();
 	}

@@ -1,8 +1,8 @@
 // tuning.h -- the library's tuning values in ONE place (round 6; the round-5 review counted 51 getenv calls scattered over csrc/).
 // None of them is part of the ABI; every one has a measured default and is read ONCE per process from the environment variable
-// named beside it (the sweeps that chose the defaults: DESIGN.md 6.4, 6.6, 4.17; tools/stream_sweep.py, tools/seed_modes.py).
+// named beside it (the sweeps that chose the defaults: DESIGN.md 6.4, 6.6, 4.17; tools/seed_modes.py).
 // Not here, on purpose: diagnostics (DMND_TRACE*, DMND_SEED_PHASES, DMND_CLI_TIMELINE), the tests' hooks that force a rare path
-// per call (buffer caps, DMND_SEED_TILED / _FUSED / _CLASSES*, DMND_TRACE_ARENA_MB, DMND_SWIPE32 ...) and the A/B switches that keep
+// per call (buffer caps, DMND_SEED_TILED / _FUSED / _CLASSES_LONG, DMND_TRACE_ARENA_MB, DMND_SWIPE32 ...) and the A/B switches that keep
 // the previous form of a stage alive as the second implementation parity tests compare with (DMND_EXTEND_DEVICE, _PLAN_GPU,
 // _XDROP_GPU, _KEEP_TRACE): DESIGN.md 9 lists them all.
 #pragma once
@@ -27,14 +27,8 @@ struct Tuning {
 	int extend_resweep_below_pct = 40; // DMND_EXTEND_RESWEEP_BELOW_PCT: device half: an iteration of which at most this share of the targets can survive the culling is swept for scores only, its survivors again with traceback (0 = always keep trace rows)
 	// ---- streams
 	bool no_stream_priority = false;   // DMND_NO_STREAM_PRIORITY: every stream at the default priority
-	// ---- seed stage geometry (seed_api.hip seed_sizes; 0 / -1 = the size-dependent default chosen there)
+	// ---- seed stage geometry (seed_api.hip seed_sizes; 0 = the size-dependent default chosen there)
 	int seed_slots_x8 = 0;             // DMND_SEED_SLOTS_X8: table slots per query position x 8 (8 .. 64; default 32 fused / 16)
-	int seed_bitmap1_log2 = 0;         // DMND_SEED_BITMAP1_LOG2: level-1 filter bits (15 .. 27; default 24, 25 for short seeds by class)
-	int seed_bm1_kb = 0;               // DMND_SEED_BM1_KB: level-1 filter size in KB, overrides the above
-	int seed_bm1_k = 0;                // DMND_SEED_BM1_K: 3 = three bits per key in one word, else two
-	int seed_stream_nt = -1;           // DMND_SEED_STREAM_NT: non-temporal loads of the streamed letters
-	int seed_probe_policy = -1;        // DMND_SEED_PROBE_POLICY: cache-policy bits of the filter probes (stream_sweep.py)
-	int seed_need_fold_log2 = 0;       // DMND_SEED_NEED_FOLD_LOG2: words of the LDS-folded need map of the deferred pass (11 .. 15; default 13)
 };
 
 inline const Tuning& tuning()
@@ -53,12 +47,6 @@ inline const Tuning& tuning()
 		x.extend_resweep_below_pct = std::max(0, std::min(100, num("DMND_EXTEND_RESWEEP_BELOW_PCT", x.extend_resweep_below_pct)));
 		x.no_stream_priority = std::getenv("DMND_NO_STREAM_PRIORITY") != nullptr;
 		if (std::getenv("DMND_SEED_SLOTS_X8")) x.seed_slots_x8 = std::min(64, std::max(8, num("DMND_SEED_SLOTS_X8", 0)));
-		if (std::getenv("DMND_SEED_BITMAP1_LOG2")) x.seed_bitmap1_log2 = std::min(27, std::max(15, num("DMND_SEED_BITMAP1_LOG2", 0)));
-		if (std::getenv("DMND_SEED_BM1_KB")) x.seed_bm1_kb = std::min(65536, std::max(4, num("DMND_SEED_BM1_KB", 0)));
-		x.seed_bm1_k = num("DMND_SEED_BM1_K", 0);
-		x.seed_stream_nt = num("DMND_SEED_STREAM_NT", -1);
-		x.seed_probe_policy = num("DMND_SEED_PROBE_POLICY", -1);
-		x.seed_need_fold_log2 = num("DMND_SEED_NEED_FOLD_LOG2", 0);
 		return x;
 	}();
 	return t;

@@ -1,5 +1,5 @@
 #!/bin/bash
-# round 4: three PMC groups of the C3 fused stream kernel (DMND_SEED_CLASSES from the environment), summary into gpurun_out/c3/
+# round 4: three PMC groups of the C3 fused stream kernel, summarised per kernel into $OUT/pmc_C3.json
 ROOT="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 OUT="$ROOT/gpurun_out/c3"; mkdir -p "$OUT"
 TMP=$(mktemp -d /tmp/pmc.XXXXXX)
@@ -10,9 +10,9 @@ for grp in "TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum TCC_EA0_RDREQ_sum" "SQ_INSTS_VA
   i=$((i+1))
   timeout 600 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d "$TMP/p$i" -o pmc -- $B > "$TMP/p$i.log" 2>&1 || tail -5 "$TMP/p$i.log"
 done
-python "$ROOT/tools/pmc_summary.py" "$OUT/pmc_C3_classes${DMND_SEED_CLASSES:-1}.json" "$TMP"/p*/
+python "$ROOT/tools/pmc_summary.py" "$OUT/pmc_C3.json" "$TMP"/p*/
 rm -rf "$TMP"
-python - "$OUT/pmc_C3_classes${DMND_SEED_CLASSES:-1}.json" <<'PY'
+python - "$OUT/pmc_C3.json" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))
 for k, v in d.items():

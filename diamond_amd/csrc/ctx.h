@@ -110,7 +110,7 @@ struct dmnd_ctx {
 	dmnd::DevBuf ext_ev;                      // the host's (e-value, bit score) pairs on their way into the device copy of the records
 	const dmnd_match* ext_records_dev = nullptr; int64_t ext_records_n = -1;      // the records of the last dmnd_extend where they lie in HBM (complete: host e-values in); n = -1: part of them only exists on the host
 	dmnd::PinBuf ext_host;                    // ... its counters, records and query states on the host
-	double ext_dev_stats[10] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };      // of the last dmnd_extend: queries extended on the device, of them redone by the host (ambiguous e-value order / 16-bit saturation), items, records, band diagonals x steps, wavefront diagonals x steps
+	double ext_dev_stats[10] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };      // of the last dmnd_extend: queries extended on the device, of them redone by the host (ambiguous e-value order / 16-bit saturation / chunk cap), items, records, band diagonals x steps, wavefront diagonals x steps, round-2 cells, of them swept again, round-2 sweep ms, queries at the chunk cap
 	std::vector<int32_t> h_bias_ids;           // block sequence ids of the queries with seed hits (Hauser bias of one dmnd_extend call)
 	int64_t block_len[2] = { 0, 0 }, cbs_len = 0;
 	std::vector<int64_t> limits[2];

@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 #include <vector>
 #include "ctx.h"
 #include "host_pool.h"
@@ -18,6 +19,45 @@
 #include "match_order.h"
 
 using namespace dmnd;
+
+namespace {
+
+// DMND_EXTEND_GUARD (a test hook, read per call): the bytes of a work buffer behind the call's layout, [used, cap), are filled with
+// a pattern before its kernels run and read back once at its end; a kernel or a clear that wrote past the layout changed some of
+// them, and the call fails with the extent. Off (the default): nothing is done.
+struct Guard {
+	enum { PATTERN = 0xA5 };
+	const DevBuf& buf;
+	size_t used;
+	hipStream_t st;
+	bool on;
+	Guard(const DevBuf& b, size_t used_bytes, hipStream_t s) : buf(b), used(used_bytes), st(s), on(std::getenv("DMND_EXTEND_GUARD") != nullptr && b.cap > used_bytes) {}
+	int arm() const
+	{
+		if (on) HIP_TRY(hipMemsetAsync(buf.as<char>() + used, PATTERN, buf.cap - used, st));
+		return DMND_OK;
+	}
+	int check(const char* who) const
+	{
+		if (!on) return DMND_OK;
+		std::vector<uint8_t> h(buf.cap - used);
+		HIP_TRY(copy_now(st, h.data(), buf.as<char>() + used, h.size(), hipMemcpyDeviceToHost));
+		size_t n_changed = 0, last = 0;
+		for (size_t i = 0; i < h.size(); ++i) if (h[i] != PATTERN) { ++n_changed; last = i; }
+		if (n_changed == 0) return DMND_OK;
+		return fail(DMND_E_CAP, std::string(who) + ": " + std::to_string(n_changed) + " bytes past the end of the work arrays (" + std::to_string(used) +
+			" bytes) were overwritten, up to " + std::to_string(last + 1) + " bytes past it");
+	}
+};
+
+// DMND_EXTEND_MAX_CHUNKS (a test hook, read per call): ranking chunks a query may take on the device, 1 .. EXT_MAX_ITERATIONS
+int ext_max_chunks()
+{
+	const char* e = std::getenv("DMND_EXTEND_MAX_CHUNKS");
+	return e ? std::max(1, std::min(atoi(e), (int)EXT_MAX_ITERATIONS)) : (int)EXT_MAX_ITERATIONS;
+}
+
+}  // namespace
 
 // Runs the planner over the call's hits (in c->xd_hits, with their x-drop extensions in c->xd_out and -- gf_on -- their gapped
 // filter flags in c->gf_flags), waits for it and copies its lists to the host. planned = false: the hits are not in
@@ -35,6 +75,8 @@ int dmnd::plan_on_device(dmnd_ctx* c, const DeviceCfg& h, int64_t n_hits, bool g
 		o_chain = align(o_counters + sizeof(PlanCounters)), bytes = o_chain + (n + 2) * sizeof(uint32_t);      // (both chaining lists, and a small group listed again)
 	TraceLaps tr("dmnd_extend (planner)");
 	if (int rc = c->plan_dev.ensure(bytes)) return rc;
+	Guard guard(c->plan_dev, bytes, c->stream);
+	if (int rc = guard.arm()) return rc;
 	tr.lap("work arrays");
 	char* d = c->plan_dev.as<char>();
 	PlanArgs a;
@@ -61,6 +103,7 @@ int dmnd::plan_on_device(dmnd_ctx* c, const DeviceCfg& h, int64_t n_hits, bool g
 	HIP_TRY(copy_now(c->stream, c->plan_host.p, a.counters, sizeof(PlanCounters), hipMemcpyDeviceToHost));
 	tr.lap("counters back");
 	const PlanCounters cn = *c->plan_host.as<PlanCounters>();
+	if (int rc = guard.check("dmnd_extend (planner)")) return rc;
 	if (cn.unsorted || cn.n_groups == 0) return DMND_OK;
 	plan.n_groups = cn.n_groups; plan.n_queries = cn.n_queries; plan.n_bands = cn.n_bands; plan.n_on_host = cn.n_on_host;
 	plan.dev = a;
@@ -101,18 +144,11 @@ int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan,
 	const int64_t chunk = h.ranking_chunk;
 	if (chunk > EXT_MAX_CHUNK || plan.n_bands == 0) return DMND_OK;
 	if (((size_t)h.max_target_seqs + 2 * (size_t)chunk) * 24 > ((size_t)60 << 10)) return DMND_OK;      // (the LDS lists of ext_append_kernel)
-	const size_t nG = plan.n_groups, nQ = plan.n_queries, nB = plan.n_bands, nR = std::min(nG, nQ * (size_t)std::max(h.max_target_seqs, 1));
-	const size_t nI = nB + nR;                            // items: every band once + a copy of every survivor (round 2 without kept traces)
-	size_t at = 0;
-	auto take = [&](size_t bytes) { const size_t o = at; at = (at + bytes + 63) & ~(size_t)63; return o; };
-	const size_t o_qstate = take(nQ), o_qactive = take(nQ), o_qi0 = take(nQ * 4), o_qi1 = take(nQ * 4), o_qtail = take(nQ * 4), o_qprev = take(nQ * 4), o_qswept = take(nQ * 4),
-		o_okeys = take(nG * 8), o_okeys2 = take(nG * 8), o_oidx = take(nG * 4), o_gorder = take(nG * 4), o_aligned = take(nG), o_gfirst = take(nG * 4), o_gcnt = take(nG * 4),
-		o_cnt = take((nG + 1) * 4), o_item_off = take((nG + 1) * 4), o_kept = take((nG + 1) * 4), o_kept_pos = take((nG + 1) * 4), o_cand_item = take(nG * 4), o_cand_ev = take(nG * 8),
-		o_items = take(nI * sizeof(dmnd_dp_target)), o_off_item = take(nI * 8), o_p = take(nI * 4), o_ends = take(nI * sizeof(SwipeEnd)), o_hsps = take(nI * sizeof(dmnd_hsp)),
-		o_keys = take(nI * 4), o_keys_sorted = take(nI * 4), o_idx = take(nI * 4), o_order = take(nI * 4), o_rows = take(nI * 8), o_rows_slot = take((nI + 1) * 8), o_off_slot = take((nI + 1) * 8),
-		o_pairs = take((nI + 8 * EXT_CLASSES) * 4), o_r2_order = take(nR * 4), o_r2_p = take(nR * 4), o_r2_off = take(nR * 8), o_r2_tr = take((nR + 1) * 8), o_r2_group = take(nR * 4),
-		o_records = take(nR * sizeof(dmnd_match)), o_ctr = take(sizeof(ExtCounters));
-	if (int rc = c->ext_dev.ensure(at)) return rc;
+	const ExtLayout L = ext_layout(plan.n_groups, plan.n_queries, plan.n_bands, h.max_target_seqs);
+	const size_t nQ = L.nQ, nR = L.nR;
+	if (int rc = c->ext_dev.ensure(L.bytes)) return rc;
+	Guard guard(c->ext_dev, L.bytes, c->stream);
+	if (int rc = guard.arm()) return rc;
 	tr.lap("work arrays");
 	char* d = c->ext_dev.as<char>();
 	ExtArgs a;
@@ -122,26 +158,27 @@ int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan,
 	a.use_cbs = h.use_cbs ? 1 : 0; a.row_min_items = (uint32_t)std::min<int64_t>(sweep_rows_min_items(), 0xffffffffll); a.chunk_size = (uint32_t)chunk; a.k = h.max_target_seqs; a.max_swipe_dp = h.max_swipe_dp;
 	const Evaluer& E = c->evaluer;
 	a.ev = ExtEvalue{ E.lambda, E.K, E.ln_k, E.db_letters, E.a, E.b, E.alpha, E.beta, E.sigma, E.tau, E.v_thr, E.c_thr, h.max_evalue };
-	a.qstate = reinterpret_cast<uint8_t*>(d + o_qstate); a.q_active = reinterpret_cast<uint8_t*>(d + o_qactive);
-	a.q_i0 = reinterpret_cast<uint32_t*>(d + o_qi0); a.q_i1 = reinterpret_cast<uint32_t*>(d + o_qi1);
-	a.q_tail = reinterpret_cast<int32_t*>(d + o_qtail); a.q_prev = reinterpret_cast<int32_t*>(d + o_qprev); a.q_swept = reinterpret_cast<uint32_t*>(d + o_qswept);
-	a.okeys = reinterpret_cast<uint64_t*>(d + o_okeys); a.okeys_sorted = reinterpret_cast<uint64_t*>(d + o_okeys2);
-	a.oidx = reinterpret_cast<uint32_t*>(d + o_oidx); a.gorder = reinterpret_cast<uint32_t*>(d + o_gorder);
-	a.aligned = reinterpret_cast<uint8_t*>(d + o_aligned); a.g_first = reinterpret_cast<uint32_t*>(d + o_gfirst); a.g_cnt = reinterpret_cast<uint32_t*>(d + o_gcnt);
-	a.cnt = reinterpret_cast<uint32_t*>(d + o_cnt); a.item_off = reinterpret_cast<uint32_t*>(d + o_item_off);
-	a.kept = reinterpret_cast<uint32_t*>(d + o_kept); a.kept_pos = reinterpret_cast<uint32_t*>(d + o_kept_pos);
-	a.cand_item = reinterpret_cast<uint32_t*>(d + o_cand_item); a.cand_ev = reinterpret_cast<double*>(d + o_cand_ev);
-	a.item_base = 0; a.item_cap = (uint32_t)nI;
-	a.items = reinterpret_cast<dmnd_dp_target*>(d + o_items); a.off_item = reinterpret_cast<int64_t*>(d + o_off_item);
-	a.p_of_item = reinterpret_cast<int32_t*>(d + o_p); a.ends = reinterpret_cast<SwipeEnd*>(d + o_ends); a.hsps = reinterpret_cast<dmnd_hsp*>(d + o_hsps);
-	a.keys = reinterpret_cast<uint32_t*>(d + o_keys); a.keys_sorted = reinterpret_cast<uint32_t*>(d + o_keys_sorted);
-	a.idx = reinterpret_cast<uint32_t*>(d + o_idx); a.order = reinterpret_cast<uint32_t*>(d + o_order);
-	a.rows = reinterpret_cast<int64_t*>(d + o_rows); a.rows_slot = reinterpret_cast<int64_t*>(d + o_rows_slot); a.off_slot = reinterpret_cast<int64_t*>(d + o_off_slot);
-	a.pairs = reinterpret_cast<int32_t*>(d + o_pairs);
-	a.r2_order = reinterpret_cast<int32_t*>(d + o_r2_order); a.r2_p = reinterpret_cast<int32_t*>(d + o_r2_p);
-	a.r2_off = reinterpret_cast<int64_t*>(d + o_r2_off); a.r2_tr = reinterpret_cast<int64_t*>(d + o_r2_tr); a.r2_group = reinterpret_cast<uint32_t*>(d + o_r2_group);
-	a.records = reinterpret_cast<dmnd_match*>(d + o_records);
-	a.ctr = reinterpret_cast<ExtCounters*>(d + o_ctr);
+	a.qstate = reinterpret_cast<uint8_t*>(d + L.o_qstate); a.q_active = reinterpret_cast<uint8_t*>(d + L.o_qactive);
+	a.q_i0 = reinterpret_cast<uint32_t*>(d + L.o_qi0); a.q_i1 = reinterpret_cast<uint32_t*>(d + L.o_qi1);
+	a.q_tail = reinterpret_cast<int32_t*>(d + L.o_qtail); a.q_prev = reinterpret_cast<int32_t*>(d + L.o_qprev); a.q_swept = reinterpret_cast<uint32_t*>(d + L.o_qswept);
+	a.okeys = reinterpret_cast<uint64_t*>(d + L.o_okeys); a.okeys_sorted = reinterpret_cast<uint64_t*>(d + L.o_okeys2);
+	a.oidx = reinterpret_cast<uint32_t*>(d + L.o_oidx); a.gorder = reinterpret_cast<uint32_t*>(d + L.o_gorder);
+	a.aligned = reinterpret_cast<uint8_t*>(d + L.o_aligned); a.g_first = reinterpret_cast<uint32_t*>(d + L.o_gfirst); a.g_cnt = reinterpret_cast<uint32_t*>(d + L.o_gcnt);
+	a.cnt = reinterpret_cast<uint32_t*>(d + L.o_cnt); a.item_off = reinterpret_cast<uint32_t*>(d + L.o_item_off);
+	a.kept = reinterpret_cast<uint32_t*>(d + L.o_kept); a.kept_pos = reinterpret_cast<uint32_t*>(d + L.o_kept_pos);
+	a.cand_item = reinterpret_cast<uint32_t*>(d + L.o_cand_item); a.cand_ev = reinterpret_cast<double*>(d + L.o_cand_ev);
+	a.item_base = 0; a.item_cap = (uint32_t)L.nI;
+	a.items = reinterpret_cast<dmnd_dp_target*>(d + L.o_items); a.off_item = reinterpret_cast<int64_t*>(d + L.o_off_item);
+	a.p_of_item = reinterpret_cast<int32_t*>(d + L.o_p); a.ends = reinterpret_cast<SwipeEnd*>(d + L.o_ends); a.hsps = reinterpret_cast<dmnd_hsp*>(d + L.o_hsps);
+	a.keys = reinterpret_cast<uint32_t*>(d + L.o_keys); a.keys_sorted = reinterpret_cast<uint32_t*>(d + L.o_keys_sorted);
+	a.idx = reinterpret_cast<uint32_t*>(d + L.o_idx); a.order = reinterpret_cast<uint32_t*>(d + L.o_order);
+	a.rows = reinterpret_cast<int64_t*>(d + L.o_rows); a.rows_slot = reinterpret_cast<int64_t*>(d + L.o_rows_slot); a.off_slot = reinterpret_cast<int64_t*>(d + L.o_off_slot);
+	a.pairs = reinterpret_cast<int32_t*>(d + L.o_pairs);
+	a.r2_cap = (uint32_t)L.nR; a.r2_tr_clear = (uint32_t)L.r2_tr_clear;
+	a.r2_order = reinterpret_cast<int32_t*>(d + L.o_r2_order); a.r2_p = reinterpret_cast<int32_t*>(d + L.o_r2_p);
+	a.r2_off = reinterpret_cast<int64_t*>(d + L.o_r2_off); a.r2_tr = reinterpret_cast<int64_t*>(d + L.o_r2_tr); a.r2_group = reinterpret_cast<uint32_t*>(d + L.o_r2_group);
+	a.records = reinterpret_cast<dmnd_match*>(d + L.o_records);
+	a.ctr = reinterpret_cast<ExtCounters*>(d + L.o_ctr);
 	a.scan_tmp = &c->plan_tmp; a.scan_tmp_bytes = &c->plan_tmp_bytes;
 	hipStream_t st = c->stream;
 	if (int rc = c->ext_host.ensure(sizeof(ExtCounters))) return rc;
@@ -167,14 +204,15 @@ int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan,
 	ExtCounters ctr;
 	double ms_sweeps = 0, ms_sweeps2 = 0, ms_walk = 0;
 	uint64_t items_total = 0;
+	const int max_chunks = ext_max_chunks();
 	for (int iter = 0;; ++iter) {
-		if (iter >= EXT_MAX_ITERATIONS) return fail(DMND_E_CAP, "dmnd_extend: a query's ranking did not end within the supported number of chunks");
+		const bool last = iter + 1 >= max_chunks;      // (a query still ranking after this chunk goes back to the host)
 		// 1. the chunk's items, launch order, trace offsets, pairs
 		HIP_TRY(launch_ext_prepare(a, st));
 		HIP_TRY(copy_now(st, c->ext_host.p, a.ctr, sizeof(ExtCounters), hipMemcpyDeviceToHost));
 		ctr = *c->ext_host.as<ExtCounters>();
 		if (iter == 0) tr.lap("items, launch order, trace offsets");
-		if (iter == 0 && ctr.n_items == 0) return DMND_OK;
+		if (iter == 0 && ctr.n_items == 0) return guard.check("dmnd_extend (device half)");
 		// a call whose first ranking iteration took the row classes keeps them for its later, smaller iterations and for the copies
 		// of round 2 (they are short next to the first one, and a row launch of 10^5 items still beats the wavefront classes)
 		if (iter == 0 && ctr.n_items >= a.row_min_items && a.row_min_items > 4096) a.row_min_items = 4096;
@@ -197,7 +235,7 @@ int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan,
 			HIP_TRY(hipEventRecord(c->ev1, st));
 		}
 		// 3. best HSP per target, append_hits, next window; and -- in case that was the last chunk of every query -- final culling + round-2 list
-		HIP_TRY(launch_ext_append(a, ctr.n_items, kept, rel, st));
+		HIP_TRY(launch_ext_append(a, ctr.n_items, kept, rel, last, st));
 		const uint32_t n_items_iter = ctr.n_items;
 		HIP_TRY(copy_now(st, c->ext_host.p, a.ctr, sizeof(ExtCounters), hipMemcpyDeviceToHost));
 		ctr = *c->ext_host.as<ExtCounters>();
@@ -206,6 +244,7 @@ int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan,
 		a.item_base += n_items_iter;
 		if (tr.on && (iter > 0 || ctr.n_active > 0)) std::fprintf(stderr, "dmnd_extend (device half): chunk %d: %u DpTargets%s, %.1f MB of trace rows kept so far, %u queries go on\n", iter, n_items_iter, kept ? "" : " (scores only)", (double)trace_used / 1048576.0, ctr.n_active);
 		if (ctr.n_active == 0) break;
+		if (last) return fail(DMND_E_CAP, "dmnd_extend: a query went on ranking past the last allowed chunk");
 	}
 	tr.lap("sweeps, culling");
 	// 4. round 2: the survivors whose trace rows were not kept are swept again with traceback (copies of their items, one more
@@ -306,6 +345,10 @@ int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan,
 	c->ext_dev_stats[0] = (double)n_eligible; c->ext_dev_stats[1] = (double)(ctr.n_ambiguous + ctr.n_saturated); c->ext_dev_stats[2] = (double)items_total; c->ext_dev_stats[3] = (double)ctr.n_kept;
 	c->ext_dev_stats[4] = (double)ctr.diag_steps; c->ext_dev_stats[5] = (double)ctr.lane_steps;
 	c->ext_dev_stats[6] = (double)ctr.cells2; c->ext_dev_stats[7] = (double)ctr.cells_again; c->ext_dev_stats[8] = ms_sweeps2;
+	c->ext_dev_stats[1] += (double)ctr.n_capped; c->ext_dev_stats[9] = (double)ctr.n_capped;
+	if (tr.on) std::fprintf(stderr, "dmnd_extend (device half): %zu queries, %u handed back to the host (%u ambiguous, %u saturated, %u at the chunk cap of %d), %zu records; %u groups, %u bands, %zu bytes of work arrays\n",
+		n_eligible, ctr.n_ambiguous + ctr.n_saturated + ctr.n_capped, ctr.n_ambiguous, ctr.n_saturated, ctr.n_capped, max_chunks, n, plan.n_groups, plan.n_bands, L.bytes);
+	if (int rc = guard.check("dmnd_extend (device half)")) return rc;
 	done = true;
 	return DMND_OK;
 }

@@ -10,37 +10,24 @@
 //   match records in (query, e-value, score, target) order                   (/root/reference/src/align/extend.h:51-56, extend.cpp:341)
 // The e-value is double arithmetic with exp / erfc (evalue.h); the device's versions of those differ from the host library's in the
 // last bits, so the device value only DECIDES (cutoff, order, first k) and a decision that two values closer than 1e-9 relative
-// could flip marks the query `ambiguous`: the host redoes that query. The records leave with the device value; the host overwrites
+// could flip marks the query `ambiguous`: the host redoes that query (two values that are 0.0 on both sides are ordered by score and
+// target exactly; next to the underflow two tiny values are always flagged). The records leave with the device value; the host overwrites
 // it with its own (and the bit score) and checks the order. Queries with a group the planner left to the host, with an item the
 // traceback path cannot take or with more than EXT_MAX_GROUPS groups stay on the host path (extend_host.hip extend_range).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/diamond_hip.h"
+#include "extend_core.h"
 #include "plan_kernels.h"
 #include "swipe_kernels.h"
 
 namespace dmnd {
 
-enum { EXT_CLASSES = 16, EXT_MAX_CHUNK = 1024, EXT_MAX_GROUPS = 1 << 16, EXT_MAX_ITERATIONS = 64 };
+static_assert(sizeof(SwipeEnd) == EXT_SWIPE_END_BYTES, "extend_core.h lays the per-item ends out with this size");
 
 struct ExtEvalue {             // Evaluer (evalue.h) as plain data + the report cutoff
 	double lambda, K, ln_k, db_letters, a, b, alpha, beta, sigma, tau, v_thr, c_thr, max_evalue;
-};
-
-struct ExtCounters {
-	uint32_t n_items;                        // of the current iteration
-	uint32_t n_active;                       // queries that go on to another ranking chunk
-	uint32_t n_saturated, n_kept, n_ambiguous, n_resweep;      // n_resweep: survivors whose round-1 sweep kept no trace
-	int32_t tb_status;                       // traceback_kernel's status word (0 = every walk ended at a cell with score 0)
-	uint32_t pad;                            // (the arrays and the 64-bit counters below lie back to back: reset_iteration clears them in one go)
-	uint32_t class_count[EXT_CLASSES];       // items of the current iteration per launch class c (P = class_of_index(c), swipe_core.h)
-	uint32_t class_max_steps[EXT_CLASSES];
-	unsigned long long total_rows;           // trace bytes of the current iteration's items
-	unsigned long long cells1, cells2;       // DP cells of all round-1 items / of the items walked in round 2 (the reference's round-2 targets)
-	unsigned long long cells_again;          // ... of those of them that round 2 swept again (their round-1 sweep kept no trace rows)
-	unsigned long long window_targets, window_bound;      // of the current iteration: targets in the active queries' windows, and sum over the queries of min(-k, targets): what can survive the culling
-	unsigned long long diag_steps, lane_steps;   // over the round-1 items: band diagonals x anti-diagonal steps, and the 128 P diagonals the item's wavefront holds x steps (lane use of the sweeps)
 };
 
 struct ExtArgs {
@@ -83,6 +70,8 @@ struct ExtArgs {
 	int64_t* rows; int64_t* rows_slot; int64_t* off_slot;
 	int32_t* pairs;
 	// round 2 and output
+	uint32_t r2_cap;               // room in the round-2 arrays and the records (ExtLayout::nR)
+	uint32_t r2_tr_clear;          // entries of r2_tr that launch_ext_begin zeroes (ExtLayout::r2_tr_clear)
 	int32_t* r2_order; int32_t* r2_p; int64_t* r2_off; int64_t* r2_tr;       // slot -> item, band class, trace offset, (zero) transcript offsets
 	uint32_t* r2_group;            // slot -> group
 	dmnd_match* records;
@@ -90,7 +79,7 @@ struct ExtArgs {
 	void** scan_tmp; size_t* scan_tmp_bytes;
 };
 
-enum { EXT_Q_HOST = 0, EXT_Q_DEVICE = 1, EXT_Q_AMBIGUOUS = 2 };
+enum { EXT_Q_HOST = 0, EXT_Q_DEVICE = 1, EXT_Q_AMBIGUOUS = 2, EXT_Q_CAPPED = 3 };      // CAPPED: still ranking after the last allowed chunk
 
 // once per call: which queries run here, their ranking order, the state of their ranking loops
 hipError_t launch_ext_begin(const ExtArgs& a, hipStream_t st);
@@ -100,8 +89,8 @@ hipError_t launch_ext_prepare(const ExtArgs& a, hipStream_t st);
 // ... behind its sweeps: best HSP per target, append_hits, the next chunk or the end of the query's ranking. kept: the sweeps ran in
 // traceback mode and their trace rows stay (rel = the iteration's arena relative to the first one); else round 2 sweeps the
 // survivors of this iteration again. Then -- speculatively: it only counts if ctr->n_active comes back 0 -- the final culling and
-// the round-2 list
-hipError_t launch_ext_append(const ExtArgs& a, uint32_t n_items, bool kept, int64_t rel, hipStream_t st);
+// the round-2 list. last: no further chunk is allowed -- a query that would go on is handed back to the host (EXT_Q_CAPPED)
+hipError_t launch_ext_append(const ExtArgs& a, uint32_t n_items, bool kept, int64_t rel, bool last, hipStream_t st);
 // round 2, first half, for the survivors without kept trace rows: copies of their items as one more iteration (launch order, trace
 // offsets, pairs); then, behind its traceback-mode sweeps, launch_ext_rewalk points the round-2 list at the copies
 hipError_t launch_ext_resweep(const ExtArgs& a, uint32_t n_kept, hipStream_t st);

@@ -52,6 +52,15 @@ __device__ inline double ext_evalue(const ExtEvalue& p, int raw_score, int qlen,
 // two device e-values whose order the host's own values could reverse (or a value that close to the cutoff)
 __device__ inline bool ext_near(double x, double y) { return fabs(x - y) <= 1e-9 * fmax(fabs(x), fabs(y)); }
 
+// Where K exp(-lambda y), the factor of the e-value that underflows, lies for a raw score y: 0 = a normal double on both sides; 2 =
+// exp underflows to 0.0 on both sides (exp(-750) is 1/100 of the smallest subnormal), so the e-value is exactly 0.0 on the host and
+// here; 1 = in between, where one side may round to 0.0 or to a subnormal (a few significant bits) that the other does not
+__device__ inline int ext_underflow(const ExtEvalue& p, int raw_score)
+{
+	const double t = -p.lambda * (double)raw_score;
+	return t < -750.0 ? 2 : (p.ln_k + t < -700.0 ? 1 : 0);
+}
+
 __device__ inline int64_t ext_cells(const dmnd_dp_target& d)       // DpTarget::cells of a banded target (dp/dp.h:47-52, 121-124)
 {
 	const int pos = imax(d.d_end - 1, 0) - (d.d_end - 1);
@@ -239,8 +248,17 @@ __device__ inline bool sel_less(const SelSlot& x, const SelSlot& y)      // Targ
 {
 	return x.ev < y.ev || (x.ev == y.ev && (x.score > y.score || (x.score == y.score && x.target < y.target)));
 }
-// the host's own e-values could order the two the other way round (equal inputs give equal values on both sides)
-__device__ inline bool sel_ambiguous(const SelSlot& x, const SelSlot& y) { return ext_near(x.ev, y.ev) && !(x.score == y.score && x.tlen == y.tlen); }
+// the host's own e-values could order the two the other way round (equal inputs give equal values on both sides). Two e-values
+// that are 0.0 on both sides are ordered by score and target exactly, as the host orders them; next to the underflow the
+// relative tolerance means nothing, and two tiny values are always flagged
+__device__ inline bool sel_ambiguous(const ExtEvalue& p, const SelSlot& x, const SelSlot& y)
+{
+	if (x.score == y.score && x.tlen == y.tlen) return false;
+	const int ux = ext_underflow(p, x.score), uy = ext_underflow(p, y.score);
+	if (ux == 2 && uy == 2) return false;
+	if ((ux == 1 || uy == 1) && fmax(x.ev, y.ev) < 1e-250) return true;
+	return ext_near(x.ev, y.ev);
+}
 
 // the query's aligned targets into an LDS list (any order); returns their number (all lanes), cap + 1 if they do not fit
 __device__ inline uint32_t gather_flagged(const ExtArgs& a, const uint8_t* flag8, const uint32_t* flag32, uint32_t g0, uint32_t ng, SelSlot* list, uint32_t cap, uint32_t* counter, uint32_t lane)
@@ -262,8 +280,9 @@ __device__ inline uint32_t gather_flagged(const ExtArgs& a, const uint8_t* flag8
 
 // One ranking-chunk iteration of a query behind its sweeps (extend.cpp:289-336 with default options, one wavefront per query):
 // the chunk's targets with a reported HSP (v), append_hits (culling.cpp:115-145) into the aligned targets, the next window, the
-// tail rule (ranking_terminate, extend.cpp:111-119).
-__global__ __launch_bounds__(64) void ext_append_kernel(ExtArgs a)
+// tail rule (ranking_terminate, extend.cpp:111-119). last: no further chunk is allowed -- a query that would go on is handed back
+// to the host like an ambiguous one (the reference goes on for as long as every chunk brings new hits)
+__global__ __launch_bounds__(64) void ext_append_kernel(ExtArgs a, int last)
 {
 	extern __shared__ SelSlot lds[];
 	__shared__ uint32_t n_v_sh, n_al_sh, flags_sh;
@@ -317,7 +336,7 @@ __global__ __launch_bounds__(64) void ext_append_kernel(ExtArgs a)
 				uint32_t rank = 0;
 				for (uint32_t y = 0; y < na; ++y) {
 					if (y == x) continue;
-					if (sel_ambiguous(al[y], me)) amb = true;
+					if (sel_ambiguous(a.ev, al[y], me)) amb = true;
 					rank += sel_less(al[y], me) ? 1u : 0u;
 				}
 				if (rank >= (uint32_t)a.k) a.aligned[me.g] = 0;
@@ -328,7 +347,7 @@ __global__ __launch_bounds__(64) void ext_append_kernel(ExtArgs a)
 			const SelSlot ks = kth_slot;
 			bool reach = false;
 			for (uint32_t x = lane; x < n_v; x += 64) {
-				if (sel_ambiguous(vs[x], ks)) amb = true;
+				if (sel_ambiguous(a.ev, vs[x], ks)) amb = true;
 				reach |= vs[x].ev <= kth;
 			}
 			if (__ballot(reach) != 0) new_hits = true;
@@ -346,15 +365,20 @@ __global__ __launch_bounds__(64) void ext_append_kernel(ExtArgs a)
 		}
 		return;
 	}
+	// the next window and whether the ranking goes on (extend.cpp:325-336; uniform over the wavefront)
+	const uint32_t n0 = i1, n1 = i1 + (a.chunk_size < ng - i1 ? a.chunk_size : ng - i1);
+	const int prev = a.q_tail[q];
+	const int next_tail = (int)a.groups[a.gorder[g0 + n1 - 1]].score;
+	const bool terminate = !new_hits && (prev == 0 || (double)next_tail / (double)prev <= 0.95 || ext_bitscore(a.ev, next_tail) < 25.0);
+	const bool go_on = n0 < ng && !terminate;
+	if (go_on && last) {
+		for (uint32_t gi = lane; gi < ng; gi += 64) a.aligned[g0 + gi] = 0;
+		if (lane == 0) { a.qstate[q] = EXT_Q_CAPPED; a.q_active[q] = 0; atomicAdd(&a.ctr->n_capped, 1u); }
+		return;
+	}
 	if (lane == 0) {
-		// the next window and whether the ranking goes on (extend.cpp:325-336)
-		const uint32_t n0 = i1, n1 = i1 + (a.chunk_size < ng - i1 ? a.chunk_size : ng - i1);
-		const int prev = a.q_tail[q];
-		const int next_tail = (int)a.groups[a.gorder[g0 + n1 - 1]].score;
 		a.q_prev[q] = prev;
 		if (new_hits) a.q_tail[q] = next_tail;
-		const bool terminate = !new_hits && (prev == 0 || (double)next_tail / (double)prev <= 0.95 || ext_bitscore(a.ev, next_tail) < 25.0);
-		const bool go_on = n0 < ng && !terminate;
 		a.q_i0[q] = n0; a.q_i1[q] = n1;
 		a.q_active[q] = go_on ? 1 : 0;
 		if (go_on) atomicAdd(&a.ctr->n_active, 1u);
@@ -380,7 +404,7 @@ __global__ __launch_bounds__(64) void ext_final_kernel(ExtArgs a)
 				uint32_t rank = 0;
 				for (uint32_t y = 0; y < na; ++y) {
 					if (y == x) continue;
-					if (sel_ambiguous(lds[y], me)) amb = true;
+					if (sel_ambiguous(a.ev, lds[y], me)) amb = true;
 					rank += sel_less(lds[y], me) ? 1u : 0u;
 				}
 				keep = rank < (uint32_t)a.k;
@@ -509,7 +533,7 @@ hipError_t launch_ext_begin(const ExtArgs& a, hipStream_t st)
 {
 	hipError_t e = hipMemsetAsync(a.ctr, 0, sizeof(ExtCounters), st);
 	if (e != hipSuccess) return e;
-	e = hipMemsetAsync(a.r2_tr, 0, ((size_t)a.n_bands + 1) * sizeof(int64_t), st);
+	e = hipMemsetAsync(a.r2_tr, 0, (size_t)a.r2_tr_clear * sizeof(int64_t), st);
 	if (e != hipSuccess) return e;
 	const int key_bits = 16 + bits_for(a.n_queries);
 	size_t need = 0;
@@ -574,14 +598,14 @@ hipError_t launch_ext_prepare(const ExtArgs& a, hipStream_t st)
 	return order_items(a, st);
 }
 
-hipError_t launch_ext_append(const ExtArgs& a, uint32_t n_items, bool kept, int64_t rel, hipStream_t st)
+hipError_t launch_ext_append(const ExtArgs& a, uint32_t n_items, bool kept, int64_t rel, bool last, hipStream_t st)
 {
 	if (n_items > 0 && (!kept || rel != 0)) hipLaunchKernelGGL(ext_rebase_kernel, dim3((n_items + 255) / 256), dim3(256), 0, st, a, n_items, rel, kept ? 1 : 0);
 	// (n_active, n_resweep, cells2 and the kept flags were cleared by this iteration's ext_window_kernel: the round-2 list below is
 	// rebuilt behind every iteration)
 	hipError_t e = hipSuccess;
 	const size_t lds_append = ((size_t)a.k + 2 * (size_t)a.chunk_size) * sizeof(SelSlot), lds_final = ((size_t)a.k + (size_t)a.chunk_size) * sizeof(SelSlot);
-	hipLaunchKernelGGL(ext_append_kernel, dim3(a.n_queries), dim3(64), lds_append, st, a);
+	hipLaunchKernelGGL(ext_append_kernel, dim3(a.n_queries), dim3(64), lds_append, st, a, last ? 1 : 0);
 	// speculatively (the host only uses it when no query is left ranking): final culling, record slots, the round-2 list
 	size_t need = 0;
 	e = rocprim::exclusive_scan(nullptr, need, a.kept, a.kept_pos, 0u, (size_t)a.n_groups + 1, rocprim::plus<uint32_t>(), st);

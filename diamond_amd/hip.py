@@ -841,6 +841,16 @@ class Context:
         self.lib.dmnd_set_top_percent.argtypes = [ctypes.c_void_p, ctypes.c_double]
         self._check(self.lib.dmnd_set_top_percent(self.h, -1.0 if percent is None else float(percent)))
 
+    def set_max_target_seqs(self, k):
+        """-k / --max-target-seqs: targets reported per query (dmnd_set_max_target_seqs)."""
+        self.lib.dmnd_set_max_target_seqs.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        self._check(self.lib.dmnd_set_max_target_seqs(self.h, int(k)))
+
+    def extend_reserve(self, n_hits_hint):
+        """First-call allocations of extend() for about n_hits_hint seed hits, made ahead of it (dmnd_extend_reserve)."""
+        self.lib.dmnd_extend_reserve.argtypes = [ctypes.c_void_p, ctypes.c_int64]
+        self._check(self.lib.dmnd_extend_reserve(self.h, ctypes.c_int64(int(n_hits_hint))))
+
     def set_query_contexts(self, contexts):
         """1 = blastp, 6 = blastx (the query block holds the six frames of every read consecutively)."""
         self._check(self.lib.dmnd_set_query_contexts(self.h, int(contexts)))
@@ -930,12 +940,13 @@ class Context:
         return dict(groups=int(st[0]), groups_on_host=int(st[1]), bands=int(st[2]))
 
     def extend_device_stats(self):
-        """(queries extended on the device, of them handed back to the host, round-1 DpTargets, records) of the last extend()"""
+        """(queries extended on the device, of them handed back to the host -- queries_capped of those because they were still ranking
+        after the last chunk allowed on the device --, round-1 DpTargets, records) of the last extend()"""
         st = (ctypes.c_double * 10)()
         self.lib.dmnd_extend_device_stats.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
         self._check(self.lib.dmnd_extend_device_stats(self.h, st))
         return dict(queries=int(st[0]), queries_back_to_host=int(st[1]), items=int(st[2]), records=int(st[3]), band_diagonal_steps=st[4], wavefront_diagonal_steps=st[5],
-                    round2_cells=st[6], round2_cells_swept_again=st[7], round2_sweep_kernel_ms=st[8])
+                    round2_cells=st[6], round2_cells_swept_again=st[7], round2_sweep_kernel_ms=st[8], queries_capped=int(st[9]))
 
     def last_kernel_ms(self):
         a, b = ctypes.c_double(0), ctypes.c_double(0)

@@ -593,10 +593,11 @@ int dmnd_extend_plan_stats(const dmnd_ctx* ctx, double out[3]);
  * HSP per target and report cutoff (src/align/gapped_score.cpp:182-268), culling (src/align/culling.cpp:97-113,189-203), round 2 as a
  * walk of the kept traces (src/align/gapped_final.cpp:66-160), match records in output order (src/align/extend.h:51-56). The host
  * writes its own e-value and bit score into the records. Of the last dmnd_extend: [0] queries extended that way, [1] of them handed
- * back to the host path (two device e-values too close to order safely, or a saturated 16-bit sweep), [2] round-1 DpTargets,
+ * back to the host path (two device e-values too close to order safely, a saturated 16-bit sweep, or still ranking after the last chunk
+ * the device takes), [2] round-1 DpTargets,
  * [3] records, [4] sum over the round-1 DpTargets of band diagonals x anti-diagonal steps and [5] of the 128 P diagonals their wavefront
  * holds x steps ([4] / [5] = lane use of the sweeps), [6] DP cells of the device half's round-2 targets, [7] of those swept again in
- * round 2 (their round-1 sweep kept no trace rows), [8] device ms of those sweeps, [9] reserved; all 0 = every query took the host path (other modes: --max-hsps != 1, --top,
+ * round 2 (their round-1 sweep kept no trace rows), [8] device ms of those sweeps, [9] of [1] the queries still ranking after the last chunk; all 0 = every query took the host path (other modes: --max-hsps != 1, --top,
  * filters, matrix adjustment, --ext full, transcripts wanted, translated queries). */
 int dmnd_extend_device_stats(const dmnd_ctx* ctx, double out[10]);
 /* Round 6: the records of the last dmnd_extend where they lie in HBM, complete (the host's e-values and bit scores are written back

@@ -578,4 +578,15 @@ struct ChainWorkspaceT {
 
 typedef ChainWorkspaceT<HostChainPolicy> ChainWorkspace;
 
+// What one lane of the device planner's chaining kernel holds in LDS (plan_kernels.hip plan_chain_kernel), and how many lanes of a
+// workgroup 48 KB hold; here so that the tests read the same numbers (tests/emu/chain_emu.cpp emu_chain_lanes)
+template<int NODES, int LINKS, int CHAINS>
+struct ChainLdsT {
+	ChainWorkspaceT<FixedChainPolicy, NODES, LINKS, CHAINS> ws;
+	Seg sg[NODES];
+	FixedVec<Chain, CHAINS> chains;
+};
+template<int NODES, int LINKS, int CHAINS>
+struct ChainLanes { enum { bytes = (int)sizeof(ChainLdsT<NODES, LINKS, CHAINS>), fit = 48 * 1024 / bytes, value = fit > 64 ? 64 : fit }; };
+
 }  // namespace dmnd

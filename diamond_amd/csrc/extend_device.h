@@ -25,6 +25,8 @@ struct DevPlan {
 	const PlanQuery* queries = nullptr;       // n_queries + 1 entries
 	const PlanBand* bands = nullptr;
 	uint32_t n_groups = 0, n_queries = 0, n_bands = 0, n_on_host = 0;
+	uint32_t n_chain = 0, n_chain_big = 0, n_relisted = 0;      // PlanCounters: the two chaining lists as the kernels left them
+	bool unsorted = false;                    // the hits were not in (query, location, seed offset) order: nothing was planned
 	PlanArgs dev;                             // the same lists (and the planner's inputs) where they lie in HBM
 };
 

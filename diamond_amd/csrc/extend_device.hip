@@ -57,6 +57,14 @@ int ext_max_chunks()
 	return e ? std::max(1, std::min(atoi(e), (int)EXT_MAX_ITERATIONS)) : (int)EXT_MAX_ITERATIONS;
 }
 
+// DMND_PLAN_SMALL_HITS (a test hook, read per call): a call of at least this many hits chains its groups of up to four segments
+// with the small workspace first (the two-kernel form of plan_kernels.hip); 0 = every call
+int64_t plan_small_hits()
+{
+	const char* e = std::getenv("DMND_PLAN_SMALL_HITS");
+	return e ? std::max<int64_t>(0, std::atoll(e)) : (int64_t)1 << 18;
+}
+
 }  // namespace
 
 // Runs the planner over the call's hits (in c->xd_hits, with their x-drop extensions in c->xd_out and -- gf_on -- their gapped
@@ -88,7 +96,7 @@ int dmnd::plan_on_device(dmnd_ctx* c, const DeviceCfg& h, int64_t n_hits, bool g
 	a.gf_flags = gf_on ? c->gf_flags.as<uint8_t>() : nullptr;
 	a.xd = c->xd_out.as<XdropSeg>();
 	a.gap_open = h.gap_open; a.gap_extend = h.gap_extend; a.band_fast = h.band_mode_fast;
-	a.small_segs = n_hits >= ((int64_t)1 << 18) ? 4 : 0;
+	a.small_segs = n_hits >= plan_small_hits() ? 4 : 0;
 	a.tgt = reinterpret_cast<uint32_t*>(d + o_tgt); a.heads = reinterpret_cast<uint64_t*>(d + o_heads); a.head_scan = reinterpret_cast<uint64_t*>(d + o_scan);
 	a.groups = reinterpret_cast<PlanGroup*>(d + o_groups); a.queries = reinterpret_cast<PlanQuery*>(d + o_queries);
 	a.segs = reinterpret_cast<int32_t*>(d + o_segs); a.band_slots = reinterpret_cast<PlanBand*>(d + o_slots);
@@ -104,8 +112,10 @@ int dmnd::plan_on_device(dmnd_ctx* c, const DeviceCfg& h, int64_t n_hits, bool g
 	tr.lap("counters back");
 	const PlanCounters cn = *c->plan_host.as<PlanCounters>();
 	if (int rc = guard.check("dmnd_extend (planner)")) return rc;
+	plan.unsorted = cn.unsorted != 0;
 	if (cn.unsorted || cn.n_groups == 0) return DMND_OK;
 	plan.n_groups = cn.n_groups; plan.n_queries = cn.n_queries; plan.n_bands = cn.n_bands; plan.n_on_host = cn.n_on_host;
+	plan.n_chain = cn.n_chain; plan.n_chain_big = cn.n_chain_big; plan.n_relisted = cn.n_relisted;
 	plan.dev = a;
 	planned = true;
 	return DMND_OK;

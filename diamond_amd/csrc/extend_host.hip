@@ -1231,6 +1231,153 @@ static int extend_range(const dmnd_ctx* c, dmnd_ctx* w, const HostCfg& h, const 
 	return DMND_OK;
 }
 
+namespace {
+
+// The configuration of an extension call from the context's settings (shared by dmnd_extend and dmnd_extend_plan_device)
+int extend_cfg(dmnd_ctx* c, HostCfg& h, CbsModel& cbs_model)
+{
+	const std::vector<int64_t>& ql = c->limits[DMND_QUERY];
+	const std::vector<int64_t>& tl = c->limits[DMND_TARGET];
+	make_cfg(c, h);
+	h.max_target_seqs = c->max_target_seqs;
+	h.max_hsps = c->max_hsps;
+	h.global_ranking = c->global_ranking;
+	if (h.global_ranking > 0 && c->ext_mode != DMND_EXT_FULL) return fail(DMND_E_ARG, "dmnd_extend: globally ranked targets are extended over the full matrix (dmnd_set_extension_mode(DMND_EXT_FULL))");
+	h.top = c->top_percent;
+	h.evaluer = &c->evaluer;
+	h.max_evalue = c->params.max_evalue;
+	h.min_bit_score = c->min_bit_score; h.min_id = c->min_id; h.query_cover = c->query_cover; h.subject_cover = c->subject_cover;
+	if (h.query_cover > 0 && c->query_contexts != 1 && c->source_lens.size() != (ql.size() - 1) / (size_t)c->query_contexts)
+		return fail(DMND_E_ARG, "dmnd_extend: the query cover of translated queries needs the read lengths (dmnd_set_query_source_lengths)");
+	if (h.max_hsps != 1 && c->query_contexts != 1 && c->source_lens.size() != (ql.size() - 1) / (size_t)c->query_contexts)
+		return fail(DMND_E_ARG, "dmnd_extend: several HSPs per target of translated queries need the read lengths (dmnd_set_query_source_lengths)");
+	h.source_lens = c->source_lens.empty() ? nullptr : c->source_lens.data();
+	h.ranking_block_letters = c->ranking_block_letters;
+	h.band_mode_fast = c->band_mode_fast;
+	h.ext_full = c->ext_mode == DMND_EXT_FULL;
+	if (c->ext_mode == DMND_EXT_BANDED_FAST) h.band_mode_fast = 1; else if (c->ext_mode == DMND_EXT_BANDED_SLOW) h.band_mode_fast = 0;
+	h.contexts = c->query_contexts;
+	h.cbs_mode = c->comp_based_stats;
+	h.use_cbs = cbs_hauser(h.cbs_mode);
+	if (cbs_matrix_adjust(h.cbs_mode)) {
+		// basic/config.cpp:700, :837, :688
+		if (c->query_contexts != 1) return fail(DMND_E_ARG, "This mode of composition based stats is not supported for translated searches.");
+		if (h.global_ranking > 0) return fail(DMND_E_ARG, "Global ranking is not supported in this mode.");
+		cbs_model_init(cbs_model, c->params);
+		if (!cbs_model.valid) return fail(DMND_E_ARG, "This value for --comp-based-stats is not supported when using a custom scoring matrix.");
+		h.cbs_model = &cbs_model;
+	}
+	const uint32_t C = (uint32_t)h.contexts;
+	if ((ql.size() - 1) % C != 0) return fail(DMND_E_ARG, "dmnd_extend: query block size is not a multiple of the query contexts");
+	h.ref_letters = (double)(tl.back() - tl.front() - ((int64_t)tl.size() - 1));
+	return DMND_OK;
+}
+
+// The front half of dmnd_extend, up to the device plan (shared with dmnd_extend_plan_device): Hauser bias, upload of the hits,
+// xdrop_seg_kernel, the gapped filter when it is on, plan_on_device. n_queries: queries with hits (split_by_query).
+// (read once per process, outside the template below: one copy whatever the number of its instantiations)
+bool env_xdrop_gpu() { static const bool on = [] { const char* e = std::getenv("DMND_EXTEND_XDROP_GPU"); return !e || e[0] != '0'; }(); return on; }
+bool env_plan_gpu() { static const bool on = [] { const char* e = std::getenv("DMND_EXTEND_PLAN_GPU"); return !e || e[0] != '0'; }(); return on; }
+struct ExtendFront {
+	const int8_t* cbs = nullptr;          // host copy of the bias, made only when the host walks the letters itself
+	bool bias_pending = false;            // work of the front half is still in flight on the context's stream
+	const XdropSeg* xd = nullptr;         // non-NULL: the x-drop segments of all hits are in c->xd_out
+	bool try_plan = false, gf_on = false, planned = false;
+	std::vector<uint8_t> gf;              // gapped filter flags on the host (only when the host plans)
+	DevPlan plan;
+};
+template<typename Lap>
+int extend_front(dmnd_ctx* c, const HostCfg& h, const dmnd_seed_hit* hits, int64_t n_hits, size_t n_queries, Lap lap, TraceLaps& trp, ExtendFront& f)
+{
+	const std::vector<int64_t>& ql = c->limits[DMND_QUERY];
+	f.cbs = nullptr;
+	f.bias_pending = false;
+	const bool xdrop_gpu = env_xdrop_gpu();
+	if (!h.use_cbs) {
+		c->cbs_len = 0;                                     // --comp-based-stats 0: no bias anywhere on the path
+	}
+	else {
+		HIP_TRY(hipSetDevice(c->device));
+		const bool host_walks = !(xdrop_gpu && !h.ext_full && n_hits > 0);
+		if (c->cbs.cap < (size_t)ql.back() + 256) c->cbs_generation = ~(uint64_t)0;      // (the buffer is about to be replaced)
+		if (int rc = c->cbs.ensure((size_t)ql.back() + 256)) return rc;
+		if (host_walks && c->pinned_cbs_cap < (size_t)ql.back() + 64) {
+			if (c->pinned_cbs) (void)hipHostFree(c->pinned_cbs);
+			c->pinned_cbs = nullptr; c->pinned_cbs_cap = 0;
+			HIP_TRY(hipHostMalloc((void**)&c->pinned_cbs, (size_t)ql.back() + 64, hipHostMallocDefault));
+			c->pinned_cbs_cap = (size_t)ql.back() + 64;
+		}
+		// Computed once per query block (dmnd_ctx::query_generation changes whenever the block's letters do) for ALL its sequences and
+		// kept in HBM next to the block: every later call against another database block finds it there. The host copy is only made
+		// when the host is going to walk letters itself (DMND_EXTEND_XDROP_GPU=0).
+		if (c->cbs_generation != c->query_generation || c->cbs_len != ql.back()) {
+			BiasArgs ba;
+			ba.block = c->block[DMND_QUERY].as<int8_t>(); ba.limits = c->d_limits[DMND_QUERY].as<int64_t>(); ba.n_seqs = (int64_t)ql.size() - 1;
+			ba.ids = nullptr;
+			ba.matrix = c->matrix.as<int8_t>(); ba.window = h.cbs_window; ba.out = c->cbs.as<int8_t>();
+			for (int i = 0; i < 20; ++i) ba.bg[i] = (float)h.background_scores[i];
+			HIP_TRY(launch_hauser_bias(ba, c->stream));
+			c->cbs_generation = c->query_generation;
+			f.bias_pending = true;                            // awaited after load_hits (extend_range) / before the runners start
+		}
+		c->cbs_len = ql.back();
+		if (host_walks) {
+			HIP_TRY(hipMemcpyAsync(c->pinned_cbs, c->cbs.p, (size_t)ql.back(), hipMemcpyDeviceToHost, c->stream));
+			f.bias_pending = true;
+			f.cbs = c->pinned_cbs;
+		}
+	}
+	trp.lap("bias");
+	// 1a. x-drop ungapped extension of every seed hit on the device (xdrop_seg_kernel), behind the bias kernel on the same stream;
+	// the host's chaining stage picks the segments up instead of walking the letters itself (DMND_EXTEND_XDROP_GPU=0: host walks)
+	f.xd = nullptr;
+	if (xdrop_gpu && !h.ext_full && n_hits > 0) {
+		HIP_TRY(hipSetDevice(c->device));
+		if (int rc = c->xd_hits.ensure((size_t)n_hits * sizeof(dmnd_seed_hit))) return rc;
+		if (int rc = c->xd_out.ensure((size_t)n_hits * sizeof(XdropSeg))) return rc;
+		HIP_TRY(hipMemcpyAsync(c->xd_hits.p, hits, (size_t)n_hits * sizeof(dmnd_seed_hit), hipMemcpyHostToDevice, c->stream));
+		XdropArgs xa;
+		xa.qblock = c->block[DMND_QUERY].as<int8_t>(); xa.tblock = c->block[DMND_TARGET].as<int8_t>();
+		xa.cbs = h.use_cbs ? c->cbs.as<int8_t>() : nullptr;
+		xa.qlimits = c->d_limits[DMND_QUERY].as<int64_t>(); xa.matrix = c->matrix.as<int8_t>();
+		xa.hits = c->xd_hits.as<dmnd_seed_hit>(); xa.n_hits = n_hits; xa.xdrop = h.xdrop; xa.out = c->xd_out.as<XdropSeg>();
+		HIP_TRY(launch_xdrop_segs(xa, c->stream));
+		f.bias_pending = true;                                // the same wait covers it
+		f.xd = reinterpret_cast<const XdropSeg*>(1);          // (set below, once it is known whether the host needs the copy)
+	}
+	lap(4, 1);
+	// The groups, segments, chains and bands of every (query, target) pair on the device (plan_kernels.hip; one query context, banded
+	// extension). DMND_EXTEND_PLAN_GPU=0: the host plans, as up to round 5.
+	f.try_plan = env_plan_gpu() && f.xd && h.contexts == 1 && n_hits < ((int64_t)1 << 31);
+	// 1b. gapped filter of every seed hit in one launch (only --sensitive and above; extend.cpp:205-213)
+	f.gf.clear();
+	c->gf_ms = 0;
+	f.gf_on = c->gapped_filter_evalue > 0.0 && n_hits > 0 && h.global_ranking == 0;      // (extend.cpp:206: not for globally ranked targets)
+	if (f.gf_on) {
+		if (f.bias_pending) { HIP_TRY(sync_stream(c->stream)); f.bias_pending = false; }      // the filter's profile reads the bias
+		if (!f.try_plan) f.gf.resize((size_t)n_hits);
+		// (with the device planner the hits are in HBM already and the flags stay there)
+		if (int rc = dmnd_gapped_filter_on(c, hits, f.try_plan ? c->xd_hits.as<dmnd_seed_hit>() : nullptr, n_hits, h.use_cbs ? 1 : 0, f.try_plan ? nullptr : f.gf.data(), nullptr)) return rc;
+	}
+	lap(4, 2);
+	trp.lap("x-drop enqueued, gapped filter");
+	f.plan = DevPlan();
+	f.planned = false;
+	if (f.try_plan) {
+		if (int rc = plan_on_device(c, device_cfg(h), n_hits, f.gf_on, f.plan, f.planned)) return rc;
+		trp.lap("planned");
+		if (f.planned && f.plan.n_queries != n_queries) f.planned = false;
+		if (!f.planned && f.gf_on) {                            // hits out of order (a caller's own list): the host plans, and needs the flags
+			f.gf.resize((size_t)n_hits);
+			HIP_TRY(copy_now(c->stream, f.gf.data(), c->gf_flags.p, (size_t)n_hits, hipMemcpyDeviceToHost));
+		}
+		f.bias_pending = false;                               // plan_on_device has waited for the stream
+	}
+	return DMND_OK;
+}
+
+}  // namespace
+
 // The whole extension stage for one (query block, reference block) pair on the uploaded blocks. The reference's per-query
 // loop over ranking chunks (extend.cpp:289-336) becomes a batch-synchronous state machine: every pass plans the current
 // chunk of all still-active queries on the host threads and scores all of them in ONE GPU launch.
@@ -1266,39 +1413,8 @@ extern "C" int dmnd_extend(dmnd_ctx* c, const int8_t* qdata, const int8_t* tdata
 		return DMND_OK;
 	}
 	HostCfg h;
-	make_cfg(c, h);
-	h.max_target_seqs = c->max_target_seqs;
-	h.max_hsps = c->max_hsps;
-	h.global_ranking = c->global_ranking;
-	if (h.global_ranking > 0 && c->ext_mode != DMND_EXT_FULL) return fail(DMND_E_ARG, "dmnd_extend: globally ranked targets are extended over the full matrix (dmnd_set_extension_mode(DMND_EXT_FULL))");
-	h.top = c->top_percent;
-	h.evaluer = &c->evaluer;
-	h.max_evalue = c->params.max_evalue;
-	h.min_bit_score = c->min_bit_score; h.min_id = c->min_id; h.query_cover = c->query_cover; h.subject_cover = c->subject_cover;
-	if (h.query_cover > 0 && c->query_contexts != 1 && c->source_lens.size() != (ql.size() - 1) / (size_t)c->query_contexts)
-		return fail(DMND_E_ARG, "dmnd_extend: the query cover of translated queries needs the read lengths (dmnd_set_query_source_lengths)");
-	if (h.max_hsps != 1 && c->query_contexts != 1 && c->source_lens.size() != (ql.size() - 1) / (size_t)c->query_contexts)
-		return fail(DMND_E_ARG, "dmnd_extend: several HSPs per target of translated queries need the read lengths (dmnd_set_query_source_lengths)");
-	h.source_lens = c->source_lens.empty() ? nullptr : c->source_lens.data();
-	h.ranking_block_letters = c->ranking_block_letters;
-	h.band_mode_fast = c->band_mode_fast;
-	h.ext_full = c->ext_mode == DMND_EXT_FULL;
-	if (c->ext_mode == DMND_EXT_BANDED_FAST) h.band_mode_fast = 1; else if (c->ext_mode == DMND_EXT_BANDED_SLOW) h.band_mode_fast = 0;
-	h.contexts = c->query_contexts;
-	h.cbs_mode = c->comp_based_stats;
-	h.use_cbs = cbs_hauser(h.cbs_mode);
 	CbsModel cbs_model;
-	if (cbs_matrix_adjust(h.cbs_mode)) {
-		// basic/config.cpp:700, :837, :688
-		if (c->query_contexts != 1) return fail(DMND_E_ARG, "This mode of composition based stats is not supported for translated searches.");
-		if (h.global_ranking > 0) return fail(DMND_E_ARG, "Global ranking is not supported in this mode.");
-		cbs_model_init(cbs_model, c->params);
-		if (!cbs_model.valid) return fail(DMND_E_ARG, "This value for --comp-based-stats is not supported when using a custom scoring matrix.");
-		h.cbs_model = &cbs_model;
-	}
-	const uint32_t C = (uint32_t)h.contexts;
-	if ((ql.size() - 1) % C != 0) return fail(DMND_E_ARG, "dmnd_extend: query block size is not a multiple of the query contexts");
-	h.ref_letters = (double)(tl.back() - tl.front() - ((int64_t)tl.size() - 1));
+	if (int rc = extend_cfg(c, h, cbs_model)) return rc;
 	if (hsp_values == 0) hsp_values = 510;
 	threads = std::max(1, threads);
 	for (double& x : c->ext_stats) x = 0;
@@ -1314,90 +1430,14 @@ extern "C" int dmnd_extend(dmnd_ctx* c, const int8_t* qdata, const int8_t* tdata
 	trp.lap("queries split");
 	// One launch over the whole query block (bias_kernels.hip: closed-form window per position), result kept in HBM next to
 	// the block for the swipe kernels and the gapped filter, and copied into a pinned host buffer for the host's x-drop stage.
-	const int8_t* cbs = nullptr;
-	bool bias_pending = false;
-	static const bool xdrop_gpu = [] { const char* e = std::getenv("DMND_EXTEND_XDROP_GPU"); return !e || e[0] != '0'; }();
-	if (!h.use_cbs) {
-		c->cbs_len = 0;                                     // --comp-based-stats 0: no bias anywhere on the path
-	}
-	else {
-		HIP_TRY(hipSetDevice(c->device));
-		const bool host_walks = !(xdrop_gpu && !h.ext_full && n_hits > 0);
-		if (c->cbs.cap < (size_t)ql.back() + 256) c->cbs_generation = ~(uint64_t)0;      // (the buffer is about to be replaced)
-		if (int rc = c->cbs.ensure((size_t)ql.back() + 256)) return rc;
-		if (host_walks && c->pinned_cbs_cap < (size_t)ql.back() + 64) {
-			if (c->pinned_cbs) (void)hipHostFree(c->pinned_cbs);
-			c->pinned_cbs = nullptr; c->pinned_cbs_cap = 0;
-			HIP_TRY(hipHostMalloc((void**)&c->pinned_cbs, (size_t)ql.back() + 64, hipHostMallocDefault));
-			c->pinned_cbs_cap = (size_t)ql.back() + 64;
-		}
-		// Computed once per query block (dmnd_ctx::query_generation changes whenever the block's letters do) for ALL its sequences and
-		// kept in HBM next to the block: every later call against another database block finds it there. The host copy is only made
-		// when the host is going to walk letters itself (DMND_EXTEND_XDROP_GPU=0).
-		if (c->cbs_generation != c->query_generation || c->cbs_len != ql.back()) {
-			BiasArgs ba;
-			ba.block = c->block[DMND_QUERY].as<int8_t>(); ba.limits = c->d_limits[DMND_QUERY].as<int64_t>(); ba.n_seqs = (int64_t)ql.size() - 1;
-			ba.ids = nullptr;
-			ba.matrix = c->matrix.as<int8_t>(); ba.window = h.cbs_window; ba.out = c->cbs.as<int8_t>();
-			for (int i = 0; i < 20; ++i) ba.bg[i] = (float)h.background_scores[i];
-			HIP_TRY(launch_hauser_bias(ba, c->stream));
-			c->cbs_generation = c->query_generation;
-			bias_pending = true;                            // awaited after load_hits (extend_range) / before the runners start
-		}
-		c->cbs_len = ql.back();
-		if (host_walks) {
-			HIP_TRY(hipMemcpyAsync(c->pinned_cbs, c->cbs.p, (size_t)ql.back(), hipMemcpyDeviceToHost, c->stream));
-			bias_pending = true;
-			cbs = c->pinned_cbs;
-		}
-	}
-	trp.lap("bias");
-	// 1a. x-drop ungapped extension of every seed hit on the device (xdrop_seg_kernel), behind the bias kernel on the same stream;
-	// the host's chaining stage picks the segments up instead of walking the letters itself (DMND_EXTEND_XDROP_GPU=0: host walks)
-	const XdropSeg* xd = nullptr;
-	if (xdrop_gpu && !h.ext_full && n_hits > 0) {
-		HIP_TRY(hipSetDevice(c->device));
-		if (int rc = c->xd_hits.ensure((size_t)n_hits * sizeof(dmnd_seed_hit))) return rc;
-		if (int rc = c->xd_out.ensure((size_t)n_hits * sizeof(XdropSeg))) return rc;
-		HIP_TRY(hipMemcpyAsync(c->xd_hits.p, hits, (size_t)n_hits * sizeof(dmnd_seed_hit), hipMemcpyHostToDevice, c->stream));
-		XdropArgs xa;
-		xa.qblock = c->block[DMND_QUERY].as<int8_t>(); xa.tblock = c->block[DMND_TARGET].as<int8_t>();
-		xa.cbs = h.use_cbs ? c->cbs.as<int8_t>() : nullptr;
-		xa.qlimits = c->d_limits[DMND_QUERY].as<int64_t>(); xa.matrix = c->matrix.as<int8_t>();
-		xa.hits = c->xd_hits.as<dmnd_seed_hit>(); xa.n_hits = n_hits; xa.xdrop = h.xdrop; xa.out = c->xd_out.as<XdropSeg>();
-		HIP_TRY(launch_xdrop_segs(xa, c->stream));
-		bias_pending = true;                                // the same wait covers it
-		xd = reinterpret_cast<const XdropSeg*>(1);          // (set below, once it is known whether the host needs the copy)
-	}
-	lap(4, 1);
-	// The groups, segments, chains and bands of every (query, target) pair on the device (plan_kernels.hip; one query context, banded
-	// extension). DMND_EXTEND_PLAN_GPU=0: the host plans, as up to round 5.
-	static const bool plan_gpu = [] { const char* e = std::getenv("DMND_EXTEND_PLAN_GPU"); return !e || e[0] != '0'; }();
-	const bool try_plan = plan_gpu && xd && h.contexts == 1 && n_hits < ((int64_t)1 << 31);
-	// 1b. gapped filter of every seed hit in one launch (only --sensitive and above; extend.cpp:205-213)
-	std::vector<uint8_t> gf;
-	c->gf_ms = 0;
-	const bool gf_on = c->gapped_filter_evalue > 0.0 && n_hits > 0 && h.global_ranking == 0;      // (extend.cpp:206: not for globally ranked targets)
-	if (gf_on) {
-		if (bias_pending) { HIP_TRY(sync_stream(c->stream)); bias_pending = false; }      // the filter's profile reads the bias
-		if (!try_plan) gf.resize((size_t)n_hits);
-		// (with the device planner the hits are in HBM already and the flags stay there)
-		if (int rc = dmnd_gapped_filter_on(c, hits, try_plan ? c->xd_hits.as<dmnd_seed_hit>() : nullptr, n_hits, h.use_cbs ? 1 : 0, try_plan ? nullptr : gf.data(), nullptr)) return rc;
-	}
-	lap(4, 2);
-	trp.lap("x-drop enqueued, gapped filter");
-	DevPlan plan;
-	bool planned = false;
-	if (try_plan) {
-		if (int rc = plan_on_device(c, device_cfg(h), n_hits, gf_on, plan, planned)) return rc;
-		trp.lap("planned");
-		if (planned && plan.n_queries != qr.size()) planned = false;
-		if (!planned && gf_on) {                            // hits out of order (a caller's own list): the host plans, and needs the flags
-			gf.resize((size_t)n_hits);
-			HIP_TRY(copy_now(c->stream, gf.data(), c->gf_flags.p, (size_t)n_hits, hipMemcpyDeviceToHost));
-		}
-		bias_pending = false;                               // plan_on_device has waited for the stream
-	}
+	ExtendFront f;
+	if (int rc = extend_front(c, h, hits, n_hits, qr.size(), lap, trp, f)) return rc;
+	const int8_t* const cbs = f.cbs;
+	bool bias_pending = f.bias_pending;
+	const XdropSeg* xd = f.xd;
+	const std::vector<uint8_t>& gf = f.gf;
+	DevPlan& plan = f.plan;
+	const bool planned = f.planned;
 	if (xd && (!planned || plan.n_on_host > 0)) {
 		if (int rc = c->xd_host.ensure((size_t)n_hits * sizeof(XdropSeg))) return rc;      // (page-locked: allocated when first needed)
 		HIP_TRY(hipMemcpyAsync(c->xd_host.p, c->xd_out.p, (size_t)n_hits * sizeof(XdropSeg), hipMemcpyDeviceToHost, c->stream));
@@ -1822,6 +1862,49 @@ extern "C" int dmnd_extend_plan_stats(const dmnd_ctx* c, double out[3])
 {
 	if (!c || !out) return fail(DMND_E_ARG, "dmnd_extend_plan_stats: NULL argument");
 	for (int i = 0; i < 3; ++i) out[i] = c->ext_plan_stats[i];
+	return DMND_OK;
+}
+
+// What the device planner makes of a hit list, for the tests (tests/test_gpu_plan_device.py): extend_front -- dmnd_extend's own front
+// half -- then the planner's lists copied out. rows: the bands of the groups the device planned, in group order, in the record of
+// dmnd_extend_plan; groups: one record per (query, target) group. A list that is not in (query, location, seed offset) order is
+// not planned: info->planned = 0, info->unsorted = 1, no rows and no groups.
+extern "C" int dmnd_extend_plan_device(dmnd_ctx* c, const dmnd_seed_hit* hits, int64_t n_hits, dmnd_plan_target* rows, int64_t row_cap,
+	dmnd_plan_group* groups, int64_t group_cap, dmnd_plan_device_info* info)
+{
+	if (!c || (!hits && n_hits) || n_hits < 0 || !info || (!rows && row_cap > 0) || (!groups && group_cap > 0)) return fail(DMND_E_ARG, "dmnd_extend_plan_device: bad argument");
+	*info = dmnd_plan_device_info{ 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+	if (c->limits[DMND_QUERY].size() < 2 || c->limits[DMND_TARGET].size() < 2) return fail(DMND_E_ARG, "dmnd_extend_plan_device: blocks must be uploaded with limits");
+	if (c->frame_shift > 0) return fail(DMND_E_ARG, "dmnd_extend_plan_device: frameshift alignment has no device plan");
+	HostCfg h;
+	CbsModel cbs_model;
+	if (int rc = extend_cfg(c, h, cbs_model)) return rc;
+	TraceLaps trp("dmnd_extend_plan_device");
+	const std::vector<Range> qr = split_by_query(hits, n_hits, h.contexts);
+	ExtendFront f;
+	if (int rc = extend_front(c, h, hits, n_hits, qr.size(), [](int, int = -1) {}, trp, f)) return rc;
+	if (f.bias_pending) HIP_TRY(sync_stream(c->stream));
+	if (n_hits > 0 && !f.try_plan) return fail(DMND_E_ARG, "dmnd_extend_plan_device: this configuration is planned by the host (translated queries, --ext full, DMND_EXTEND_PLAN_GPU=0 or DMND_EXTEND_XDROP_GPU=0)");
+	info->unsorted = f.plan.unsorted ? 1 : 0;
+	if (!f.planned) return DMND_OK;
+	DevPlan& plan = f.plan;
+	if (int rc = plan_fetch_lists(c, plan)) return rc;
+	info->planned = 1;
+	info->n_groups = plan.n_groups; info->n_queries = plan.n_queries; info->n_bands = plan.n_bands; info->n_on_host = plan.n_on_host;
+	info->n_chain = plan.n_chain; info->n_chain_big = plan.n_chain_big; info->n_relisted = plan.n_relisted;
+	if ((int64_t)plan.n_groups > group_cap || (int64_t)plan.n_bands > row_cap) return fail(DMND_E_CAP, "dmnd_extend_plan_device: output buffer too small");
+	int64_t n_rows = 0;
+	for (uint32_t g = 0; g < plan.n_groups; ++g) {
+		const PlanGroup& pg = plan.groups[g];
+		const uint32_t query = hits[pg.hit_begin].query;
+		const bool on_host = pg.n_bands == PLAN_ON_HOST;
+		groups[g] = dmnd_plan_group{ query, pg.target, pg.n_hits, on_host ? 0u : (uint32_t)pg.n_bands, pg.pass, (uint8_t)(on_host ? 1 : 0), { 0, 0 } };
+		if (on_host) continue;
+		if (pg.band_begin + (uint32_t)pg.n_bands > plan.n_bands) return fail(DMND_E_CAP, "dmnd_extend_plan_device: a group's bands lie outside the band list");
+		for (uint32_t k = 0; k < pg.n_bands; ++k)
+			rows[n_rows++] = dmnd_plan_target{ query, pg.target, plan.bands[pg.band_begin + k].d_begin, plan.bands[pg.band_begin + k].d_end, (int32_t)pg.score };
+	}
+	if (n_rows != (int64_t)plan.n_bands) return fail(DMND_E_CAP, "dmnd_extend_plan_device: the groups' band counts do not add up to the band list");
 	return DMND_OK;
 }
 

@@ -31,7 +31,7 @@ struct PlanGroup {             // the seed hits of one (query, target) pair = Se
 };
 struct PlanBand { int32_t d_begin, d_end; };
 struct PlanQuery { uint32_t query, group_begin, hit_begin; };      // one per query that has hits, in hit order; one sentinel entry behind the last
-struct PlanCounters { uint32_t n_groups, n_queries, n_bands, unsorted, n_on_host, n_chain, n_chain_big, pad; };      // n_chain / n_chain_big: groups with two to PLAN_SMALL_SEGS / more segments (plan_chain_list_kernel)
+struct PlanCounters { uint32_t n_groups, n_queries, n_bands, unsorted, n_on_host, n_chain, n_chain_big, n_relisted; };      // n_chain / n_chain_big: groups with two to PLAN_SMALL_SEGS / more segments (plan_chain_list_kernel); n_relisted: small ones listed again for the large workspace (counted in n_chain_big too)
 
 struct PlanArgs {
 	const int8_t* qblock; const int8_t* tblock;

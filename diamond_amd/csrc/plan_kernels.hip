@@ -153,7 +153,10 @@ __global__ __launch_bounds__(64) void plan_segments_kernel(PlanArgs a)
 		return;
 	}
 	if (ns > PLAN_MAX_SEGS) { grp.n_bands = PLAN_ON_HOST; a.groups[g] = grp; return; }
-	// stable by (diagonal, segment start): the x-drop walk to the left may carry a later hit's segment in front of an earlier one's
+	// stable by (diagonal, segment start), the order the chaining expects. It moves nothing: a kept hit lies behind the end of the segment
+	// before it on its diagonal, and its walk to the left arrives at the earlier hit with a running best no lower than the one the earlier
+	// walk started from, so it stops no further left -- its segment begins at or behind the earlier one's. Kept as the statement of the
+	// order, not for an input that needs it (tests/test_gpu_plan_device.py asserts the order is unchanged on every group it builds).
 	for (int x = 1; x < ns; ++x) {
 		const int vi = L.hi[x][lane], vj = L.hj[x][lane], vl = L.hs[x][lane], vs = L.ss[x][lane];
 		int p = x;
@@ -176,15 +179,12 @@ __global__ __launch_bounds__(64) void plan_segments_kernel(PlanArgs a)
 // 6 KB workspace for the rest and for a small one whose links did not fit (it is appended to the other list). A call with few
 // hits (PlanArgs::small_segs = 0) uses the large form only: each kernel's time is the one longest chain in it (~0.1 ms: the junction
 // search reads letters one dependent load at a time), and two kernels would pay that twice.
+// The retry of a small group: with at most four segments the 16 links cannot run out -- sweep() links a segment to each earlier one at
+// most twice (once into it, once back when it overhangs), 2 * (1 + 2 + 3) = 12 -- so only the 4 chains or the 5 walk frames can. No
+// such input is known (tests/test_chain_graph.py counts none in 7 700 random groups, tests/test_gpu_plan_device.py asserts the
+// re-listed count the CPU predicts, 0 so far), and no proof that there is none: the retry stays.
 enum { PLAN_SMALL_SEGS = 4 };
-template<int NODES, int LINKS, int CHAINS>
-struct ChainLdsT {
-	ChainWorkspaceT<FixedChainPolicy, NODES, LINKS, CHAINS> ws;
-	Seg sg[NODES];
-	FixedVec<Chain, CHAINS> chains;
-};
-template<int NODES, int LINKS, int CHAINS>
-struct ChainLanes { enum { bytes = (int)sizeof(ChainLdsT<NODES, LINKS, CHAINS>), fit = 48 * 1024 / bytes, value = fit > 64 ? 64 : fit }; };
+// (ChainLdsT, ChainLanes: chain_graph.h)
 
 __global__ __launch_bounds__(256) void plan_chain_list_kernel(PlanArgs a)
 {
@@ -240,8 +240,11 @@ __global__ __launch_bounds__(64) void plan_chain_kernel(PlanArgs a)
 	if (L.ws.overflowed() || L.chains.overflow) {
 		if (SMALL) {      // once more with the large workspace (the group keeps its PLAN_NEED_CHAIN state)
 			a.chain_list[a.chain_cap - 1 - atomicAdd(&a.counters->n_chain_big, 1u)] = g;
+			atomicAdd(&a.counters->n_relisted, 1u);
 			return;
 		}
+		// (16 segments can outgrow 96 links: sixteen overlapping segments two diagonals apart on a two-letter repeat link pairwise, in both
+		// directions; tests/test_gpu_plan_device.py builds such groups)
 		grp.band_begin = 0; grp.n_bands = PLAN_ON_HOST; a.groups[g] = grp;
 		return;
 	}
@@ -249,6 +252,7 @@ __global__ __launch_bounds__(64) void plan_chain_kernel(PlanArgs a)
 	insertion_sort(L.chains.begin(), L.chains.end(), [](const Chain& x, const Chain& y) { return x.d_min < y.d_min; });      // std::stable_sort by d_min
 	BandOut out{ a.band_slots + b, (int)grp.n_hits, 0, false };
 	merge_bands(L.chains, (int)L.chains.size(), band_for_dev(qlen, a.band_fast != 0), qlen, tlen, out);
+	// (a guard no input reaches: at most CHAINS = 16 chains give at most 16 bands, below PLAN_NEED_CHAIN)
 	grp.n_bands = out.overflow || out.n >= PLAN_NEED_CHAIN ? (uint8_t)PLAN_ON_HOST : (uint8_t)out.n;
 	a.groups[g] = grp;
 }

@@ -49,6 +49,14 @@ MATCH_DTYPE = np.dtype([("query", "<u4"), ("target", "<u4"), ("ungapped_score", 
 assert MATCH_DTYPE.itemsize == 104
 
 PLAN_DTYPE = np.dtype([("query", "<u4"), ("target", "<u4"), ("d_begin", "<i4"), ("d_end", "<i4"), ("ungapped_score", "<i4")])
+PLAN_GROUP_DTYPE = np.dtype([("query", "<u4"), ("target", "<u4"), ("n_hits", "<u4"), ("n_bands", "<u4"), ("pass", "u1"), ("on_host", "u1"), ("pad", "u1", (2,))])
+assert PLAN_DTYPE.itemsize == 20 and PLAN_GROUP_DTYPE.itemsize == 20
+
+
+class PlanDeviceInfo(ctypes.Structure):
+    """dmnd_plan_device_info"""
+    _fields_ = [(n, ctypes.c_int64) for n in "n_groups n_queries n_bands n_on_host n_chain n_chain_big n_relisted".split()] + \
+               [("planned", ctypes.c_int32), ("unsorted", ctypes.c_int32)]
 
 DP_TARGET_DTYPE = np.dtype([("query_off", "<i8"), ("target_off", "<i8"), ("cbs_off", "<i8"), ("query_len", "<i4"),
                             ("target_len", "<i4"), ("d_begin", "<i4"), ("d_end", "<i4")], align=True)
@@ -70,7 +78,7 @@ EXPORTS = ["dmnd_abi_version", "dmnd_last_error", "dmnd_default_params", "dmnd_c
            "dmnd_set_db_letters", "dmnd_upload_block", "dmnd_upload_cbs", "dmnd_banded_swipe",
            "dmnd_banded_swipe_host", "dmnd_banded_cols", "dmnd_evalue", "dmnd_bitscore", "dmnd_evalue_p",
            "dmnd_bitscore_p", "dmnd_evalue_batch", "dmnd_last_kernel_ms", "dmnd_seed_params_fast", "dmnd_seed_params_default", "dmnd_seed_search",
-           "dmnd_seed_hits", "dmnd_seed_kernel_ms", "dmnd_extend_plan", "dmnd_extend", "dmnd_extend_stats", "dmnd_extend_plan_stats", "dmnd_extend_device_stats", "dmnd_extend_reserve", "dmnd_extend_records_device", "dmnd_join_contexts_device", "dmnd_format_tab", "dmnd_set_max_target_seqs",
+           "dmnd_seed_hits", "dmnd_seed_kernel_ms", "dmnd_extend_plan", "dmnd_extend", "dmnd_extend_stats", "dmnd_extend_plan_stats", "dmnd_extend_plan_device", "dmnd_extend_device_stats", "dmnd_extend_reserve", "dmnd_extend_records_device", "dmnd_join_contexts_device", "dmnd_format_tab", "dmnd_set_max_target_seqs",
            "dmnd_seed_params_sensitive", "dmnd_set_gapped_filter", "dmnd_gapped_filter", "dmnd_gapped_filter_ms",
            "dmnd_set_query_contexts", "dmnd_translate", "dmnd_format_tab_translated", "dmnd_mask_block", "dmnd_mask_kernel_ms", "dmnd_seed_params_preset", "dmnd_set_comp_based_stats",
            "dmnd_seed_params_set_index_chunks", "dmnd_join_blocks", "dmnd_set_sensitivity", "dmnd_touch_streams",
@@ -938,6 +946,22 @@ class Context:
         self.lib.dmnd_extend_plan_stats.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
         self._check(self.lib.dmnd_extend_plan_stats(self.h, st))
         return dict(groups=int(st[0]), groups_on_host=int(st[1]), bands=int(st[2]))
+
+    def extend_plan_device(self, hits):
+        """dmnd_extend_plan_device: what the device planner makes of a hit list on the uploaded blocks. Returns (rows, groups, info):
+        rows (PLAN_DTYPE) = the bands of the groups the device planned, in group order; groups (PLAN_GROUP_DTYPE) = one record per
+        (query, target) group; info = dict of the planner's counters, `planned` and `unsorted`. A list that is not sorted by
+        (query, subject, seed offset) comes back with planned = False and no rows."""
+        hits = np.ascontiguousarray(hits, dtype=SEED_HIT_DTYPE)
+        cap = max(1, hits.size)
+        rows, groups, info = np.zeros(cap, dtype=PLAN_DTYPE), np.zeros(cap, dtype=PLAN_GROUP_DTYPE), PlanDeviceInfo()
+        v = ctypes.c_void_p
+        self.lib.dmnd_extend_plan_device.argtypes = [v, v, ctypes.c_int64, v, ctypes.c_int64, v, ctypes.c_int64, ctypes.POINTER(PlanDeviceInfo)]
+        self._check(self.lib.dmnd_extend_plan_device(self.h, hits.ctypes.data_as(v) if hits.size else None, ctypes.c_int64(hits.size), rows.ctypes.data_as(v), ctypes.c_int64(cap),
+                                                     groups.ctypes.data_as(v), ctypes.c_int64(cap), ctypes.byref(info)))
+        d = {n: int(getattr(info, n)) for n, _ in PlanDeviceInfo._fields_}
+        d["planned"], d["unsorted"] = bool(d["planned"]), bool(d["unsorted"])
+        return rows[:d["n_bands"]].copy(), groups[:d["n_groups"]].copy(), d
 
     def extend_device_stats(self):
         """(queries extended on the device, of them handed back to the host -- queries_capped of those because they were still ranking

@@ -588,6 +588,28 @@ int dmnd_extend_stats(const dmnd_ctx* ctx, double out[12]);
  * or 16 segments), [2] round-1 bands it planned; all 0 = the host planned (several contexts, --ext full, hits not in
  * (query, location) order). Lets a test tell which path produced the records. */
 int dmnd_extend_plan_stats(const dmnd_ctx* ctx, double out[3]);
+/* Test entry: the device planner's own result for a hit list (both blocks uploaded). Runs the front half of dmnd_extend -- Hauser
+ * bias, upload of the hits, x-drop extension, gapped filter when it is on, the planner -- and copies the plan out. rows: the bands
+ * of the groups the device planned, in group order, in the record of dmnd_extend_plan (row_cap >= n_hits is enough); groups: one
+ * record per (query, target) group (group_cap >= n_hits is enough). A list that is not sorted by (query, subject, seed_offset) is
+ * not planned: planned = 0, unsorted = 1, no rows. DMND_PLAN_SMALL_HITS (environment, read per call): the number of hits from
+ * which a call chains its groups of up to four segments in a kernel of their own (default 2^18). */
+typedef struct {
+	uint32_t query, target;       /* block sequence ids */
+	uint32_t n_hits;
+	uint32_t n_bands;             /* its rows (0 when left to the host) */
+	uint8_t pass;                 /* some hit passed the gapped filter (1 when the filter is off); 0 = no rows */
+	uint8_t on_host;              /* left to the host planner: no rows here */
+	uint8_t pad[2];
+} dmnd_plan_group;
+typedef struct {
+	int64_t n_groups, n_queries, n_bands, n_on_host;
+	int64_t n_chain, n_chain_big; /* entries of the two chaining lists; n_chain_big counts a re-listed group again */
+	int64_t n_relisted;           /* groups the small chaining workspace overflowed on, listed again for the large one */
+	int32_t planned, unsorted;
+} dmnd_plan_device_info;
+int dmnd_extend_plan_device(dmnd_ctx* ctx, const dmnd_seed_hit* hits, int64_t n_hits, dmnd_plan_target* rows, int64_t row_cap,
+	dmnd_plan_group* groups, int64_t group_cap, dmnd_plan_device_info* info);
 /* Round 6: for the queries whose targets fit one ranking chunk (src/align/extend.cpp:79-92) the rest of the extension stage runs in
  * HBM as well -- DpTargets and their launch order from the bands (DP::BandedSwipe::bin, src/dp/swipe/swipe_wrapper.cpp:75-102), best
  * HSP per target and report cutoff (src/align/gapped_score.cpp:182-268), culling (src/align/culling.cpp:97-113,189-203), round 2 as a

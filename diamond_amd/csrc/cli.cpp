@@ -33,6 +33,7 @@
 #include <sys/mman.h>
 #include <sys/stat.h>
 #include "../../include/diamond_hip.h"
+#include "filter_core.h"
 
 namespace {
 
@@ -479,6 +480,7 @@ struct Options {
 	int unal = -1;                  // --unal: report queries without alignments (-1 = the format's default)
 	std::string header;             // --header [simple|verbose|0]
 	double min_id = 0, query_cover = 0, subject_cover = 0, min_score = 0;      // --id, --query-cover, --subject-cover, --min-score
+	double approx_id = 0; bool approx_id_given = false;      // --approx-id (config.approx_min_id)
 };
 
 Options parse(int argc, char** argv)
@@ -514,6 +516,7 @@ Options parse(int argc, char** argv)
 		else if (a == "-e" || a == "--evalue") o.evalue = std::atof(need(i).c_str());
 		else if (a == "--fast") o.fast = true;
 		else if (a == "--id") o.min_id = std::atof(need(i).c_str());
+		else if (a == "--approx-id") { o.approx_id = std::atof(need(i).c_str()); o.approx_id_given = true; }
 		else if (a == "--query-cover") o.query_cover = std::atof(need(i).c_str());
 		else if (a == "--subject-cover") o.subject_cover = std::atof(need(i).c_str());
 		else if (a == "--min-score") o.min_score = std::atof(need(i).c_str());
@@ -590,10 +593,11 @@ Options parse(int argc, char** argv)
 		else if (a == "--global-ranking" || a == "-g") { o.global_ranking = std::atoi(need(i).c_str()); if (o.global_ranking < 0) throw std::runtime_error("Invalid value for --global-ranking."); }
 		else if (a == "--max-hsps") { o.max_hsps = std::atoi(need(i).c_str()); if (o.max_hsps < 0) throw std::runtime_error("Invalid value for --max-hsps."); }
 		else if (a == "--custom-matrix") throw std::runtime_error("--custom-matrix is not part of this build (the standard matrices of --matrix are).");
-		else if (a == "-g" || a == "--global-ranking" || a == "--swipe" || a == "--iterate" || a == "--approx-id" || a == "--taxonlist" || a == "--taxon-exclude" || a == "--seqidlist")
+		else if (a == "-g" || a == "--global-ranking" || a == "--swipe" || a == "--iterate" || a == "--taxonlist" || a == "--taxon-exclude" || a == "--seqidlist")
 			throw std::runtime_error(a + " is not part of this build.");
 		else throw std::runtime_error("Invalid option: " + a);
 	}
+	if (o.approx_id_given && o.min_id != 0.0) throw std::runtime_error("Incompatible options: --approx-id, --id.");      // run/config.cpp:168
 	if (o.top >= 0.0 && o.k_given) throw std::runtime_error("--top and -k/--max-target-seqs are mutually exclusive.");      // basic/config.cpp:674-675
 	if (o.long_reads) {                                       // basic/config.cpp:680-686
 		o.range_culling = true;
@@ -864,6 +868,8 @@ int run_blastp(const Options& o)
 	double gf_evalue = 0.0;
 	chk(dmnd_seed_params_preset(&sp, sens, threads, &p, &gf_evalue));
 	if (o.gapped_filter_evalue >= 0.0) gf_evalue = o.gapped_filter_evalue;
+	// search/setup.cpp:343: the mode's Hamming identities, raised by what --approx-id asks for; an explicit --id2 overrides both
+	sp.hamming_filter_id = std::max<decltype(sp.hamming_filter_id)>(sp.hamming_filter_id, (decltype(sp.hamming_filter_id))dmnd::hamming_id_cutoff(o.approx_id));
 	if (o.id2 > 0) sp.hamming_filter_id = o.id2;
 	if (o.seed_cut != 0.0) sp.seed_complexity_cut = o.seed_cut * 0.69314718055994530942 * sp.shape_weight[0];
 	if (o.index_chunks > 0) chk(dmnd_seed_params_set_index_chunks(&sp, o.index_chunks, threads));
@@ -882,6 +888,7 @@ int run_blastp(const Options& o)
 		chk(dmnd_set_max_hsps(c, o.max_hsps));
 		chk(dmnd_set_top_percent(c, o.top));
 		chk(dmnd_set_filters(c, o.min_id, o.query_cover, o.subject_cover, o.min_score));
+		chk(dmnd_set_approx_id(c, std::max(0.0, o.approx_id)));      // (the reference reads a value <= 0 as off)
 		chk(dmnd_set_comp_based_stats(c, o.cbs));
 		chk(dmnd_set_query_contexts(c, blastx ? 6 : 1));
 		chk(dmnd_set_frameshift(c, o.frameshift, o.range_culling ? 1 : 0, o.range_cover, 16));
@@ -1793,7 +1800,7 @@ int main(int argc, char** argv)
 				"scoring      --matrix BLOSUM45|50|62|80|90|PAM30|70|250  --gapopen N  --gapextend N  --comp-based-stats 0|1\n"
 				"masking      --masking tantan|seg|none  --motif-masking 0|1\n"
 				"extension    --ext banded-fast|banded-slow|full\n"
-				"reporting    -k N  --max-hsps N  --global-ranking N  --top PCT  -e EVALUE  --min-score BITS  --id PCT  --query-cover PCT  --subject-cover PCT  --no-self-hits\n"
+				"reporting    -k N  --max-hsps N  --global-ranking N  --top PCT  -e EVALUE  --min-score BITS  --id PCT  --approx-id PCT  --query-cover PCT  --subject-cover PCT  --no-self-hits\n"
 				"             --unal 0|1  --un FILE  --al FILE  --header [simple|verbose]  --compress 1  --salltitles  --sallseqid\n"
 				"formats      -f 6 [FIELD...] | 0 (pairwise) | 5 (XML) | 100 (DAA) | 101 (SAM) | 103 (PAF)\n"
 				"translated   --strand both|plus|minus  --query-gencode N  --min-orf N\n"

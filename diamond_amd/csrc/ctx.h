@@ -110,6 +110,7 @@ struct dmnd_ctx {
 	dmnd::DevBuf ext_ev;                      // the host's (e-value, bit score) pairs on their way into the device copy of the records
 	const dmnd_match* ext_records_dev = nullptr; int64_t ext_records_n = -1;      // the records of the last dmnd_extend where they lie in HBM (complete: host e-values in); n = -1: part of them only exists on the host
 	dmnd::PinBuf ext_host;                    // ... its counters, records and query states on the host
+	double ext_filter_stats[2] = { 0, 0 };     // of the last dmnd_extend: records removed by a filter on the device, queries handed back to the host because a filter value lay on its threshold
 	double ext_dev_stats[10] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };      // of the last dmnd_extend: queries extended on the device, of them redone by the host (ambiguous e-value order / 16-bit saturation / chunk cap), items, records, band diagonals x steps, wavefront diagonals x steps, round-2 cells, of them swept again, round-2 sweep ms, queries at the chunk cap
 	std::vector<int32_t> h_bias_ids;           // block sequence ids of the queries with seed hits (Hauser bias of one dmnd_extend call)
 	int64_t block_len[2] = { 0, 0 }, cbs_len = 0;
@@ -179,6 +180,7 @@ struct dmnd_ctx {
 	dmnd::DevBuf alt_targets;                  // masked target copies of the alternative-HSP rounds (extend_host.hip)
 	double top_percent = -1.0;                 // config.toppercent (--top); < 0 = off
 	double min_id = 0, query_cover = 0, subject_cover = 0, min_bit_score = 0;      // --id, --query-cover, --subject-cover, --min-score
+	double approx_id = 0;                      // --approx-id (dmnd_set_approx_id)
 	dmnd_same_title_fn same_title = nullptr;   // --no-self-hits: title comparison of the caller (dmnd_set_no_self_hits)
 	void* same_title_user = nullptr;
 	bool reuse_query_index = false;            // dmnd_set_query_index_reuse

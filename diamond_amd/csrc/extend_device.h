@@ -5,6 +5,7 @@
 #include <vector>
 #include "ctx.h"
 #include "plan_kernels.h"
+#include "filter_core.h"
 
 namespace dmnd {
 
@@ -17,6 +18,8 @@ struct DeviceCfg {
 	int64_t max_swipe_dp = 1000000;
 	bool use_cbs = true;                 // Hauser bias
 	double max_evalue = 0.001;
+	double min_bit_score = 0.0;          // --min-score
+	FilterCfg filters;                   // --id, --approx-id, --query-cover, --subject-cover (filter_core.h)
 };
 
 // What the device planner hands over (page-locked host copies of its lists; valid until the context's next dmnd_extend)

@@ -154,7 +154,10 @@ int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan,
 	const int64_t chunk = h.ranking_chunk;
 	if (chunk > EXT_MAX_CHUNK || plan.n_bands == 0) return DMND_OK;
 	if (((size_t)h.max_target_seqs + 2 * (size_t)chunk) * 24 > ((size_t)60 << 10)) return DMND_OK;      // (the LDS lists of ext_append_kernel)
-	const ExtLayout L = ext_layout(plan.n_groups, plan.n_queries, plan.n_bands, h.max_target_seqs);
+	const bool filt = filters_on(h.filters);
+	// (with filters: the aligned targets of a query and a chunk, and the matches of all rounds -- fewer than 2 k --, fit the LDS list)
+	if (filt && ((size_t)h.max_target_seqs + (size_t)chunk > EXT_FILTER_LIST || 2 * (size_t)h.max_target_seqs > EXT_FILTER_LIST)) return DMND_OK;
+	const ExtLayout L = ext_layout(plan.n_groups, plan.n_queries, plan.n_bands, h.max_target_seqs, filt);
 	const size_t nQ = L.nQ, nR = L.nR;
 	if (int rc = c->ext_dev.ensure(L.bytes)) return rc;
 	Guard guard(c->ext_dev, L.bytes, c->stream);
@@ -167,6 +170,7 @@ int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan,
 	a.hits = plan.dev.hits; a.qlimits = plan.dev.qlimits; a.tlimits = plan.dev.tlimits;
 	a.use_cbs = h.use_cbs ? 1 : 0; a.row_min_items = (uint32_t)std::min<int64_t>(sweep_rows_min_items(), 0xffffffffll); a.chunk_size = (uint32_t)chunk; a.k = h.max_target_seqs; a.max_swipe_dp = h.max_swipe_dp;
 	const Evaluer& E = c->evaluer;
+	a.min_bit_score = h.min_bit_score; a.filt = h.filters; a.filt_on = filt ? 1 : 0;
 	a.ev = ExtEvalue{ E.lambda, E.K, E.ln_k, E.db_letters, E.a, E.b, E.alpha, E.beta, E.sigma, E.tau, E.v_thr, E.c_thr, h.max_evalue };
 	a.qstate = reinterpret_cast<uint8_t*>(d + L.o_qstate); a.q_active = reinterpret_cast<uint8_t*>(d + L.o_qactive);
 	a.q_i0 = reinterpret_cast<uint32_t*>(d + L.o_qi0); a.q_i1 = reinterpret_cast<uint32_t*>(d + L.o_qi1);
@@ -177,6 +181,8 @@ int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan,
 	a.cnt = reinterpret_cast<uint32_t*>(d + L.o_cnt); a.item_off = reinterpret_cast<uint32_t*>(d + L.o_item_off);
 	a.kept = reinterpret_cast<uint32_t*>(d + L.o_kept); a.kept_pos = reinterpret_cast<uint32_t*>(d + L.o_kept_pos);
 	a.cand_item = reinterpret_cast<uint32_t*>(d + L.o_cand_item); a.cand_ev = reinterpret_cast<double*>(d + L.o_cand_ev);
+	a.fverdict = reinterpret_cast<uint8_t*>(d + L.o_fverdict); a.matched = reinterpret_cast<uint8_t*>(d + L.o_matched);
+	a.q_matched = reinterpret_cast<uint32_t*>(d + L.o_qmatched); a.q_removed = reinterpret_cast<uint32_t*>(d + L.o_qremoved);
 	a.item_base = 0; a.item_cap = (uint32_t)L.nI;
 	a.items = reinterpret_cast<dmnd_dp_target*>(d + L.o_items); a.off_item = reinterpret_cast<int64_t*>(d + L.o_off_item);
 	a.p_of_item = reinterpret_cast<int32_t*>(d + L.o_p); a.ends = reinterpret_cast<SwipeEnd*>(d + L.o_ends); a.hsps = reinterpret_cast<dmnd_hsp*>(d + L.o_hsps);
@@ -184,7 +190,7 @@ int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan,
 	a.idx = reinterpret_cast<uint32_t*>(d + L.o_idx); a.order = reinterpret_cast<uint32_t*>(d + L.o_order);
 	a.rows = reinterpret_cast<int64_t*>(d + L.o_rows); a.rows_slot = reinterpret_cast<int64_t*>(d + L.o_rows_slot); a.off_slot = reinterpret_cast<int64_t*>(d + L.o_off_slot);
 	a.pairs = reinterpret_cast<int32_t*>(d + L.o_pairs);
-	a.r2_cap = (uint32_t)L.nR; a.r2_tr_clear = (uint32_t)L.r2_tr_clear;
+	a.r2_cap = (uint32_t)L.nS; a.r2_tr_clear = (uint32_t)L.r2_tr_clear;
 	a.r2_order = reinterpret_cast<int32_t*>(d + L.o_r2_order); a.r2_p = reinterpret_cast<int32_t*>(d + L.o_r2_p);
 	a.r2_off = reinterpret_cast<int64_t*>(d + L.o_r2_off); a.r2_tr = reinterpret_cast<int64_t*>(d + L.o_r2_tr); a.r2_group = reinterpret_cast<uint32_t*>(d + L.o_r2_group);
 	a.records = reinterpret_cast<dmnd_match*>(d + L.o_records);
@@ -212,11 +218,47 @@ int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan,
 	};
 	HIP_TRY(launch_ext_begin(a, st));
 	ExtCounters ctr;
+	// the trace walk over the first n entries of the round-2 list
+	auto walk = [&](uint32_t n) -> int {
+		TracebackArgs t;
+		t.qblock = c->block[DMND_QUERY].as<int8_t>(); t.tblock = c->block[DMND_TARGET].as<int8_t>(); t.cbs = c->cbs_len > 0 ? c->cbs.as<int8_t>() : nullptr;
+		t.matrix = c->matrix.as<int8_t>(); t.matrices = nullptr;
+		t.items = a.items; t.order = a.r2_order; t.p_of_slot = a.r2_p; t.trace_off = a.r2_off; t.transcript_off = a.r2_tr;
+		t.trace = c->ext_trace.as<uint8_t>(); t.transcript = nullptr; t.ends = a.ends; t.hsps = a.hsps; t.status = &a.ctr->tb_status;
+		t.n = n; t.gap_open = c->params.gap_open; t.gap_extend = c->params.gap_extend;
+		HIP_TRY(launch_traceback(t, st));
+		return DMND_OK;
+	};
+	// the list's entries whose round-1 sweep kept no trace rows, swept again with traceback as one more iteration (copies of their items)
+	auto resweep = [&](uint32_t n_listed, double& ms) -> int {
+		HIP_TRY(launch_ext_resweep(a, n_listed, st));
+		HIP_TRY(copy_now(st, c->ext_host.p, a.ctr, sizeof(ExtCounters), hipMemcpyDeviceToHost));
+		ctr = *c->ext_host.as<ExtCounters>();
+		// (these rows are not held against the budget of round 1, only against a hard limit)
+		if ((size_t)ctr.total_rows > std::max(c->trace_arena_max * 4, (size_t)4 << 30)) return fail(DMND_E_NOMEM, "dmnd_extend: the trace rows of round 2 exceed the trace limit (4 x DMND_TRACE_ARENA_MB, at least 4 GB)");
+		DevBuf* arena = nullptr;
+		int64_t rel = 0;
+		if (int rc = arena_for((size_t)ctr.total_rows, arena, rel)) return rc;
+		HIP_TRY(hipEventRecord(c->ev0, st));
+		if (int rc = dmnd_sweep_classes(c, c, a.items + a.item_base, ctr.class_count, ctr.class_max_steps, EXT_CLASSES, reinterpret_cast<const int32_t*>(a.order), a.off_slot, a.pairs,
+			a.off_item + a.item_base, arena->as<uint8_t>(), a.ends + a.item_base)) return rc;
+		HIP_TRY(hipEventRecord(c->ev1, st));
+		HIP_TRY(launch_ext_rewalk(a, ctr.n_items, n_listed, rel, st));
+		HIP_TRY(sync_stream(st));
+		float t_ms = 0.f;
+		HIP_TRY(hipEventElapsedTime(&t_ms, c->ev0, c->ev1));
+		ms += t_ms;
+		return DMND_OK;
+	};
 	double ms_sweeps = 0, ms_sweeps2 = 0, ms_walk = 0;
-	uint64_t items_total = 0;
+	uint64_t items_total = 0, walked_filt = 0;
+	unsigned long long cells2_filt = 0;
 	const int max_chunks = ext_max_chunks();
 	for (int iter = 0;; ++iter) {
 		const bool last = iter + 1 >= max_chunks;      // (a query still ranking after this chunk goes back to the host)
+		// with filters a chunk's targets are walked before the next chunk is swept: its trace rows are dead by now, and the arenas --
+		// the kept rows' and the one of a chunk swept again -- are used again, so a call never holds more than one chunk's rows
+		if (filt) { trace_used = 0; n_more = 0; }
 		// 1. the chunk's items, launch order, trace offsets, pairs
 		HIP_TRY(launch_ext_prepare(a, st));
 		HIP_TRY(copy_now(st, c->ext_host.p, a.ctr, sizeof(ExtCounters), hipMemcpyDeviceToHost));
@@ -234,7 +276,8 @@ int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan,
 			// culling (at most -k per query) that sweeping all of them for scores only (18 VALU instructions per packed cell
 			// against 31 with trace bits) and the survivors a second time is less work: 18 + 31 f < 31 for a surviving fraction
 			// f < 0.42 (C2skew: 125 targets per query, f <= 0.2; C2, C3: f = 0.8 / 0.56, rows kept)
-			const bool few_survive = ctr.window_bound * 100 < ctr.window_targets * (unsigned long long)tuning().extend_resweep_below_pct;
+			// (with filters every target past the report cutoff is walked, not the -k survivors: the rows are kept whenever they fit)
+			const bool few_survive = !filt && ctr.window_bound * 100 < ctr.window_targets * (unsigned long long)tuning().extend_resweep_below_pct;
 			kept = keep_traces_dev() && !few_survive && trace_used + (size_t)ctr.total_rows <= trace_budget;
 			DevBuf* arena = nullptr;
 			if (kept) if (int rc = arena_for((size_t)ctr.total_rows, arena, rel)) return rc;
@@ -244,14 +287,38 @@ int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan,
 				a.off_item + a.item_base, kept ? arena->as<uint8_t>() : nullptr, a.ends + a.item_base)) return rc;
 			HIP_TRY(hipEventRecord(c->ev1, st));
 		}
-		// 3. best HSP per target, append_hits, next window; and -- in case that was the last chunk of every query -- final culling + round-2 list
-		HIP_TRY(launch_ext_append(a, ctr.n_items, kept, rel, last, st));
 		const uint32_t n_items_iter = ctr.n_items;
-		HIP_TRY(copy_now(st, c->ext_host.p, a.ctr, sizeof(ExtCounters), hipMemcpyDeviceToHost));
-		ctr = *c->ext_host.as<ExtCounters>();
-		if (n_items_iter > 0) { float ms = 0.f; HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1)); ms_sweeps += ms; }
+		if (!filt) {
+			// 3. best HSP per target, append_hits, next window; and -- in case that was the last chunk of every query -- final culling + round-2 list
+			HIP_TRY(launch_ext_append(a, ctr.n_items, kept, rel, last, st));
+			HIP_TRY(copy_now(st, c->ext_host.p, a.ctr, sizeof(ExtCounters), hipMemcpyDeviceToHost));
+			ctr = *c->ext_host.as<ExtCounters>();
+			if (n_items_iter > 0) { float ms = 0.f; HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1)); ms_sweeps += ms; }
+			a.item_base += n_items_iter;
+		}
+		else {
+			// 3. with HSP filters: the chunk's targets past the report cutoff are walked now, before any culling; then the filters and
+			// the ranking step read the walk's statistics (launch_ext_fcand .. launch_ext_fappend, extend_kernels.h)
+			HIP_TRY(launch_ext_fcand(a, ctr.n_items, kept, rel, st));
+			HIP_TRY(copy_now(st, c->ext_host.p, a.ctr, sizeof(ExtCounters), hipMemcpyDeviceToHost));
+			ctr = *c->ext_host.as<ExtCounters>();
+			if (n_items_iter > 0) { float ms = 0.f; HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1)); ms_sweeps += ms; }
+			a.item_base += n_items_iter;
+			const uint32_t n_listed = ctr.n_kept, list_need = ctr.list_need;
+			if (n_listed > L.nS) return fail(DMND_E_CAP, "dmnd_extend: more targets to walk than groups");
+			cells2_filt += ctr.cells2; walked_filt += n_listed;
+			if (ctr.n_resweep > 0) {
+				if ((size_t)a.item_base + ctr.n_resweep > L.nI) return fail(DMND_E_CAP, "dmnd_extend: no room for the items swept again");
+				if (int rc = resweep(n_listed, ms_sweeps2)) return rc;
+				a.item_base += ctr.n_items;
+			}
+			if (n_listed > 0) if (int rc = walk(n_listed)) return rc;
+			HIP_TRY(launch_ext_fappend(a, n_listed, list_need, last, st));
+			HIP_TRY(copy_now(st, c->ext_host.p, a.ctr, sizeof(ExtCounters), hipMemcpyDeviceToHost));
+			ctr = *c->ext_host.as<ExtCounters>();
+			if (ctr.tb_status != 0) return fail(ctr.tb_status, ctr.tb_status == DMND_E_TRACEBACK ? "Traceback error." : "transcript slot too small");
+		}
 		items_total += n_items_iter;
-		a.item_base += n_items_iter;
 		if (tr.on && (iter > 0 || ctr.n_active > 0)) std::fprintf(stderr, "dmnd_extend (device half): chunk %d: %u DpTargets%s, %.1f MB of trace rows kept so far, %u queries go on\n", iter, n_items_iter, kept ? "" : " (scores only)", (double)trace_used / 1048576.0, ctr.n_active);
 		if (ctr.n_active == 0) break;
 		if (last) return fail(DMND_E_CAP, "dmnd_extend: a query went on ranking past the last allowed chunk");
@@ -259,39 +326,23 @@ int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan,
 	tr.lap("sweeps, culling");
 	// 4. round 2: the survivors whose trace rows were not kept are swept again with traceback (copies of their items, one more
 	// iteration), then one walk over all survivors' traces, then the records
+	if (filt) {
+		// every walk is done: the first -k of each query's matches and their record slots
+		HIP_TRY(launch_ext_ffinal(a, st));
+		HIP_TRY(copy_now(st, c->ext_host.p, a.ctr, sizeof(ExtCounters), hipMemcpyDeviceToHost));
+		ctr = *c->ext_host.as<ExtCounters>();
+		ctr.n_resweep = 0;
+	}
 	if (ctr.n_kept > nR) return fail(DMND_E_CAP, "dmnd_extend: more device records than -k allows");
 	const uint32_t n_kept = ctr.n_kept;
 	if (ctr.n_resweep > 0) {
-		HIP_TRY(launch_ext_resweep(a, n_kept, st));
-		HIP_TRY(copy_now(st, c->ext_host.p, a.ctr, sizeof(ExtCounters), hipMemcpyDeviceToHost));
-		ctr = *c->ext_host.as<ExtCounters>();
-		// (at most -k survivors per query: their rows are not held against the budget of round 1, only against a hard limit)
-		if ((size_t)ctr.total_rows > std::max(c->trace_arena_max * 4, (size_t)4 << 30)) return fail(DMND_E_NOMEM, "dmnd_extend: the trace rows of round 2 exceed the trace limit (4 x DMND_TRACE_ARENA_MB, at least 4 GB)");
-		DevBuf* arena = nullptr;
-		int64_t rel = 0;
-		if (int rc = arena_for((size_t)ctr.total_rows, arena, rel)) return rc;
-		HIP_TRY(hipEventRecord(c->ev0, st));
-		if (int rc = dmnd_sweep_classes(c, c, a.items + a.item_base, ctr.class_count, ctr.class_max_steps, EXT_CLASSES, reinterpret_cast<const int32_t*>(a.order), a.off_slot, a.pairs,
-			a.off_item + a.item_base, arena->as<uint8_t>(), a.ends + a.item_base)) return rc;
-		HIP_TRY(hipEventRecord(c->ev1, st));
-		HIP_TRY(launch_ext_rewalk(a, ctr.n_items, n_kept, rel, st));
-		HIP_TRY(sync_stream(st));
-		float ms = 0.f;
-		HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-		ms_sweeps2 += ms;
+		// (at most -k survivors per query)
+		if (int rc = resweep(n_kept, ms_sweeps2)) return rc;
 		tr.lap("round-2 sweeps");
 	}
 	ctr.n_kept = n_kept;
 	HIP_TRY(hipEventRecord(c->ev1, st));
-	if (ctr.n_kept > 0) {
-		TracebackArgs t;
-		t.qblock = c->block[DMND_QUERY].as<int8_t>(); t.tblock = c->block[DMND_TARGET].as<int8_t>(); t.cbs = c->cbs_len > 0 ? c->cbs.as<int8_t>() : nullptr;
-		t.matrix = c->matrix.as<int8_t>(); t.matrices = nullptr;
-		t.items = a.items; t.order = a.r2_order; t.p_of_slot = a.r2_p; t.trace_off = a.r2_off; t.transcript_off = a.r2_tr;
-		t.trace = c->ext_trace.as<uint8_t>(); t.transcript = nullptr; t.ends = a.ends; t.hsps = a.hsps; t.status = &a.ctr->tb_status;
-		t.n = ctr.n_kept; t.gap_open = c->params.gap_open; t.gap_extend = c->params.gap_extend;
-		HIP_TRY(launch_traceback(t, st));
-	}
+	if (ctr.n_kept > 0 && !filt) if (int rc = walk(ctr.n_kept)) return rc;
 	HIP_TRY(hipEventRecord(c->ev2, st));
 	HIP_TRY(launch_ext_records(a, ctr.n_kept, st));
 	const size_t h_ctr = 0, h_qstate = (sizeof(ExtCounters) + 63) & ~(size_t)63, h_records = (h_qstate + nQ + 63) & ~(size_t)63,
@@ -356,6 +407,11 @@ int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan,
 	c->ext_dev_stats[4] = (double)ctr.diag_steps; c->ext_dev_stats[5] = (double)ctr.lane_steps;
 	c->ext_dev_stats[6] = (double)ctr.cells2; c->ext_dev_stats[7] = (double)ctr.cells_again; c->ext_dev_stats[8] = ms_sweeps2;
 	c->ext_dev_stats[1] += (double)ctr.n_capped; c->ext_dev_stats[9] = (double)ctr.n_capped;
+	if (filt) {
+		c->ext_stats[1] += (double)walked_filt - (double)ctr.n_kept; c->ext_stats[3] += (double)cells2_filt - (double)ctr.cells2;      // (every walked target is a round-2 target)
+		c->ext_dev_stats[1] += (double)ctr.n_threshold; c->ext_dev_stats[6] = (double)cells2_filt;
+		c->ext_filter_stats[0] = (double)ctr.n_filtered; c->ext_filter_stats[1] = (double)ctr.n_threshold;
+	}
 	if (tr.on) std::fprintf(stderr, "dmnd_extend (device half): %zu queries, %u handed back to the host (%u ambiguous, %u saturated, %u at the chunk cap of %d), %zu records; %u groups, %u bands, %zu bytes of work arrays\n",
 		n_eligible, ctr.n_ambiguous + ctr.n_saturated + ctr.n_capped, ctr.n_ambiguous, ctr.n_saturated, ctr.n_capped, max_chunks, n, plan.n_groups, plan.n_bands, L.bytes);
 	if (int rc = guard.check("dmnd_extend (device half)")) return rc;

@@ -105,8 +105,9 @@ struct HostCfg {
 	double max_evalue = 0.001;
 	double min_bit_score = 0.0;          // config.min_bit_score (--min-score): replaces the e-value cutoff (ScoreMatrix::report_cutoff)
 	double min_id = 0.0, query_cover = 0.0, subject_cover = 0.0;      // --id, --query-cover, --subject-cover (filter_hsp, culling.cpp:147-170)
+	double approx_id = 0.0;              // --approx-id (config.approx_min_id; filter_core.h)
 	const int32_t* source_lens = nullptr; // translated queries: DNA read length per query
-	bool have_filters() const { return min_id > 0 || query_cover > 0 || subject_cover > 0; }
+	bool have_filters() const { return min_id > 0 || approx_id > 0 || query_cover > 0 || subject_cover > 0; }      // extend.cpp:94-96
 	bool reported(int score, double evalue) const { return min_bit_score != 0.0 ? evaluer->bitscore(score) >= min_bit_score : evalue <= max_evalue; }
 };
 
@@ -164,7 +165,8 @@ DeviceCfg device_cfg(const HostCfg& h)      // what the device half reads of the
 	DeviceCfg d;
 	d.gap_open = h.S.gap_open; d.gap_extend = h.S.gap_extend; d.band_mode_fast = h.band_mode_fast; d.max_target_seqs = h.max_target_seqs;
 	d.ranking_chunk = ranking_chunk_size(h.ref_letters, h.max_target_seqs, h.ranking_block_letters, false);
-	d.max_swipe_dp = h.max_swipe_dp; d.use_cbs = h.use_cbs; d.max_evalue = h.max_evalue;
+	d.max_swipe_dp = h.max_swipe_dp; d.use_cbs = h.use_cbs; d.max_evalue = h.max_evalue; d.min_bit_score = h.min_bit_score;
+	d.filters.min_id = h.min_id; d.filters.approx_id = h.approx_id; d.filters.query_cover = h.query_cover; d.filters.subject_cover = h.subject_cover;
 	return d;
 }
 
@@ -630,6 +632,8 @@ static int extend_range(const dmnd_ctx* c, dmnd_ctx* w, const HostCfg& h, const 
 	const int K = h.max_target_seqs;
 	const CullCfg cc{ K, h.top, &c->evaluer };
 	const bool first_round_culling = !h.have_filters() || h.top >= 0.0;      // extend.cpp:272
+	FilterCfg fcfg;
+	fcfg.min_id = h.min_id; fcfg.approx_id = h.approx_id; fcfg.query_cover = h.query_cover; fcfg.subject_cover = h.subject_cover;
 	const bool multi = h.max_hsps != 1;                                       // several HSPs per target: every reported band goes through round 2
 	for (int i = 0; i < 12; ++i) if (i != 4 || w != c) w->ext_stats[i] = 0;      // [4] (bias + upload) of the caller's prelude is kept
 	for (double& x : w->host_ms) x = 0;
@@ -985,9 +989,8 @@ static int extend_range(const dmnd_ctx* c, dmnd_ctx* w, const HostCfg& h, const 
 					const int tlen = (int)(tl[m.target + 1] - tl[m.target] - 1);
 					const uint32_t qc = q * C + (uint32_t)m.frame;
 					const int qlen = (int)(ql[qc + 1] - ql[qc] - 1);
-					if (h.have_filters() && ((double)hsp.identities * 100.0 / (double)hsp.length < h.min_id
-						|| (C == 1 ? (double)(hsp.q_end - hsp.q_begin) * 100 / qlen : (double)(3 * (hsp.q_end - hsp.q_begin)) * 100 / (h.source_lens ? h.source_lens[q] : 1)) < h.query_cover
-						|| (double)(hsp.s_end - hsp.s_begin) * 100 / tlen < h.subject_cover)) return true;
+					if (h.have_filters() && filter_fails(fcfg, filter_values(hsp.score, hsp.identities, hsp.length, hsp.q_begin, hsp.q_end, hsp.s_begin, hsp.s_end,
+						C == 1 ? hsp.q_end - hsp.q_begin : 3 * (hsp.q_end - hsp.q_begin), C == 1 ? qlen : (h.source_lens ? h.source_lens[q] : 1), tlen))) return true;
 					// --no-self-hits: same letters (Sequence::operator==, the query's first context) and same title
 					if (c->same_title && C == 1 && qlen == tlen) {
 						const int8_t* a = qdata + ql[qc];
@@ -1246,7 +1249,7 @@ int extend_cfg(dmnd_ctx* c, HostCfg& h, CbsModel& cbs_model)
 	h.top = c->top_percent;
 	h.evaluer = &c->evaluer;
 	h.max_evalue = c->params.max_evalue;
-	h.min_bit_score = c->min_bit_score; h.min_id = c->min_id; h.query_cover = c->query_cover; h.subject_cover = c->subject_cover;
+	h.min_bit_score = c->min_bit_score; h.min_id = c->min_id; h.query_cover = c->query_cover; h.subject_cover = c->subject_cover; h.approx_id = c->approx_id;
 	if (h.query_cover > 0 && c->query_contexts != 1 && c->source_lens.size() != (ql.size() - 1) / (size_t)c->query_contexts)
 		return fail(DMND_E_ARG, "dmnd_extend: the query cover of translated queries needs the read lengths (dmnd_set_query_source_lengths)");
 	if (h.max_hsps != 1 && c->query_contexts != 1 && c->source_lens.size() != (ql.size() - 1) / (size_t)c->query_contexts)
@@ -1446,17 +1449,19 @@ extern "C" int dmnd_extend(dmnd_ctx* c, const int8_t* qdata, const int8_t* tdata
 	if (xd) xd = c->xd_host.as<XdropSeg>();              // (NULL while no group was left to the host: nothing reads it then)
 	const DevPlan* dp = planned ? &plan : nullptr;
 	// The queries whose targets fit one ranking chunk are extended in HBM from here on (extend_kernels.hip): the default search of a
-	// protein query block -- one HSP per target, -k culling by e-value, Hauser bias or none, no --id / cover filters, no transcripts
+	// protein query block -- one HSP per target, -k culling by e-value, Hauser bias or none, with or without the HSP filters, no transcripts
 	// (the caller formats from the statistics). The others, and every query of any other mode, take the host path below.
-	// DMND_EXTEND_DEVICE=0: all queries on the host path, as up to round 5.
-	static const bool ext_gpu = [] { const char* e = std::getenv("DMND_EXTEND_DEVICE"); return !e || e[0] != '0'; }();
+	// DMND_EXTEND_DEVICE=0: all queries on the host path, as up to round 5. Read per call, like the hooks of extend_device.hip
+	// (DESIGN.md 9): a test compares the two paths in one process.
+	const bool ext_gpu = [] { const char* e = std::getenv("DMND_EXTEND_DEVICE"); return !e || e[0] != '0'; }();
 	c->ext_records_dev = nullptr; c->ext_records_n = -1;
 	std::vector<dmnd_match> dev_records;
 	std::vector<Range> qr_host;
 	std::vector<uint32_t> pq_host;
 	bool on_device = false;
 	for (double& x : c->ext_dev_stats) x = 0;
-	if (ext_gpu && planned && h.max_hsps == 1 && !h.have_filters() && h.top < 0.0 && h.min_bit_score == 0.0 && !cbs_matrix_adjust(h.cbs_mode) && !h.ext_full && !transcript
+	c->ext_filter_stats[0] = c->ext_filter_stats[1] = 0;
+	if (ext_gpu && planned && h.max_hsps == 1 && h.top < 0.0 && !cbs_matrix_adjust(h.cbs_mode) && !h.ext_full && !transcript
 		&& h.global_ranking == 0 && !c->same_title && h.max_target_seqs > 0) {
 		std::vector<uint8_t> qstate;
 		double kept[12];
@@ -1792,6 +1797,13 @@ extern "C" int dmnd_set_filters(dmnd_ctx* c, double min_id, double query_cover, 
 	return DMND_OK;
 }
 
+extern "C" int dmnd_set_approx_id(dmnd_ctx* c, double approx_min_id)
+{
+	if (!c || !(approx_min_id >= 0)) return fail(DMND_E_ARG, "dmnd_set_approx_id: bad argument");
+	c->approx_id = approx_min_id;
+	return DMND_OK;
+}
+
 extern "C" int dmnd_set_query_source_lengths(dmnd_ctx* c, const int32_t* lengths, int64_t n_queries)
 {
 	if (!c || n_queries < 0 || (n_queries > 0 && !lengths)) return fail(DMND_E_ARG, "dmnd_set_query_source_lengths: bad argument");
@@ -1848,6 +1860,13 @@ extern "C" int dmnd_extend_records_device(const dmnd_ctx* c, const dmnd_match** 
 	if (!c || !records_dev || !n) return fail(DMND_E_ARG, "dmnd_extend_records_device: NULL argument");
 	*records_dev = c->ext_records_n >= 0 ? c->ext_records_dev : nullptr;
 	*n = c->ext_records_n;
+	return DMND_OK;
+}
+
+extern "C" int dmnd_extend_filter_stats(const dmnd_ctx* c, double out[2])
+{
+	if (!c || !out) return fail(DMND_E_ARG, "dmnd_extend_filter_stats: NULL argument");
+	out[0] = c->ext_filter_stats[0]; out[1] = c->ext_filter_stats[1];
 	return DMND_OK;
 }
 

@@ -19,6 +19,7 @@
 #include <stdint.h>
 #include "../../include/diamond_hip.h"
 #include "extend_core.h"
+#include "filter_core.h"
 #include "plan_kernels.h"
 #include "swipe_kernels.h"
 
@@ -42,12 +43,15 @@ struct ExtArgs {
 	int k;                         // max_target_seqs
 	int64_t max_swipe_dp;
 	ExtEvalue ev;
+	double min_bit_score;          // --min-score: != 0 replaces the e-value cutoff (ScoreMatrix::report_cutoff)
+	FilterCfg filt; int filt_on;   // the HSP filters (filter_core.h); filt_on: the call runs the filtered ranking loop (the f-kernels)
 	// per query
 	uint8_t* qstate;               // EXT_Q_*
 	uint8_t* q_active;             // still ranking: its window [q_i0, q_i1) of the order below is the next chunk
 	uint32_t* q_i0; uint32_t* q_i1;
 	int32_t* q_tail; int32_t* q_prev;        // tail_score / previous_tail_score of the ranking loop
 	uint32_t* q_swept;             // targets of its current window that are swept (0: none, or not active)
+	uint32_t* q_matched; uint32_t* q_removed;      // filt_on: matches of the rounds so far (Extension::extend's `matches`), records a filter removed
 	// per group
 	uint64_t* okeys; uint64_t* okeys_sorted; uint32_t* oidx;      // ranking order: sort keys (query, 0xffff - score), group numbers
 	uint32_t* gorder;              // groups of a query in ranking order (TargetScore::operator<: score descending, then load order)
@@ -57,6 +61,8 @@ struct ExtArgs {
 	uint32_t* kept; uint32_t* kept_pos;      // (+ 1) survives the final culling / its record slot
 	uint32_t* cand_item;           // the item of its best HSP
 	double* cand_ev;
+	uint8_t* fverdict;             // filt_on: the filters' verdict on the target's best HSP (EXT_F_*)
+	uint8_t* matched;              // filt_on: the target is one of the query's matches of an earlier round
 	// per item: all iterations' items one after the other (a group is swept once, so n_bands bounds them)
 	uint32_t item_base;            // first item of the current iteration
 	uint32_t item_cap;             // room in the per-item arrays: n_bands + one copy of every survivor (round 2 sweeps those again whose traces were not kept)
@@ -79,6 +85,7 @@ struct ExtArgs {
 	void** scan_tmp; size_t* scan_tmp_bytes;
 };
 
+enum { EXT_F_PASS = 0, EXT_F_FAIL = 1, EXT_F_THRESHOLD = 2 };
 enum { EXT_Q_HOST = 0, EXT_Q_DEVICE = 1, EXT_Q_AMBIGUOUS = 2, EXT_Q_CAPPED = 3 };      // CAPPED: still ranking after the last allowed chunk
 
 // once per call: which queries run here, their ranking order, the state of their ranking loops
@@ -95,6 +102,16 @@ hipError_t launch_ext_append(const ExtArgs& a, uint32_t n_items, bool kept, int6
 // offsets, pairs); then, behind its traceback-mode sweeps, launch_ext_rewalk points the round-2 list at the copies
 hipError_t launch_ext_resweep(const ExtArgs& a, uint32_t n_kept, hipStream_t st);
 hipError_t launch_ext_rewalk(const ExtArgs& a, uint32_t n_items, uint32_t n_kept, int64_t rel, hipStream_t st);
+// With HSP filters (a.filt_on; src/align/extend.cpp:226-344 with have_filters, src/align/gapped_final.cpp:105-152) a chunk takes
+// three steps behind its sweeps instead of launch_ext_append: launch_ext_fcand lists the chunk's targets past the report cutoff
+// in the round-2 arrays (ctr->n_kept of them, ctr->n_resweep without kept trace rows: launch_ext_resweep / _rewalk as in round 2);
+// the host has their traces walked; launch_ext_fappend then filters them (ext_filter_kernel, one lane per listed target) and runs
+// the query's ranking step: append_hits without culling and -- where the chunk loop ends -- round 2's stepping over the sorted
+// aligned targets, in which a target that fails a filter takes no place, and the outer loop's decision to rank on.
+// launch_ext_ffinal, once no query is left ranking: the first -k of every query's matches, record slots.
+hipError_t launch_ext_fcand(const ExtArgs& a, uint32_t n_items, bool kept, int64_t rel, hipStream_t st);
+hipError_t launch_ext_fappend(const ExtArgs& a, uint32_t n_listed, uint32_t list_need, bool last, hipStream_t st);      // list_need: ctr->list_need as launch_ext_fcand left it
+hipError_t launch_ext_ffinal(const ExtArgs& a, hipStream_t st);
 // after the walk: the records
 hipError_t launch_ext_records(const ExtArgs& a, uint32_t n_kept, hipStream_t st);
 

@@ -71,6 +71,19 @@ __device__ inline int64_t ext_cells(const dmnd_dp_target& d)       // DpTarget::
 // bit score of a raw score (Evaluer::bitscore, evalue.h): plain double arithmetic, no library function -- the host's value bit for bit
 __device__ inline double ext_bitscore(const ExtEvalue& p, int raw_score) { return (p.lambda * (double)raw_score - p.ln_k) / 0.69314718055994530941723212145818; }
 
+// the report cutoff (ScoreMatrix::report_cutoff): the e-value against --evalue, or -- --min-score -- the bit score against that; amb
+// is set where the host's own value could decide the other way
+__device__ inline bool ext_reported(const ExtArgs& a, int score, double ev, bool& amb)
+{
+	if (a.min_bit_score != 0.0) {
+		const double bits = ext_bitscore(a.ev, score);
+		if (ext_near(bits, a.min_bit_score)) amb = true;
+		return bits >= a.min_bit_score;
+	}
+	if (ext_near(ev, a.ev.max_evalue)) amb = true;
+	return ev <= a.ev.max_evalue;
+}
+
 __global__ __launch_bounds__(64) void ext_mark_kernel(ExtArgs a)
 {
 	const uint32_t q = blockIdx.x, lane = threadIdx.x;
@@ -100,12 +113,14 @@ __global__ __launch_bounds__(64) void ext_mark_kernel(ExtArgs a)
 		a.okeys[g] = ((uint64_t)q << 16) | (uint64_t)(0xffffu - (uint32_t)a.groups[g].score);
 		a.oidx[g] = g;
 		a.aligned[g] = 0; a.g_cnt[g] = 0; a.g_first[g] = 0;
+		if (a.filt_on) { a.fverdict[g] = EXT_F_PASS; a.matched[g] = 0; }
 	}
 	if (lane == 0) {
 		a.qstate[q] = ok ? EXT_Q_DEVICE : EXT_Q_HOST;
 		a.q_active[q] = ok ? 1 : 0;
 		a.q_i0[q] = 0; a.q_i1[q] = ng < a.chunk_size ? ng : a.chunk_size;
 		a.q_tail[q] = 0; a.q_prev[q] = 0;
+		if (a.filt_on) { a.q_matched[q] = 0; a.q_removed[q] = 0; }
 	}
 }
 
@@ -133,7 +148,7 @@ __global__ __launch_bounds__(64) void ext_window_kernel(ExtArgs a)
 	if (q == 0 && lane == 0) {
 		a.cnt[a.n_groups] = 0; a.kept[a.n_groups] = 0;
 		a.ctr->n_items = 0; a.ctr->n_active = 0; a.ctr->n_resweep = 0; a.ctr->total_rows = 0; a.ctr->cells2 = 0;
-		a.ctr->window_targets = 0; a.ctr->window_bound = 0;
+		a.ctr->window_targets = 0; a.ctr->window_bound = 0; a.ctr->list_need = 0;
 	}
 }
 
@@ -313,8 +328,7 @@ __global__ __launch_bounds__(64) void ext_append_kernel(ExtArgs a, int last)
 			if (e.pad[0]) sat = true;
 			if (e.score <= 0) continue;
 			const double ev = ext_evalue(a.ev, e.score, qlen, tlen);
-			if (ext_near(ev, a.ev.max_evalue)) amb = true;
-			if (!(ev <= a.ev.max_evalue)) continue;
+			if (!ext_reported(a, e.score, ev, amb)) continue;
 			if (!have || e.score > best || (e.score == best && a.items[first + k].d_begin < a.items[bi].d_begin)) { have = true; best = e.score; bi = first + k; bev = ev; }
 		}
 		a.cand_item[g] = bi;
@@ -515,6 +529,242 @@ __global__ __launch_bounds__(64) void ext_records_kernel(ExtArgs a)
 	}
 }
 
+// ---- the ranking loop with HSP filters (a.filt_on) ----
+
+// the query goes back to the host: nothing of it stays here
+__device__ inline void ext_hand_back(const ExtArgs& a, uint32_t q, uint32_t g0, uint32_t ng, uint32_t lane, uint8_t state)
+{
+	for (uint32_t gi = lane; gi < ng; gi += 64) { a.aligned[g0 + gi] = 0; a.matched[g0 + gi] = 0; a.kept[g0 + gi] = 0; }
+	if (lane == 0) { a.qstate[q] = state; a.q_active[q] = 0; }
+}
+
+// Behind a chunk's sweeps: best HSP per target past the report cutoff (the first loop of ext_append_kernel), flagged in `kept` --
+// the list the trace walk runs over BEFORE any culling, so that the filters can read identities, length and coordinates of every
+// target that a place among the -k could go to
+__global__ __launch_bounds__(64) void ext_fcand_kernel(ExtArgs a)
+{
+	const uint32_t q = blockIdx.x, lane = threadIdx.x;
+	if (!a.q_active[q]) return;
+	const uint32_t g0 = a.queries[q].group_begin, g1 = a.queries[q + 1].group_begin, ng = g1 - g0;
+	const uint32_t i0 = a.q_i0[q], i1 = a.q_i1[q];
+	const uint32_t query = a.queries[q].query;
+	const int qlen = (int)(a.qlimits[query + 1] - a.qlimits[query] - 1);
+	bool amb = false, sat = false;
+	for (uint32_t w = i0 + lane; w < i1; w += 64) {
+		const uint32_t g = a.gorder[g0 + w], n = a.g_cnt[g], first = a.g_first[g];
+		const uint32_t target = a.groups[g].target;
+		const int tlen = (int)(a.tlimits[target + 1] - a.tlimits[target] - 1);
+		bool have = false;
+		int best = 0; uint32_t bi = 0; double bev = 0;
+		for (uint32_t k = 0; k < n; ++k) {
+			const SwipeEnd e = a.ends[first + k];
+			if (e.pad[0]) sat = true;
+			if (e.score <= 0) continue;
+			const double ev = ext_evalue(a.ev, e.score, qlen, tlen);
+			if (!ext_reported(a, e.score, ev, amb)) continue;
+			if (!have || e.score > best || (e.score == best && a.items[first + k].d_begin < a.items[bi].d_begin)) { have = true; best = e.score; bi = first + k; bev = ev; }
+		}
+		a.cand_item[g] = bi;
+		a.cand_ev[g] = bev;
+		a.kept[g] = have ? 1u : 0u;
+	}
+	const bool any_amb = __ballot(amb) != 0, any_sat = __ballot(sat) != 0;
+	if (any_amb || any_sat) {
+		ext_hand_back(a, q, g0, ng, lane, EXT_Q_AMBIGUOUS);
+		if (lane == 0) { if (any_amb) atomicAdd(&a.ctr->n_ambiguous, 1u); if (any_sat) atomicAdd(&a.ctr->n_saturated, 1u); }
+	}
+	else if (lane == 0) atomicMax(&a.ctr->list_need, i1 < ng ? i1 : ng);      // (aligned targets + this chunk's <= targets swept so far)
+}
+
+// The HSP filters (filter_hsp, culling.cpp:147-170), one lane per target of the walked list: identity, approximate identity and the
+// two covers of its HSP from what traceback_kernel left, with the arithmetic of the host path (filter_core.h) -- the verdict the
+// ranking step below reads. A value on a threshold (within the tolerance of ext_near) is not decided here.
+// Bound: n <= ctr->n_kept <= n_groups, the capacity of the round-2 arrays under filters (ExtLayout::nS); one byte per group written.
+__global__ __launch_bounds__(256) void ext_filter_kernel(ExtArgs a, uint32_t n)
+{
+	const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+	if (k >= n) return;
+	const uint32_t g = a.r2_group[k];
+	const PlanGroup grp = a.groups[g];
+	const uint32_t query = a.hits[grp.hit_begin].query;
+	const int qlen = (int)(a.qlimits[query + 1] - a.qlimits[query] - 1), tlen = (int)(a.tlimits[grp.target + 1] - a.tlimits[grp.target] - 1);
+	const dmnd_hsp h = a.hsps[a.cand_item[g]];
+	const FilterValues v = filter_values(h.score, h.identities, h.length, h.q_begin, h.q_end, h.s_begin, h.s_end, h.q_end - h.q_begin, qlen, tlen);
+	a.fverdict[g] = filter_on_threshold(a.filt, v) ? EXT_F_THRESHOLD : filter_fails(a.filt, v) ? EXT_F_FAIL : EXT_F_PASS;
+}
+
+// ranks of the LDS list's entries [0, n) among themselves in Target::comp_evalue order; returns whether a pair's order is ambiguous
+__device__ inline bool rank_list(const ExtArgs& a, const SelSlot* list, uint32_t n, uint16_t* rank_of, uint32_t lane)
+{
+	bool amb = false;
+	for (uint32_t x = lane; x < n; x += 64) {
+		const SelSlot me = list[x];
+		uint32_t rank = 0;
+		for (uint32_t y = 0; y < n; ++y) {
+			if (y == x) continue;
+			if (sel_ambiguous(a.ev, list[y], me)) amb = true;
+			rank += sel_less(list[y], me) ? 1u : 0u;
+		}
+		rank_of[x] = (uint16_t)rank;
+	}
+	return amb;
+}
+
+// One ranking step of a query with HSP filters, behind the walk and the filter kernel (one wavefront per query):
+//   append_hits without culling (culling.cpp:115-145 with with_culling = false, extend.cpp:272): the chunk's targets always join the
+//     aligned targets; new_hits = fewer than k were aligned, or the chunk's best e-value reaches the k-th best's
+//   the next window and the tail rule, as ext_append_kernel
+//   where the chunk loop ends: round 2 (gapped_final.cpp:105-152) over the aligned targets in e-value order, a step of
+//     ceil16(max(k - passed, 16)) targets at a time until k matches (with those of earlier rounds) passed the filters or the list
+//     ends -- a target that fails a filter takes no place; the first k that passed become matches
+//   extend.cpp:336: fewer than k matches, targets left and the last chunk had hits -> the chunk loop starts again, no target aligned
+// LDS (dynamic): cap slots -- the most any active query can need, at most EXT_FILTER_LIST --, their ranks, verdicts by rank,
+// selection by rank: 28 bytes per slot. A query with more than EXT_FILTER_LIST aligned targets goes
+// back to the host (counted with the capped ones).
+__global__ __launch_bounds__(64) void ext_fappend_kernel(ExtArgs a, int last, uint32_t cap)
+{
+	extern __shared__ SelSlot lds[];
+	SelSlot* list = lds;
+	uint16_t* rank_of = reinterpret_cast<uint16_t*>(lds + cap);
+	uint8_t* verdict = reinterpret_cast<uint8_t*>(rank_of + cap);
+	uint8_t* sel = verdict + cap;
+	__shared__ uint32_t n_sh, res_sh[4];
+	__shared__ SelSlot kth_slot;
+	const uint32_t q = blockIdx.x, lane = threadIdx.x;
+	if (!a.q_active[q]) return;
+	const uint32_t K = (uint32_t)a.k;
+	const uint32_t g0 = a.queries[q].group_begin, g1 = a.queries[q + 1].group_begin, ng = g1 - g0;
+	const uint32_t i1 = a.q_i1[q];
+	const uint32_t na = gather_flagged(a, a.aligned, nullptr, g0, ng, list, cap, &n_sh, lane);
+	uint32_t nv = 0;
+	if (na <= cap) nv = gather_flagged(a, nullptr, a.kept, g0, ng, list + na, cap - na, &n_sh, lane);
+	if (na > cap || nv > cap - na) {
+		ext_hand_back(a, q, g0, ng, lane, EXT_Q_CAPPED);
+		if (lane == 0) atomicAdd(&a.ctr->n_capped, 1u);
+		return;
+	}
+	const uint32_t n = na + nv;
+	bool amb = false;
+	bool new_hits = nv > 0 && na < K;
+	if (nv > 0 && !new_hits) {
+		amb |= rank_list(a, list, na, rank_of, lane);
+		__syncthreads();
+		for (uint32_t x = lane; x < na; x += 64) if (rank_of[x] == K - 1) kth_slot = list[x];
+		__syncthreads();
+		const SelSlot ks = kth_slot;
+		bool reach = false;
+		for (uint32_t x = na + lane; x < n; x += 64) {
+			if (sel_ambiguous(a.ev, list[x], ks)) amb = true;
+			reach |= list[x].ev <= ks.ev;
+		}
+		new_hits = __ballot(reach) != 0;
+	}
+	// the next window and whether the chunk loop goes on (extend.cpp:325-336)
+	const uint32_t n0 = i1, n1 = i1 + (a.chunk_size < ng - i1 ? a.chunk_size : ng - i1);
+	const int prev = a.q_tail[q];
+	const int next_tail = (int)a.groups[a.gorder[g0 + n1 - 1]].score;
+	const bool terminate = !new_hits && (prev == 0 || (double)next_tail / (double)prev <= 0.95 || ext_bitscore(a.ev, next_tail) < 25.0);
+	bool go_on = n0 < ng && !terminate;
+	uint32_t matched_now = a.q_matched[q];
+	bool threshold = false;
+	const bool round2 = !go_on;
+	if (round2) {
+		// round 2: the aligned targets in e-value order, a step at a time
+		__syncthreads();
+		amb |= rank_list(a, list, n, rank_of, lane);
+		__syncthreads();
+		for (uint32_t x = lane; x < n; x += 64) verdict[rank_of[x]] = a.fverdict[list[x].g];
+		__syncthreads();
+		if (lane == 0) {
+			uint32_t pos = 0, passed = 0, removed = 0, thr = 0;
+			for (;;) {
+				const uint32_t left = n - pos, want = K - passed > 16 ? K - passed : 16;
+				const uint32_t step = (want + 15) / 16 * 16 < left ? (want + 15) / 16 * 16 : left;
+				uint32_t got = 0;
+				for (uint32_t r = pos; r < pos + step; ++r) {
+					const uint8_t v = verdict[r];
+					sel[r] = v == EXT_F_PASS && passed + got < K ? 1 : 0;
+					got += v == EXT_F_PASS ? 1u : 0u; removed += v == EXT_F_FAIL ? 1u : 0u; thr += v == EXT_F_THRESHOLD ? 1u : 0u;
+				}
+				passed = passed + got < K ? passed + got : K;      // culling(matches): the first k of the round stay
+				pos += step;
+				if (!(pos < n && passed + matched_now < K)) break;
+			}
+			for (uint32_t r = pos; r < n; ++r) sel[r] = 0;
+			res_sh[0] = passed; res_sh[1] = removed; res_sh[2] = thr;
+		}
+		__syncthreads();
+		threshold = res_sh[2] != 0;
+	}
+	const bool any_amb = __ballot(amb) != 0;
+	if (any_amb || threshold) {
+		ext_hand_back(a, q, g0, ng, lane, EXT_Q_AMBIGUOUS);
+		if (lane == 0) { if (any_amb) atomicAdd(&a.ctr->n_ambiguous, 1u); else atomicAdd(&a.ctr->n_threshold, 1u); }
+		return;
+	}
+	if (round2) {
+		for (uint32_t x = lane; x < n; x += 64) {
+			const uint32_t g = list[x].g;
+			a.aligned[g] = 0;
+			if (sel[rank_of[x]]) a.matched[g] = 1;
+		}
+		matched_now += res_sh[0];
+		// extend.cpp:336: the chunk loop starts again
+		go_on = matched_now < K && n0 < ng && nv > 0;
+	}
+	else for (uint32_t x = na + lane; x < n; x += 64) a.aligned[list[x].g] = 1;
+	if (go_on && last) {
+		ext_hand_back(a, q, g0, ng, lane, EXT_Q_CAPPED);
+		if (lane == 0) atomicAdd(&a.ctr->n_capped, 1u);
+		return;
+	}
+	if (lane == 0) {
+		a.q_prev[q] = prev;
+		if (new_hits) a.q_tail[q] = next_tail;
+		a.q_i0[q] = n0; a.q_i1[q] = n1;
+		a.q_matched[q] = matched_now;
+		if (round2) a.q_removed[q] += res_sh[1];
+		a.q_active[q] = go_on ? 1 : 0;
+		if (go_on) atomicAdd(&a.ctr->n_active, 1u);
+	}
+}
+
+// culling(matches) once every round is over (extend.cpp:341): the first k of the query's matches by (e-value, score, target)
+__global__ __launch_bounds__(64) void ext_ffinal_kernel(ExtArgs a)
+{
+	extern __shared__ SelSlot list[];                      // 2 k slots
+	__shared__ uint32_t n_sh;
+	const uint32_t cap = 2 * (uint32_t)a.k;
+	const uint32_t q = blockIdx.x, lane = threadIdx.x;
+	const uint32_t g0 = a.queries[q].group_begin, g1 = a.queries[q + 1].group_begin, ng = g1 - g0;
+	for (uint32_t gi = lane; gi < ng; gi += 64) a.kept[g0 + gi] = 0;
+	if (q == 0 && lane == 0) { a.kept[a.n_groups] = 0; a.ctr->n_resweep = 0; }
+	if (a.qstate[q] != EXT_Q_DEVICE) return;
+	__syncthreads();
+	const uint32_t nm = gather_flagged(a, a.matched, nullptr, g0, ng, list, cap, &n_sh, lane);
+	bool amb = nm > cap;                                  // (cannot happen: fewer than 2 k matches)
+	if (!amb)
+		for (uint32_t x = lane; x < nm; x += 64) {
+			const SelSlot me = list[x];
+			bool keep = true;
+			if (nm > (uint32_t)a.k) {
+				uint32_t rank = 0;
+				for (uint32_t y = 0; y < nm; ++y) {
+					if (y == x) continue;
+					if (sel_ambiguous(a.ev, list[y], me)) amb = true;
+					rank += sel_less(list[y], me) ? 1u : 0u;
+				}
+				keep = rank < (uint32_t)a.k;
+			}
+			a.kept[me.g] = keep ? 1u : 0u;
+		}
+	if (__ballot(amb) != 0) {
+		for (uint32_t gi = lane; gi < ng; gi += 64) a.kept[g0 + gi] = 0;
+		if (lane == 0) { a.qstate[q] = EXT_Q_AMBIGUOUS; atomicAdd(&a.ctr->n_ambiguous, 1u); }
+	}
+	else if (lane == 0 && a.q_removed[q]) atomicAdd(&a.ctr->n_filtered, a.q_removed[q]);
+}
+
 hipError_t ensure_tmp(void** tmp, size_t* have, size_t need)
 {
 	if (need <= *have) return hipSuccess;
@@ -617,6 +867,45 @@ hipError_t launch_ext_append(const ExtArgs& a, uint32_t n_items, bool kept, int6
 	if (e != hipSuccess) return e;
 	hipLaunchKernelGGL(ext_round2_kernel, dim3((a.n_groups + 255) / 256), dim3(256), 0, st, a);
 	return hipGetLastError();
+}
+
+namespace {
+// record slots (exclusive scan of the kept flags) and the list the trace walk runs over
+hipError_t list_kept(const ExtArgs& a, hipStream_t st)
+{
+	size_t need = 0;
+	hipError_t e = rocprim::exclusive_scan(nullptr, need, a.kept, a.kept_pos, 0u, (size_t)a.n_groups + 1, rocprim::plus<uint32_t>(), st);
+	if (e != hipSuccess) return e;
+	e = ensure_tmp(a.scan_tmp, a.scan_tmp_bytes, need);
+	if (e != hipSuccess) return e;
+	e = rocprim::exclusive_scan(*a.scan_tmp, need, a.kept, a.kept_pos, 0u, (size_t)a.n_groups + 1, rocprim::plus<uint32_t>(), st);
+	if (e != hipSuccess) return e;
+	hipLaunchKernelGGL(ext_round2_kernel, dim3((a.n_groups + 255) / 256), dim3(256), 0, st, a);
+	return hipGetLastError();
+}
+}
+
+hipError_t launch_ext_fcand(const ExtArgs& a, uint32_t n_items, bool kept, int64_t rel, hipStream_t st)
+{
+	if (n_items > 0 && (!kept || rel != 0)) hipLaunchKernelGGL(ext_rebase_kernel, dim3((n_items + 255) / 256), dim3(256), 0, st, a, n_items, rel, kept ? 1 : 0);
+	hipLaunchKernelGGL(ext_fcand_kernel, dim3(a.n_queries), dim3(64), 0, st, a);
+	return list_kept(a, st);
+}
+
+hipError_t launch_ext_fappend(const ExtArgs& a, uint32_t n_listed, uint32_t list_need, bool last, hipStream_t st)
+{
+	if (n_listed > 0) hipLaunchKernelGGL(ext_filter_kernel, dim3((n_listed + 255) / 256), dim3(256), 0, st, a, n_listed);
+	// the LDS list: what the query with the most swept targets can need, in steps of 64 slots, at most EXT_FILTER_LIST (56 KB)
+	uint32_t cap = (list_need + 63) / 64 * 64;
+	cap = cap < 64 ? 64 : cap > EXT_FILTER_LIST ? EXT_FILTER_LIST : cap;
+	hipLaunchKernelGGL(ext_fappend_kernel, dim3(a.n_queries), dim3(64), (size_t)cap * (sizeof(SelSlot) + 4), st, a, last ? 1 : 0, cap);
+	return hipGetLastError();
+}
+
+hipError_t launch_ext_ffinal(const ExtArgs& a, hipStream_t st)
+{
+	hipLaunchKernelGGL(ext_ffinal_kernel, dim3(a.n_queries), dim3(64), 2 * (size_t)a.k * sizeof(SelSlot), st, a);
+	return list_kept(a, st);
 }
 
 hipError_t launch_ext_resweep(const ExtArgs& a, uint32_t n_kept, hipStream_t st)

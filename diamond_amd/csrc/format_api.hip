@@ -11,6 +11,7 @@
 #include <vector>
 #include "../../include/diamond_hip.h"
 #include "ctx.h"
+#include "filter_core.h"
 
 using namespace dmnd;
 
@@ -21,10 +22,10 @@ const char* const NT = "ACGTN";
 const char* const FIELD_NAMES[DMND_F_COUNT] = { "qseqid", "qlen", "sseqid", "sallseqid", "slen", "qstart", "qend", "sstart", "send", "qseq", "sseq",
 	"evalue", "bitscore", "score", "length", "pident", "nident", "mismatch", "positive", "gapopen", "gaps", "ppos", "qframe", "btop", "stitle",
 	"salltitles", "qcovhsp", "qtitle", "full_sseq", "qnum", "snum", "scovhsp", "full_qseq", "qseq_gapped", "sseq_gapped", "qstrand", "cigar",
-	"qseq_translated", "hspnum" };
+	"qseq_translated", "hspnum", "approx_pident" };
 // fields of the reference that this build does not print
 const char* const UNAVAILABLE[] = { "staxids", "sscinames", "sskingdoms", "skingdoms", "sphylums", "slineages", "qqual", "full_qqual", "full_qseq_mate",
-	"normalized_bitscore", "normalized_bitscore_query", "normalized_nident", "approx_pident", "corrected_bitscore" };
+	"normalized_bitscore", "normalized_bitscore_query", "normalized_nident", "corrected_bitscore" };
 
 enum { OP_MATCH = 0, OP_INSERTION = 1, OP_DELETION = 2, OP_SUBSTITUTION = 3 };
 
@@ -251,6 +252,7 @@ int print_field(Out& o, const dmnd_hsp_view& v, int id)
 		else for (int i = h.q_begin; i < h.q_end; ++i) o << AA[v.qseq[i] & 31];
 		break;
 	case DMND_F_HSPNUM: o << 0; break;                      // max_hsps = 1
+	case DMND_F_APPROX_PIDENT: o << dmnd::hsp_approx_id(h.score, h.q_end - h.q_begin, h.s_end - h.s_begin, h.identities, h.length); break;      // Hsp::approx_id (filter_core.h)
 	default: return fail(DMND_E_ARG, "dmnd_format_fields: unknown field id");
 	}
 	return DMND_OK;

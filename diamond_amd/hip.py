@@ -78,7 +78,7 @@ EXPORTS = ["dmnd_abi_version", "dmnd_last_error", "dmnd_default_params", "dmnd_c
            "dmnd_set_db_letters", "dmnd_upload_block", "dmnd_upload_cbs", "dmnd_banded_swipe",
            "dmnd_banded_swipe_host", "dmnd_banded_cols", "dmnd_evalue", "dmnd_bitscore", "dmnd_evalue_p",
            "dmnd_bitscore_p", "dmnd_evalue_batch", "dmnd_last_kernel_ms", "dmnd_seed_params_fast", "dmnd_seed_params_default", "dmnd_seed_search",
-           "dmnd_seed_hits", "dmnd_seed_kernel_ms", "dmnd_extend_plan", "dmnd_extend", "dmnd_extend_stats", "dmnd_extend_plan_stats", "dmnd_extend_plan_device", "dmnd_extend_device_stats", "dmnd_extend_reserve", "dmnd_extend_records_device", "dmnd_join_contexts_device", "dmnd_format_tab", "dmnd_set_max_target_seqs",
+           "dmnd_seed_hits", "dmnd_seed_kernel_ms", "dmnd_extend_plan", "dmnd_extend", "dmnd_extend_stats", "dmnd_extend_plan_stats", "dmnd_extend_plan_device", "dmnd_extend_device_stats", "dmnd_extend_filter_stats", "dmnd_set_approx_id", "dmnd_extend_reserve", "dmnd_extend_records_device", "dmnd_join_contexts_device", "dmnd_format_tab", "dmnd_set_max_target_seqs",
            "dmnd_seed_params_sensitive", "dmnd_set_gapped_filter", "dmnd_gapped_filter", "dmnd_gapped_filter_ms",
            "dmnd_set_query_contexts", "dmnd_translate", "dmnd_format_tab_translated", "dmnd_mask_block", "dmnd_mask_kernel_ms", "dmnd_seed_params_preset", "dmnd_set_comp_based_stats",
            "dmnd_seed_params_set_index_chunks", "dmnd_join_blocks", "dmnd_set_sensitivity", "dmnd_touch_streams",
@@ -854,6 +854,16 @@ class Context:
         self.lib.dmnd_set_max_target_seqs.argtypes = [ctypes.c_void_p, ctypes.c_int]
         self._check(self.lib.dmnd_set_max_target_seqs(self.h, int(k)))
 
+    def set_filters(self, min_id=0.0, query_cover=0.0, subject_cover=0.0, min_bit_score=0.0):
+        """--id, --query-cover, --subject-cover (percentages, 0 = off) and --min-score BITS (dmnd_set_filters)."""
+        self.lib.dmnd_set_filters.argtypes = [ctypes.c_void_p] + [ctypes.c_double] * 4
+        self._check(self.lib.dmnd_set_filters(self.h, float(min_id), float(query_cover), float(subject_cover), float(min_bit_score)))
+
+    def set_approx_id(self, approx_min_id):
+        """--approx-id PERCENT (0 = off): filter on the identity estimated from score and range lengths (dmnd_set_approx_id)."""
+        self.lib.dmnd_set_approx_id.argtypes = [ctypes.c_void_p, ctypes.c_double]
+        self._check(self.lib.dmnd_set_approx_id(self.h, float(approx_min_id)))
+
     def extend_reserve(self, n_hits_hint):
         """First-call allocations of extend() for about n_hits_hint seed hits, made ahead of it (dmnd_extend_reserve)."""
         self.lib.dmnd_extend_reserve.argtypes = [ctypes.c_void_p, ctypes.c_int64]
@@ -969,8 +979,12 @@ class Context:
         st = (ctypes.c_double * 10)()
         self.lib.dmnd_extend_device_stats.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
         self._check(self.lib.dmnd_extend_device_stats(self.h, st))
+        fs = (ctypes.c_double * 2)()
+        self.lib.dmnd_extend_filter_stats.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
+        self._check(self.lib.dmnd_extend_filter_stats(self.h, fs))
         return dict(queries=int(st[0]), queries_back_to_host=int(st[1]), items=int(st[2]), records=int(st[3]), band_diagonal_steps=st[4], wavefront_diagonal_steps=st[5],
-                    round2_cells=st[6], round2_cells_swept_again=st[7], round2_sweep_kernel_ms=st[8], queries_capped=int(st[9]))
+                    round2_cells=st[6], round2_cells_swept_again=st[7], round2_sweep_kernel_ms=st[8], queries_capped=int(st[9]),
+                    records_filtered=int(fs[0]), queries_on_filter_threshold=int(fs[1]))
 
     def last_kernel_ms(self):
         a, b = ctypes.c_double(0), ctypes.c_double(0)

@@ -483,6 +483,16 @@ int dmnd_set_top_percent(dmnd_ctx* ctx, double percent);
  * replaces the e-value cutoff (ScoreMatrix::report_cutoff, stats/score_matrix.cpp:234-239). Query cover is only available for
  * untranslated queries. */
 int dmnd_set_filters(dmnd_ctx* ctx, double min_id, double query_cover, double subject_cover, double min_bit_score);
+/* --approx-id PERCENT (0 = off): one more of those filters, on the identity estimated from the raw score and the longer of the HSP's
+ * two ranges -- min(max(score / max(query range, subject range) * 16.56 + 11.41, 0), 100), and 100 for an HSP whose every column
+ * is an identity (Stats::approx_id, stats/stats.cpp:113-118; Hsp::approx_id_percent, basic/hssp.cpp:380-391; filter_hsp,
+ * align/culling.cpp:157-161). The value is the output column approx_pident. It stays set until the next call, like the filters
+ * above; dmnd_set_filters does not touch it. The reference refuses it together with --id (run/config.cpp:168) and raises the
+ * Hamming identities of a stage-1 hit to 20 (from 50 %) or 30 (from 90 %) unless --id2 is given (search/setup.cpp:70-78, 343):
+ * both are the caller's business, as for the other options (the CLI does them). The frameshift pipeline (dmnd_frameshift_swipe, -F)
+ * does not read it, as the reference's does not. Not reproduced: the early rejection before a reversed sweep
+ * (dp/swipe/swipe_wrapper.cpp:365-377; DESIGN.md 4.17 says where it differs). */
+int dmnd_set_approx_id(dmnd_ctx* ctx, double approx_min_id);
 /* Translated queries: the lengths of the DNA reads of the uploaded query block (one per query = per six contexts), which the
  * query cover of an HSP is measured against (Hsp::query_cover_percent over query_source_range). Cleared by the next upload of
  * the query block. */
@@ -620,8 +630,15 @@ int dmnd_extend_plan_device(dmnd_ctx* ctx, const dmnd_seed_hit* hits, int64_t n_
  * [3] records, [4] sum over the round-1 DpTargets of band diagonals x anti-diagonal steps and [5] of the 128 P diagonals their wavefront
  * holds x steps ([4] / [5] = lane use of the sweeps), [6] DP cells of the device half's round-2 targets, [7] of those swept again in
  * round 2 (their round-1 sweep kept no trace rows), [8] device ms of those sweeps, [9] of [1] the queries still ranking after the last chunk; all 0 = every query took the host path (other modes: --max-hsps != 1, --top,
- * filters, matrix adjustment, --ext full, transcripts wanted, translated queries). */
+ * --no-self-hits, matrix adjustment, --ext full, transcripts wanted, translated queries). Under the filters of dmnd_set_filters /
+ * dmnd_set_approx_id [1] also counts the queries of dmnd_extend_filter_stats [1]. */
 int dmnd_extend_device_stats(const dmnd_ctx* ctx, double out[10]);
+/* The device half under the filters of dmnd_set_filters / dmnd_set_approx_id (it applies them in HBM: every target of a ranking chunk
+ * that passes the report cutoff is walked before the culling, a filter kernel reads the walk's statistics, and a target that fails
+ * takes none of the -k places). Of the last dmnd_extend: [0] records a filter removed on the device (of the queries it finished),
+ * [1] queries handed back to the host path because a filter value lay on its threshold (within 1e-9 relative; counted in
+ * dmnd_extend_device_stats [1] as well). Both 0 without filters or when every query took the host path. */
+int dmnd_extend_filter_stats(const dmnd_ctx* ctx, double out[2]);
 /* Round 6: the records of the last dmnd_extend where they lie in HBM, complete (the host's e-values and bit scores are written back
  * into them): *records_dev is valid until the context's next dmnd_extend; *n = -1 (and NULL) when part of the records only exists on the
  * host (queries that took the host path: other modes, or a query handed back). The records dmnd_extend returned are the same. */
@@ -650,7 +667,7 @@ enum {
 	DMND_F_QSEQ, DMND_F_SSEQ, DMND_F_EVALUE, DMND_F_BITSCORE, DMND_F_SCORE, DMND_F_LENGTH, DMND_F_PIDENT, DMND_F_NIDENT, DMND_F_MISMATCH,
 	DMND_F_POSITIVE, DMND_F_GAPOPEN, DMND_F_GAPS, DMND_F_PPOS, DMND_F_QFRAME, DMND_F_BTOP, DMND_F_STITLE, DMND_F_SALLTITLES, DMND_F_QCOVHSP,
 	DMND_F_QTITLE, DMND_F_FULL_SSEQ, DMND_F_QNUM, DMND_F_SNUM, DMND_F_SCOVHSP, DMND_F_FULL_QSEQ, DMND_F_QSEQ_GAPPED, DMND_F_SSEQ_GAPPED,
-	DMND_F_QSTRAND, DMND_F_CIGAR, DMND_F_QSEQ_TRANSLATED, DMND_F_HSPNUM, DMND_F_COUNT
+	DMND_F_QSTRAND, DMND_F_CIGAR, DMND_F_QSEQ_TRANSLATED, DMND_F_HSPNUM, DMND_F_APPROX_PIDENT, DMND_F_COUNT
 };
 /* One HSP with everything a format reads (HspContext, src/basic/match.h:281-440) */
 typedef struct {

@@ -29,13 +29,16 @@ struct ExtCounters {
 	unsigned long long diag_steps, lane_steps;   // over the round-1 items: band diagonals x anti-diagonal steps, and the 128 P diagonals the item's wavefront holds x steps (lane use of the sweeps)
 	uint32_t list_need, list_pad;            // with HSP filters, of the current iteration: the most targets one active query has had swept so far = what its aligned targets and the chunk's can come to (sizes the LDS list of ext_fappend_kernel)
 	uint32_t n_filtered, n_threshold;        // with HSP filters: records a filter removed (of the queries done here), queries handed back for a value on a threshold
+	uint32_t n_records, n_records_pad;       // --top: entries of the walked list that are records (with HSP filters fewer than n_kept)
 };
 
 // Byte offsets of the work arrays in the buffer (each 64-byte aligned), for nG groups, nQ queries, nB bands and -k k
 struct ExtLayout {
 	size_t nG, nQ, nB;
 	bool filters;           // the layout of a call with HSP filters (--id, --approx-id, covers): the arrays below marked so exist
-	size_t nR;              // round-2 capacity: survivors = records (at most -k per query, at most one per group)
+	bool top;               // the layout of a --top call: the arrays below marked so exist
+	size_t nR;              // round-2 capacity: survivors = records (at most -k per query, at most one per group); --top: nG -- the
+	                        // cut is a threshold against the best score, so every group of a query can become a record
 	size_t nS;              // capacity of the trace walk's list: nR; with HSP filters nG -- every target of a chunk that passes the report
 	                        // cutoff is walked BEFORE the culling (a group is swept once, so the groups bound all chunks' candidates)
 	size_t nI;              // items: every band once + a copy of every walked target (round 2 without kept traces)
@@ -43,18 +46,19 @@ struct ExtLayout {
 	size_t o_qstate, o_qactive, o_qi0, o_qi1, o_qtail, o_qprev, o_qswept;
 	size_t o_okeys, o_okeys2, o_oidx, o_gorder, o_aligned, o_gfirst, o_gcnt, o_cnt, o_item_off, o_kept, o_kept_pos, o_cand_item, o_cand_ev;
 	size_t o_fverdict, o_matched, o_qmatched, o_qremoved;      // with HSP filters only (empty otherwise)
+	size_t o_cand_score, o_rperm;                              // --top only (empty otherwise): best reported score per group, record order of the walked list
 	size_t o_items, o_off_item, o_p, o_ends, o_hsps, o_keys, o_keys_sorted, o_idx, o_order, o_rows, o_rows_slot, o_off_slot, o_pairs;
 	size_t o_r2_order, o_r2_p, o_r2_off, o_r2_tr, o_r2_group, o_records, o_ctr;
 	size_t bytes;           // the whole buffer
 };
 
-inline ExtLayout ext_layout(size_t nG, size_t nQ, size_t nB, int k, bool filters = false)
+inline ExtLayout ext_layout(size_t nG, size_t nQ, size_t nB, int k, bool filters = false, bool top = false)
 {
 	ExtLayout L;
-	L.nG = nG; L.nQ = nQ; L.nB = nB; L.filters = filters;
+	L.nG = nG; L.nQ = nQ; L.nB = nB; L.filters = filters; L.top = top;
 	const size_t kk = k > 1 ? (size_t)k : 1;
-	L.nR = nG < nQ * kk ? nG : nQ * kk;
-	L.nS = filters ? nG : L.nR;
+	L.nR = top || nG < nQ * kk ? nG : nQ * kk;
+	L.nS = filters || top ? nG : L.nR;
 	L.nI = nB + L.nS;
 	L.r2_tr_clear = L.nS + 1;
 	const size_t nI = L.nI, nR = L.nR, nS = L.nS;
@@ -64,6 +68,7 @@ inline ExtLayout ext_layout(size_t nG, size_t nQ, size_t nB, int k, bool filters
 	L.o_okeys = take(nG * 8); L.o_okeys2 = take(nG * 8); L.o_oidx = take(nG * 4); L.o_gorder = take(nG * 4); L.o_aligned = take(nG); L.o_gfirst = take(nG * 4); L.o_gcnt = take(nG * 4);
 	L.o_cnt = take((nG + 1) * 4); L.o_item_off = take((nG + 1) * 4); L.o_kept = take((nG + 1) * 4); L.o_kept_pos = take((nG + 1) * 4); L.o_cand_item = take(nG * 4); L.o_cand_ev = take(nG * 8);
 	L.o_fverdict = take(filters ? nG : 0); L.o_matched = take(filters ? nG : 0); L.o_qmatched = take(filters ? nQ * 4 : 0); L.o_qremoved = take(filters ? nQ * 4 : 0);
+	L.o_cand_score = take(top ? nG * 4 : 0); L.o_rperm = take(top ? nS * 4 : 0);
 	L.o_items = take(nI * sizeof(dmnd_dp_target)); L.o_off_item = take(nI * 8); L.o_p = take(nI * 4); L.o_ends = take(nI * EXT_SWIPE_END_BYTES); L.o_hsps = take(nI * sizeof(dmnd_hsp));
 	L.o_keys = take(nI * 4); L.o_keys_sorted = take(nI * 4); L.o_idx = take(nI * 4); L.o_order = take(nI * 4); L.o_rows = take(nI * 8); L.o_rows_slot = take((nI + 1) * 8); L.o_off_slot = take((nI + 1) * 8);
 	L.o_pairs = take((nI + 8 * EXT_CLASSES) * 4);
@@ -74,14 +79,15 @@ inline ExtLayout ext_layout(size_t nG, size_t nQ, size_t nB, int k, bool filters
 }
 
 // What the device half touches of each array, from the array's offset on: its reads and writes by the sizes the kernels index with
-// (n_groups, item_cap = nI, r2_cap = nR), and its memset clears. In layout order; returns the number of regions.
+// (n_groups, item_cap = nI, r2_cap = nR), and its memset clears. In layout order; returns the number of regions. Under --top the
+// record order of the walked list is sorted in okeys / okeys_sorted / oidx (free once the ranking order stands; nS = nG entries).
 struct ExtRegion { const char* name; size_t off, used; };
-enum { EXT_REGIONS = 44 };
+enum { EXT_REGIONS = 46 };
 
 inline int ext_regions(const ExtLayout& L, ExtRegion* r)
 {
 	const size_t nG = L.nG, nQ = L.nQ, nI = L.nI, nR = L.nR, nS = L.nS;
-	const bool filters = L.filters;
+	const bool filters = L.filters, top = L.top;
 	int n = 0;
 	auto add = [&](const char* name, size_t off, size_t used) { r[n++] = ExtRegion{ name, off, used }; };
 	add("qstate", L.o_qstate, nQ); add("q_active", L.o_qactive, nQ); add("q_i0", L.o_qi0, nQ * 4); add("q_i1", L.o_qi1, nQ * 4);
@@ -93,6 +99,7 @@ inline int ext_regions(const ExtLayout& L, ExtRegion* r)
 	add("cand_item", L.o_cand_item, nG * 4); add("cand_ev", L.o_cand_ev, nG * 8);
 	add("fverdict", L.o_fverdict, filters ? nG : 0); add("matched", L.o_matched, filters ? nG : 0);
 	add("q_matched", L.o_qmatched, filters ? nQ * 4 : 0); add("q_removed", L.o_qremoved, filters ? nQ * 4 : 0);
+	add("cand_score", L.o_cand_score, top ? nG * 4 : 0); add("rperm", L.o_rperm, top ? nS * 4 : 0);
 	add("items", L.o_items, nI * sizeof(dmnd_dp_target)); add("off_item", L.o_off_item, nI * 8); add("p_of_item", L.o_p, nI * 4);
 	add("ends", L.o_ends, nI * EXT_SWIPE_END_BYTES); add("hsps", L.o_hsps, nI * sizeof(dmnd_hsp));
 	add("keys", L.o_keys, nI * 4); add("keys_sorted", L.o_keys_sorted, nI * 4); add("idx", L.o_idx, nI * 4); add("order", L.o_order, nI * 4);

@@ -20,6 +20,7 @@ struct DeviceCfg {
 	double max_evalue = 0.001;
 	double min_bit_score = 0.0;          // --min-score
 	FilterCfg filters;                   // --id, --approx-id, --query-cover, --subject-cover (filter_core.h)
+	double top = -1.0;                   // --top: >= 0 = the targets within this percentage of the best bit score, -k plays no part
 };
 
 // What the device planner hands over (page-locked host copies of its lists; valid until the context's next dmnd_extend)

@@ -142,9 +142,10 @@ int dmnd::plan_fetch_lists(dmnd_ctx* c, DevPlan& plan)
 
 static bool keep_traces_dev() { static const bool v = [] { const char* e = std::getenv("DMND_EXTEND_KEEP_TRACE"); return !e || e[0] != '0'; }(); return v; }
 
-// The extension of the queries whose targets fit one ranking chunk, in HBM from the planner's bands to the match records
-// (extend_kernels.h). records: those queries' matches in output order (query ascending; e-value, score, target inside a query) with
-// the HOST's e-value and bit score; qstate[k] (k = index into plan.queries): EXT_Q_DEVICE = done here, anything else = the host path
+// The extension of the planned queries, ranking chunk by ranking chunk, in HBM from the planner's bands to the match records
+// (extend_kernels.h): -k culling by e-value, or -- h.top >= 0 -- the --top culling by score, either with or without the HSP filters.
+// records: those queries' matches in output order (query ascending; inside a query e-value, score, target, or under --top score,
+// target) with the HOST's e-value and bit score; qstate[k] (k = index into plan.queries): EXT_Q_DEVICE = done here, anything else = the host path
 // has to extend the query. done = false: nothing was done here (no eligible query, or the kept traces would not fit the context's
 // trace budget), every query goes to the host path.
 int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan, int threads, std::vector<dmnd_match>& records, std::vector<uint8_t>& qstate, bool& done)
@@ -153,11 +154,13 @@ int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan,
 	TraceLaps tr("dmnd_extend (device half)");
 	const int64_t chunk = h.ranking_chunk;
 	if (chunk > EXT_MAX_CHUNK || plan.n_bands == 0) return DMND_OK;
-	if (((size_t)h.max_target_seqs + 2 * (size_t)chunk) * 24 > ((size_t)60 << 10)) return DMND_OK;      // (the LDS lists of ext_append_kernel)
+	const bool top = h.top >= 0.0;                      // (--top: no LDS list, -k plays no part)
+	if (!top && ((size_t)h.max_target_seqs + 2 * (size_t)chunk) * 24 > ((size_t)60 << 10)) return DMND_OK;      // (the LDS lists of ext_append_kernel)
 	const bool filt = filters_on(h.filters);
 	// (with filters: the aligned targets of a query and a chunk, and the matches of all rounds -- fewer than 2 k --, fit the LDS list)
-	if (filt && ((size_t)h.max_target_seqs + (size_t)chunk > EXT_FILTER_LIST || 2 * (size_t)h.max_target_seqs > EXT_FILTER_LIST)) return DMND_OK;
-	const ExtLayout L = ext_layout(plan.n_groups, plan.n_queries, plan.n_bands, h.max_target_seqs, filt);
+	if (!top && filt && ((size_t)h.max_target_seqs + (size_t)chunk > EXT_FILTER_LIST || 2 * (size_t)h.max_target_seqs > EXT_FILTER_LIST)) return DMND_OK;
+	const bool fchunk = filt && !top;                   // the chunk-by-chunk walk of the -k filter path (under --top the filters come after the one walk)
+	const ExtLayout L = ext_layout(plan.n_groups, plan.n_queries, plan.n_bands, h.max_target_seqs, filt, top);
 	const size_t nQ = L.nQ, nR = L.nR;
 	if (int rc = c->ext_dev.ensure(L.bytes)) return rc;
 	Guard guard(c->ext_dev, L.bytes, c->stream);
@@ -171,6 +174,8 @@ int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan,
 	a.use_cbs = h.use_cbs ? 1 : 0; a.row_min_items = (uint32_t)std::min<int64_t>(sweep_rows_min_items(), 0xffffffffll); a.chunk_size = (uint32_t)chunk; a.k = h.max_target_seqs; a.max_swipe_dp = h.max_swipe_dp;
 	const Evaluer& E = c->evaluer;
 	a.min_bit_score = h.min_bit_score; a.filt = h.filters; a.filt_on = filt ? 1 : 0;
+	a.top = top_cfg(top ? h.top : 0.0, E.lambda, E.ln_k); a.top_on = top ? 1 : 0;
+	a.cand_score = reinterpret_cast<int32_t*>(d + L.o_cand_score); a.rperm = reinterpret_cast<uint32_t*>(d + L.o_rperm);
 	a.ev = ExtEvalue{ E.lambda, E.K, E.ln_k, E.db_letters, E.a, E.b, E.alpha, E.beta, E.sigma, E.tau, E.v_thr, E.c_thr, h.max_evalue };
 	a.qstate = reinterpret_cast<uint8_t*>(d + L.o_qstate); a.q_active = reinterpret_cast<uint8_t*>(d + L.o_qactive);
 	a.q_i0 = reinterpret_cast<uint32_t*>(d + L.o_qi0); a.q_i1 = reinterpret_cast<uint32_t*>(d + L.o_qi1);
@@ -258,7 +263,7 @@ int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan,
 		const bool last = iter + 1 >= max_chunks;      // (a query still ranking after this chunk goes back to the host)
 		// with filters a chunk's targets are walked before the next chunk is swept: its trace rows are dead by now, and the arenas --
 		// the kept rows' and the one of a chunk swept again -- are used again, so a call never holds more than one chunk's rows
-		if (filt) { trace_used = 0; n_more = 0; }
+		if (fchunk) { trace_used = 0; n_more = 0; }
 		// 1. the chunk's items, launch order, trace offsets, pairs
 		HIP_TRY(launch_ext_prepare(a, st));
 		HIP_TRY(copy_now(st, c->ext_host.p, a.ctr, sizeof(ExtCounters), hipMemcpyDeviceToHost));
@@ -277,7 +282,8 @@ int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan,
 			// against 31 with trace bits) and the survivors a second time is less work: 18 + 31 f < 31 for a surviving fraction
 			// f < 0.42 (C2skew: 125 targets per query, f <= 0.2; C2, C3: f = 0.8 / 0.56, rows kept)
 			// (with filters every target past the report cutoff is walked, not the -k survivors: the rows are kept whenever they fit)
-			const bool few_survive = !filt && ctr.window_bound * 100 < ctr.window_targets * (unsigned long long)tuning().extend_resweep_below_pct;
+			// (--top: how many survive the cut is not known before the sweeps, the rows are kept whenever they fit)
+			const bool few_survive = !filt && !top && ctr.window_bound * 100 < ctr.window_targets * (unsigned long long)tuning().extend_resweep_below_pct;
 			kept = keep_traces_dev() && !few_survive && trace_used + (size_t)ctr.total_rows <= trace_budget;
 			DevBuf* arena = nullptr;
 			if (kept) if (int rc = arena_for((size_t)ctr.total_rows, arena, rel)) return rc;
@@ -288,9 +294,10 @@ int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan,
 			HIP_TRY(hipEventRecord(c->ev1, st));
 		}
 		const uint32_t n_items_iter = ctr.n_items;
-		if (!filt) {
+		if (!fchunk) {
 			// 3. best HSP per target, append_hits, next window; and -- in case that was the last chunk of every query -- final culling + round-2 list
-			HIP_TRY(launch_ext_append(a, ctr.n_items, kept, rel, last, st));
+			if (top) HIP_TRY(launch_ext_top_append(a, ctr.n_items, kept, rel, last, st));
+			else HIP_TRY(launch_ext_append(a, ctr.n_items, kept, rel, last, st));
 			HIP_TRY(copy_now(st, c->ext_host.p, a.ctr, sizeof(ExtCounters), hipMemcpyDeviceToHost));
 			ctr = *c->ext_host.as<ExtCounters>();
 			if (n_items_iter > 0) { float ms = 0.f; HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1)); ms_sweeps += ms; }
@@ -326,14 +333,14 @@ int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan,
 	tr.lap("sweeps, culling");
 	// 4. round 2: the survivors whose trace rows were not kept are swept again with traceback (copies of their items, one more
 	// iteration), then one walk over all survivors' traces, then the records
-	if (filt) {
+	if (fchunk) {
 		// every walk is done: the first -k of each query's matches and their record slots
 		HIP_TRY(launch_ext_ffinal(a, st));
 		HIP_TRY(copy_now(st, c->ext_host.p, a.ctr, sizeof(ExtCounters), hipMemcpyDeviceToHost));
 		ctr = *c->ext_host.as<ExtCounters>();
 		ctr.n_resweep = 0;
 	}
-	if (ctr.n_kept > nR) return fail(DMND_E_CAP, "dmnd_extend: more device records than -k allows");
+	if (ctr.n_kept > nR) return fail(DMND_E_CAP, "dmnd_extend: more device records than -k allows");      // (--top: nR = the groups, the list has at most one entry per group)
 	const uint32_t n_kept = ctr.n_kept;
 	if (ctr.n_resweep > 0) {
 		// (at most -k survivors per query)
@@ -342,16 +349,25 @@ int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan,
 	}
 	ctr.n_kept = n_kept;
 	HIP_TRY(hipEventRecord(c->ev1, st));
-	if (ctr.n_kept > 0 && !filt) if (int rc = walk(ctr.n_kept)) return rc;
+	if (ctr.n_kept > 0 && !fchunk) if (int rc = walk(ctr.n_kept)) return rc;
 	HIP_TRY(hipEventRecord(c->ev2, st));
-	HIP_TRY(launch_ext_records(a, ctr.n_kept, st));
+	// (--top: the filters' verdicts over the walked list, the cut against the best match that passed, the records in score order;
+	// how many of the walked targets are records is known only now)
+	uint32_t n_out = ctr.n_kept;
+	if (top) {
+		HIP_TRY(launch_ext_top_records(a, n_kept, st));
+		HIP_TRY(copy_now(st, c->ext_host.p, a.ctr, sizeof(ExtCounters), hipMemcpyDeviceToHost));
+		n_out = c->ext_host.as<ExtCounters>()->n_records;
+		if (n_out > n_kept) return fail(DMND_E_CAP, "dmnd_extend: more device records than walked targets");
+	}
+	else HIP_TRY(launch_ext_records(a, ctr.n_kept, st));
 	const size_t h_ctr = 0, h_qstate = (sizeof(ExtCounters) + 63) & ~(size_t)63, h_records = (h_qstate + nQ + 63) & ~(size_t)63,
-		h_bytes = h_records + (size_t)ctr.n_kept * sizeof(dmnd_match);
+		h_bytes = h_records + (size_t)n_out * sizeof(dmnd_match);
 	if (int rc = c->ext_host.ensure(h_bytes)) return rc;
 	char* hp = c->ext_host.as<char>();
 	HIP_TRY(hipMemcpyAsync(hp + h_ctr, a.ctr, sizeof(ExtCounters), hipMemcpyDeviceToHost, st));
 	HIP_TRY(hipMemcpyAsync(hp + h_qstate, a.qstate, nQ, hipMemcpyDeviceToHost, st));
-	if (ctr.n_kept) HIP_TRY(hipMemcpyAsync(hp + h_records, a.records, (size_t)ctr.n_kept * sizeof(dmnd_match), hipMemcpyDeviceToHost, st));
+	if (n_out) HIP_TRY(hipMemcpyAsync(hp + h_records, a.records, (size_t)n_out * sizeof(dmnd_match), hipMemcpyDeviceToHost, st));
 	HIP_TRY(sync_stream(st));
 	ctr = *reinterpret_cast<const ExtCounters*>(hp + h_ctr);
 	tr.lap("walk, records, copy");
@@ -363,7 +379,7 @@ int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan,
 	// 4. the host's own e-value and bit score in every record; the device ordered a query's records by ITS e-values -- checked,
 	// and put right where the two disagree
 	const dmnd_match* rec = reinterpret_cast<const dmnd_match*>(hp + h_records);
-	records.assign(rec, rec + ctr.n_kept);
+	records.assign(rec, rec + n_out);
 	const std::vector<int64_t>& ql = c->limits[DMND_QUERY];
 	const std::vector<int64_t>& tl = c->limits[DMND_TARGET];
 	const size_t n = records.size(), per = 4096, n_chunks = (n + per - 1) / per;
@@ -375,11 +391,12 @@ int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan,
 		}
 	});
 	bool reordered = false;
+	const auto less = top ? match_less_score : match_less;      // (Match::cmp_score under --top: exact on integers, so the check never fires there)
 	for (size_t b = 0; b < n;) {
 		size_t e = b + 1;
 		bool sorted = true;
-		while (e < n && records[e].query == records[b].query) { sorted &= !match_less(records[e], records[e - 1]); ++e; }
-		if (!sorted) { std::sort(records.begin() + (ptrdiff_t)b, records.begin() + (ptrdiff_t)e, match_less); reordered = true; }
+		while (e < n && records[e].query == records[b].query) { sorted &= !less(records[e], records[e - 1]); ++e; }
+		if (!sorted) { std::sort(records.begin() + (ptrdiff_t)b, records.begin() + (ptrdiff_t)e, less); reordered = true; }
 		b = e;
 	}
 	// 5. ... and back into the copy in HBM: the records stay there, complete, for a join on the device (dmnd_extend_records_device,
@@ -403,11 +420,12 @@ int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan,
 	c->ext_stats[9] += ms_sweeps; c->ext_stats[10] += ms_sweeps2; c->ext_stats[11] += ms_walk;
 	size_t n_eligible = 0;
 	for (uint8_t x : qstate) n_eligible += x != EXT_Q_HOST;
-	c->ext_dev_stats[0] = (double)n_eligible; c->ext_dev_stats[1] = (double)(ctr.n_ambiguous + ctr.n_saturated); c->ext_dev_stats[2] = (double)items_total; c->ext_dev_stats[3] = (double)ctr.n_kept;
+	c->ext_dev_stats[0] = (double)n_eligible; c->ext_dev_stats[1] = (double)(ctr.n_ambiguous + ctr.n_saturated); c->ext_dev_stats[2] = (double)items_total; c->ext_dev_stats[3] = (double)n_out;
 	c->ext_dev_stats[4] = (double)ctr.diag_steps; c->ext_dev_stats[5] = (double)ctr.lane_steps;
 	c->ext_dev_stats[6] = (double)ctr.cells2; c->ext_dev_stats[7] = (double)ctr.cells_again; c->ext_dev_stats[8] = ms_sweeps2;
 	c->ext_dev_stats[1] += (double)ctr.n_capped; c->ext_dev_stats[9] = (double)ctr.n_capped;
-	if (filt) {
+	if (top && filt) { c->ext_dev_stats[1] += (double)ctr.n_threshold; c->ext_filter_stats[0] = (double)ctr.n_filtered; c->ext_filter_stats[1] = (double)ctr.n_threshold; }
+	if (fchunk) {
 		c->ext_stats[1] += (double)walked_filt - (double)ctr.n_kept; c->ext_stats[3] += (double)cells2_filt - (double)ctr.cells2;      // (every walked target is a round-2 target)
 		c->ext_dev_stats[1] += (double)ctr.n_threshold; c->ext_dev_stats[6] = (double)cells2_filt;
 		c->ext_filter_stats[0] = (double)ctr.n_filtered; c->ext_filter_stats[1] = (double)ctr.n_threshold;

@@ -56,6 +56,7 @@
 #include "extend_kernels.h"
 #include "match_order.h"
 #include "extend_device.h"
+#include "top_core.h"
 #include <unordered_map>
 
 namespace dmnd {
@@ -164,7 +165,8 @@ DeviceCfg device_cfg(const HostCfg& h)      // what the device half reads of the
 {
 	DeviceCfg d;
 	d.gap_open = h.S.gap_open; d.gap_extend = h.S.gap_extend; d.band_mode_fast = h.band_mode_fast; d.max_target_seqs = h.max_target_seqs;
-	d.ranking_chunk = ranking_chunk_size(h.ref_letters, h.max_target_seqs, h.ranking_block_letters, false);
+	d.top = h.top;
+	d.ranking_chunk = ranking_chunk_size(h.ref_letters, h.max_target_seqs, h.ranking_block_letters, h.top >= 0.0);
 	d.max_swipe_dp = h.max_swipe_dp; d.use_cbs = h.use_cbs; d.max_evalue = h.max_evalue; d.min_bit_score = h.min_bit_score;
 	d.filters.min_id = h.min_id; d.filters.approx_id = h.approx_id; d.filters.query_cover = h.query_cover; d.filters.subject_cover = h.subject_cover;
 	return d;
@@ -495,9 +497,10 @@ size_t output_range(size_t n, const CullCfg& cc, Score score_at)
 {
 	if (n == 0) return 0;
 	if (cc.top < 0.0) return std::min(n, (size_t)cc.k);
-	const double cutoff = std::max((1.0 - cc.top / 100.0) * cc.ev->bitscore(score_at(0)), 1.0);      // top_cutoff_score<double>
+	const TopCfg tc = top_cfg(cc.top, cc.ev->lambda, cc.ev->ln_k);      // top_cutoff_score<double> (top_core.h: the device half's arithmetic)
+	const int best = (int)score_at(0);
 	size_t i = 0;
-	while (i < n && cc.ev->bitscore(score_at(i)) >= cutoff) ++i;
+	while (i < n && top_pass(tc, (int)score_at(i), best)) ++i;
 	return i;
 }
 
@@ -576,7 +579,7 @@ bool append_hits(std::vector<Cand>& targets, const std::vector<Cand>& v, const C
 	const size_t range_end = output_range(targets.size(), cc, [&](size_t i) { return targets[i].score; });
 	if (targets.empty()
 		|| (cc.top < 0.0 && min_evalue <= targets[range_end - 1].evalue)
-		|| (cc.top >= 0.0 && max_score >= (int)((1.0 - cc.top / 100.0) * targets[range_end - 1].score))) {      // top_cutoff_score<int>
+		|| (cc.top >= 0.0 && top_append(top_cfg(cc.top, cc.ev->lambda, cc.ev->ln_k), max_score, targets[range_end - 1].score))) {      // top_cutoff_score<int>
 		append = true; new_hits = true;
 	}
 	if (append) targets.insert(targets.end(), v.begin(), v.end());
@@ -1448,9 +1451,10 @@ extern "C" int dmnd_extend(dmnd_ctx* c, const int8_t* qdata, const int8_t* tdata
 	}
 	if (xd) xd = c->xd_host.as<XdropSeg>();              // (NULL while no group was left to the host: nothing reads it then)
 	const DevPlan* dp = planned ? &plan : nullptr;
-	// The queries whose targets fit one ranking chunk are extended in HBM from here on (extend_kernels.hip): the default search of a
-	// protein query block -- one HSP per target, -k culling by e-value, Hauser bias or none, with or without the HSP filters, no transcripts
-	// (the caller formats from the statistics). The others, and every query of any other mode, take the host path below.
+	// The queries are extended in HBM from here on (extend_kernels.hip), ranking chunk by ranking chunk: the default search of a
+	// protein query block -- one HSP per target, -k culling by e-value or --top culling by score, Hauser bias or none, with or without
+	// the HSP filters, no transcripts (the caller formats from the statistics). The queries the device half hands back, and every
+	// query of any other mode, take the host path below.
 	// DMND_EXTEND_DEVICE=0: all queries on the host path, as up to round 5. Read per call, like the hooks of extend_device.hip
 	// (DESIGN.md 9): a test compares the two paths in one process.
 	const bool ext_gpu = [] { const char* e = std::getenv("DMND_EXTEND_DEVICE"); return !e || e[0] != '0'; }();
@@ -1461,7 +1465,7 @@ extern "C" int dmnd_extend(dmnd_ctx* c, const int8_t* qdata, const int8_t* tdata
 	bool on_device = false;
 	for (double& x : c->ext_dev_stats) x = 0;
 	c->ext_filter_stats[0] = c->ext_filter_stats[1] = 0;
-	if (ext_gpu && planned && h.max_hsps == 1 && h.top < 0.0 && !cbs_matrix_adjust(h.cbs_mode) && !h.ext_full && !transcript
+	if (ext_gpu && planned && h.max_hsps == 1 && !cbs_matrix_adjust(h.cbs_mode) && !h.ext_full && !transcript
 		&& h.global_ranking == 0 && !c->same_title && h.max_target_seqs > 0) {
 		std::vector<uint8_t> qstate;
 		double kept[12];

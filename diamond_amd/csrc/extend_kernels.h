@@ -20,6 +20,7 @@
 #include "../../include/diamond_hip.h"
 #include "extend_core.h"
 #include "filter_core.h"
+#include "top_core.h"
 #include "plan_kernels.h"
 #include "swipe_kernels.h"
 
@@ -44,7 +45,8 @@ struct ExtArgs {
 	int64_t max_swipe_dp;
 	ExtEvalue ev;
 	double min_bit_score;          // --min-score: != 0 replaces the e-value cutoff (ScoreMatrix::report_cutoff)
-	FilterCfg filt; int filt_on;   // the HSP filters (filter_core.h); filt_on: the call runs the filtered ranking loop (the f-kernels)
+	FilterCfg filt; int filt_on;   // the HSP filters (filter_core.h); filt_on: the filter arrays exist (without top_on: the call runs the filtered ranking loop, the f-kernels)
+	TopCfg top; int top_on;        // --top (top_core.h); top_on: the call runs the --top kernels, -k plays no part
 	// per query
 	uint8_t* qstate;               // EXT_Q_*
 	uint8_t* q_active;             // still ranking: its window [q_i0, q_i1) of the order below is the next chunk
@@ -63,6 +65,7 @@ struct ExtArgs {
 	double* cand_ev;
 	uint8_t* fverdict;             // filt_on: the filters' verdict on the target's best HSP (EXT_F_*)
 	uint8_t* matched;              // filt_on: the target is one of the query's matches of an earlier round
+	int32_t* cand_score;           // top_on: the score of its best reported HSP (0: none, or not swept yet)
 	// per item: all iterations' items one after the other (a group is swept once, so n_bands bounds them)
 	uint32_t item_base;            // first item of the current iteration
 	uint32_t item_cap;             // room in the per-item arrays: n_bands + one copy of every survivor (round 2 sweeps those again whose traces were not kept)
@@ -80,6 +83,7 @@ struct ExtArgs {
 	uint32_t r2_tr_clear;          // entries of r2_tr that launch_ext_begin zeroes (ExtLayout::r2_tr_clear)
 	int32_t* r2_order; int32_t* r2_p; int64_t* r2_off; int64_t* r2_tr;       // slot -> item, band class, trace offset, (zero) transcript offsets
 	uint32_t* r2_group;            // slot -> group
+	uint32_t* rperm;               // top_on: record -> slot of the walked list (a query's records by score descending, target ascending)
 	dmnd_match* records;
 	ExtCounters* ctr;
 	void** scan_tmp; size_t* scan_tmp_bytes;
@@ -114,6 +118,17 @@ hipError_t launch_ext_fappend(const ExtArgs& a, uint32_t n_listed, uint32_t list
 hipError_t launch_ext_ffinal(const ExtArgs& a, hipStream_t st);
 // after the walk: the records
 hipError_t launch_ext_records(const ExtArgs& a, uint32_t n_kept, hipStream_t st);
+// --top (a.top_on; src/align/culling.cpp:92-144 with config.toppercent, extend.cpp:272, 331, gapped_final.cpp:103-154). The culling
+// never orders by e-value: the aligned targets are cut by a threshold against the bit score of the best one, and a chunk is appended
+// by an integer comparison against the lowest score left -- wavefront reductions over the query's `aligned` flags in HBM, no LDS
+// list and no limit on the number of aligned targets. launch_ext_top_append stands where launch_ext_append stands (and lists the
+// survivors of the last cut for the walk, speculatively); a score within the tolerance of the cutoff hands the query back.
+// launch_ext_top_records, after the walk of all n_walked survivors: with HSP filters their verdicts (ext_filter_kernel) and the
+// cut against the best match that PASSED (a filtered match is a placeholder of score 0: it sorts last and drops out); then one
+// stable device-wide sort of the walked list by (query, 0xffffffff - score) -- the list is in load order, ascending target, so
+// that is Match::cmp_score order -- and the records written through that permutation; ctr->n_records of them.
+hipError_t launch_ext_top_append(const ExtArgs& a, uint32_t n_items, bool kept, int64_t rel, bool last, hipStream_t st);
+hipError_t launch_ext_top_records(const ExtArgs& a, uint32_t n_walked, hipStream_t st);
 
 // the host's (e-value, bit score) pairs into the records where they lie in HBM; records of a context gathered for a join with
 // their block-local target ids turned into database-wide ordinals

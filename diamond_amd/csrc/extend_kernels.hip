@@ -18,6 +18,10 @@
 //                        the list the trace walk runs over (launched behind every iteration, used when no query is left ranking)
 //   (traceback_kernel, swipe_kernels.hip)
 //   ext_records_kernel   one wavefront per query: its match records in output order
+//   --top (top_core.h): ext_top_append_kernel / ext_top_final_kernel in the place of ext_append_kernel / ext_final_kernel -- cuts by a
+//                        threshold against the best bit score, wavefront reductions over the query's aligned flags, no LDS list;
+//                        behind the walk ext_filter_kernel + ext_top_ffinal_kernel (with HSP filters), ext_top_keys_kernel, one
+//                        rocPRIM radix sort by (query, 0xffffffff - score), ext_top_records_kernel
 // Compiled with -ffp-contract=off like plan_kernels.hip (the e-value below follows evalue.h operation by operation).
 #include <hip/hip_runtime.h>
 #include <cfloat>
@@ -92,7 +96,8 @@ __global__ __launch_bounds__(64) void ext_mark_kernel(ExtArgs a)
 	const int qlen = (int)(a.qlimits[query + 1] - a.qlimits[query] - 1);
 	// more groups than a chunk: ranked in chunks (extend.cpp:289-336). A first chunk smaller than -k would grow by the e-value of
 	// the seed-hit scores (extend.cpp:262-268): those queries stay on the host
-	bool bad = ng > EXT_MAX_GROUPS || qlen <= 0 || (ng > a.chunk_size && (uint32_t)a.k > a.chunk_size);
+	// (--top: the chunk is 128 x block_mult whatever -k is, and the growth rule does not apply)
+	bool bad = ng > EXT_MAX_GROUPS || qlen <= 0 || (!a.top_on && ng > a.chunk_size && (uint32_t)a.k > a.chunk_size);
 	if (!bad)
 		for (uint32_t g = g0 + lane; g < g1; g += 64) {
 			const PlanGroup grp = a.groups[g];
@@ -114,6 +119,7 @@ __global__ __launch_bounds__(64) void ext_mark_kernel(ExtArgs a)
 		a.oidx[g] = g;
 		a.aligned[g] = 0; a.g_cnt[g] = 0; a.g_first[g] = 0;
 		if (a.filt_on) { a.fverdict[g] = EXT_F_PASS; a.matched[g] = 0; }
+		if (a.top_on) a.cand_score[g] = 0;
 	}
 	if (lane == 0) {
 		a.qstate[q] = ok ? EXT_Q_DEVICE : EXT_Q_HOST;
@@ -765,6 +771,222 @@ __global__ __launch_bounds__(64) void ext_ffinal_kernel(ExtArgs a)
 	else if (lane == 0 && a.q_removed[q]) atomicAdd(&a.ctr->n_filtered, a.q_removed[q]);
 }
 
+// ---- --top (a.top_on): culling by score against a threshold, top_core.h ----
+
+__device__ inline int wave_max(int v) { for (int off = 32; off >= 1; off >>= 1) { const int o = __shfl_xor(v, off); v = o > v ? o : v; } return v; }
+__device__ inline int wave_min(int v) { for (int off = 32; off >= 1; off >>= 1) { const int o = __shfl_xor(v, off); v = o < v ? o : v; } return v; }
+__device__ inline uint32_t wave_sum(uint32_t v) { for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off); return v; }
+
+// the query goes back to the host: nothing of it stays here
+__device__ inline void ext_top_hand_back(const ExtArgs& a, uint32_t q, uint32_t g0, uint32_t ng, uint32_t lane, uint8_t state)
+{
+	for (uint32_t gi = lane; gi < ng; gi += 64) { a.aligned[g0 + gi] = 0; a.kept[g0 + gi] = 0; }
+	if (lane == 0) { a.qstate[q] = state; a.q_active[q] = 0; }
+}
+
+// One ranking-chunk iteration of a query under --top behind its sweeps (one wavefront per query): the chunk's targets with a reported
+// HSP (V), append_hits with culling (culling.cpp:115-145 with config.toppercent): the aligned targets A are cut to those whose bit
+// score reaches max((1 - top/100) x bits(best of A), 1.0), V joins them if A is empty or V's best score reaches
+// (int)((1 - top/100) x lowest score left in A), and that same condition is new_hits; then the next window and the tail rule as
+// ext_append_kernel. A and its cut are two reductions over the query's `aligned` flags and scores in HBM (both loaded for every group,
+// so a pass is one round trip per 64 groups): no list, no limit on |A|. Indices: groups g0 + gi < g1 <= n_groups, the per-group arrays'
+// size; the window [i0, i1) lies inside [0, ng).
+__global__ __launch_bounds__(64) void ext_top_append_kernel(ExtArgs a, int last)
+{
+	const uint32_t q = blockIdx.x, lane = threadIdx.x;
+	if (!a.q_active[q]) return;
+	const uint32_t g0 = a.queries[q].group_begin, g1 = a.queries[q + 1].group_begin, ng = g1 - g0;
+	const uint32_t i0 = a.q_i0[q], i1 = a.q_i1[q];
+	const uint32_t query = a.queries[q].query;
+	const int qlen = (int)(a.qlimits[query + 1] - a.qlimits[query] - 1);
+	bool amb = false, sat = false;
+	int max_v = 0;
+	for (uint32_t w = i0 + lane; w < i1; w += 64) {
+		const uint32_t g = a.gorder[g0 + w], n = a.g_cnt[g], first = a.g_first[g];
+		const uint32_t target = a.groups[g].target;
+		const int tlen = (int)(a.tlimits[target + 1] - a.tlimits[target] - 1);
+		// best HSP of the target among its bands that pass the report cutoff, as ext_append_kernel
+		bool have = false;
+		int best = 0; uint32_t bi = 0; double bev = 0;
+		for (uint32_t k = 0; k < n; ++k) {
+			const SwipeEnd e = a.ends[first + k];
+			if (e.pad[0]) sat = true;
+			if (e.score <= 0) continue;
+			const double ev = ext_evalue(a.ev, e.score, qlen, tlen);
+			if (!ext_reported(a, e.score, ev, amb)) continue;
+			if (!have || e.score > best || (e.score == best && a.items[first + k].d_begin < a.items[bi].d_begin)) { have = true; best = e.score; bi = first + k; bev = ev; }
+		}
+		a.cand_item[g] = bi;
+		a.cand_ev[g] = bev;
+		a.cand_score[g] = have ? best : 0;
+		max_v = best > max_v ? best : max_v;
+	}
+	max_v = wave_max(max_v);
+	bool new_hits = false;
+	if (max_v > 0) {
+		// (the scores read below are those of earlier chunks -- earlier launches --: the window's targets are not aligned yet)
+		int max_a = 0;
+		for (uint32_t gi = lane; gi < ng; gi += 64) {
+			const uint8_t al = a.aligned[g0 + gi];
+			const int s = a.cand_score[g0 + gi];
+			if (al && s > max_a) max_a = s;
+		}
+		max_a = wave_max(max_a);
+		int min_a = 0x7fffffff;
+		if (max_a > 0)
+			for (uint32_t gi = lane; gi < ng; gi += 64) {
+				const uint8_t al = a.aligned[g0 + gi];
+				const int s = a.cand_score[g0 + gi];
+				if (!al) continue;
+				if (top_near(a.top, s, max_a)) amb = true;
+				if (top_pass(a.top, s, max_a)) min_a = s < min_a ? s : min_a;
+				else a.aligned[g0 + gi] = 0;
+			}
+		min_a = wave_min(min_a);
+		new_hits = min_a == 0x7fffffff || top_append(a.top, max_v, min_a);      // (nothing aligned, or nothing left of it)
+		if (new_hits)
+			for (uint32_t w = i0 + lane; w < i1; w += 64) {
+				const uint32_t g = a.gorder[g0 + w];
+				if (a.cand_score[g] > 0) a.aligned[g] = 1;               // (written by this lane above)
+			}
+	}
+	const bool any_amb = __ballot(amb) != 0, any_sat = __ballot(sat) != 0;
+	if (any_amb || any_sat) {
+		ext_top_hand_back(a, q, g0, ng, lane, EXT_Q_AMBIGUOUS);
+		if (lane == 0) { if (any_amb) atomicAdd(&a.ctr->n_ambiguous, 1u); if (any_sat) atomicAdd(&a.ctr->n_saturated, 1u); }
+		return;
+	}
+	// the next window and whether the ranking goes on (extend.cpp:325-336; uniform over the wavefront)
+	const uint32_t n0 = i1, n1 = i1 + (a.chunk_size < ng - i1 ? a.chunk_size : ng - i1);
+	const int prev = a.q_tail[q];
+	const int next_tail = (int)a.groups[a.gorder[g0 + n1 - 1]].score;
+	const bool terminate = !new_hits && (prev == 0 || (double)next_tail / (double)prev <= 0.95 || ext_bitscore(a.ev, next_tail) < 25.0);
+	const bool go_on = n0 < ng && !terminate;
+	if (go_on && last) {
+		ext_top_hand_back(a, q, g0, ng, lane, EXT_Q_CAPPED);
+		if (lane == 0) atomicAdd(&a.ctr->n_capped, 1u);
+		return;
+	}
+	if (lane == 0) {
+		a.q_prev[q] = prev;
+		if (new_hits) a.q_tail[q] = next_tail;
+		a.q_i0[q] = n0; a.q_i1[q] = n1;
+		a.q_active[q] = go_on ? 1 : 0;
+		if (go_on) atomicAdd(&a.ctr->n_active, 1u);
+	}
+}
+
+// culling(aligned_targets) once the ranking is over (extend.cpp:331) under --top: the same cut once more; what it leaves is walked.
+// Every group of the query gets its `kept` flag (ext_window_kernel cleared them for this iteration).
+__global__ __launch_bounds__(64) void ext_top_final_kernel(ExtArgs a)
+{
+	const uint32_t q = blockIdx.x, lane = threadIdx.x;
+	if (a.qstate[q] != EXT_Q_DEVICE || a.q_active[q]) return;
+	const uint32_t g0 = a.queries[q].group_begin, g1 = a.queries[q + 1].group_begin, ng = g1 - g0;
+	int max_a = 0;
+	for (uint32_t gi = lane; gi < ng; gi += 64) {
+		const uint8_t al = a.aligned[g0 + gi];
+		const int s = a.cand_score[g0 + gi];
+		if (al && s > max_a) max_a = s;
+	}
+	max_a = wave_max(max_a);
+	bool amb = false;
+	for (uint32_t gi = lane; gi < ng; gi += 64) {
+		const uint8_t al = a.aligned[g0 + gi];
+		const int s = a.cand_score[g0 + gi];
+		bool keep = false;
+		if (al) { if (top_near(a.top, s, max_a)) amb = true; keep = top_pass(a.top, s, max_a); }
+		a.kept[g0 + gi] = keep ? 1u : 0u;
+	}
+	if (__ballot(amb) != 0) {
+		ext_top_hand_back(a, q, g0, ng, lane, EXT_Q_AMBIGUOUS);
+		if (lane == 0) atomicAdd(&a.ctr->n_ambiguous, 1u);
+	}
+}
+
+// --top with HSP filters, behind the walk of the survivors and ext_filter_kernel (gapped_final.cpp:103-154, culling.cpp:199-202):
+// a match that a filter removed stays as a placeholder of score 0, the matches are cut against the best one that passed -- none
+// passed: none is reported. A value on a filter threshold hands the query back; so does a cutoff so low that the placeholders
+// themselves would pass it (bits(0) against max(f x bits(best), 1.0): --top near 100 only).
+__global__ __launch_bounds__(64) void ext_top_ffinal_kernel(ExtArgs a)
+{
+	const uint32_t q = blockIdx.x, lane = threadIdx.x;
+	if (a.qstate[q] != EXT_Q_DEVICE) return;
+	const uint32_t g0 = a.queries[q].group_begin, g1 = a.queries[q + 1].group_begin, ng = g1 - g0;
+	int best = 0;
+	uint32_t n_fail = 0;
+	bool thr = false;
+	for (uint32_t gi = lane; gi < ng; gi += 64) {
+		const uint32_t kp = a.kept[g0 + gi];
+		const uint8_t v = a.fverdict[g0 + gi];
+		const int s = a.cand_score[g0 + gi];
+		if (!kp) continue;
+		thr |= v == EXT_F_THRESHOLD;
+		n_fail += v == EXT_F_FAIL ? 1u : 0u;
+		if (v == EXT_F_PASS && s > best) best = s;
+	}
+	best = wave_max(best);
+	n_fail = wave_sum(n_fail);
+	if (__ballot(thr) != 0) {
+		ext_top_hand_back(a, q, g0, ng, lane, EXT_Q_AMBIGUOUS);
+		if (lane == 0) atomicAdd(&a.ctr->n_threshold, 1u);
+		return;
+	}
+	bool amb = n_fail > 0 && best > 0 && (top_pass(a.top, 0, best) || top_near(a.top, 0, best));
+	for (uint32_t gi = lane; gi < ng; gi += 64) {
+		const uint32_t kp = a.kept[g0 + gi];
+		const uint8_t v = a.fverdict[g0 + gi];
+		const int s = a.cand_score[g0 + gi];
+		if (!kp) continue;
+		bool keep = false;
+		if (v == EXT_F_PASS && best > 0) { if (top_near(a.top, s, best)) amb = true; keep = top_pass(a.top, s, best); }
+		a.kept[g0 + gi] = keep ? 1u : 0u;
+	}
+	if (__ballot(amb) != 0) {
+		ext_top_hand_back(a, q, g0, ng, lane, EXT_Q_AMBIGUOUS);
+		if (lane == 0) atomicAdd(&a.ctr->n_ambiguous, 1u);
+	}
+	else if (lane == 0 && n_fail) atomicAdd(&a.ctr->n_filtered, n_fail);
+}
+
+// Record order under --top: a sort key per entry of the walked list (n <= r2_cap = n_groups entries, the size of okeys / oidx):
+// (query, 0xffffffff - score) for an entry that is a record, all ones -- behind every record -- for one that is none (filtered, cut,
+// or its query handed back). The list is in load order, so a stable sort by this key is Match::cmp_score order inside a query.
+__global__ __launch_bounds__(256) void ext_top_keys_kernel(ExtArgs a, uint32_t n)
+{
+	const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+	bool rec = false;
+	if (k < n) {
+		const uint32_t g = a.r2_group[k];
+		rec = a.kept[g] != 0;
+		const uint32_t query = a.hits[a.groups[g].hit_begin].query;
+		a.okeys[k] = rec ? ((uint64_t)query << 32) | (uint64_t)(0xffffffffu - (uint32_t)a.cand_score[g]) : ~(uint64_t)0;
+		a.oidx[k] = k;
+	}
+	const unsigned long long m = __ballot(rec);
+	if ((threadIdx.x & 63) == 0 && m) atomicAdd(&a.ctr->n_records, (uint32_t)__popcll(m));
+}
+
+// ... and the records through the sorted permutation: record i < ctr->n_records <= n <= r2_cap, the size of `records` under --top
+__global__ __launch_bounds__(256) void ext_top_records_kernel(ExtArgs a, uint32_t n)
+{
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n || i >= a.ctr->n_records) return;
+	const uint32_t g = a.r2_group[a.rperm[i]], item = a.cand_item[g];
+	const PlanGroup grp = a.groups[g];
+	const dmnd_dp_target d = a.items[item];
+	dmnd_match& m = a.records[i];                            // (field by field into HBM: a local record would live in scratch memory)
+	m.query = a.hits[grp.hit_begin].query; m.target = grp.target;
+	m.ungapped_score = (int32_t)grp.score; m.d_begin = d.d_begin; m.d_end = d.d_end;
+	m.frame = 0; m.read_begin = 0; m.read_end = 0;
+	m.evalue = a.cand_ev[g]; m.bit_score = 0.0;               // the host writes its own e-value and the bit score
+	const dmnd_hsp hsp = a.hsps[item];
+	m.hsp.score = hsp.score; m.hsp.q_begin = hsp.q_begin; m.hsp.q_end = hsp.q_end; m.hsp.s_begin = hsp.s_begin; m.hsp.s_end = hsp.s_end;
+	m.hsp.length = hsp.length; m.hsp.identities = hsp.identities; m.hsp.mismatches = hsp.mismatches; m.hsp.positives = hsp.positives;
+	m.hsp.gap_openings = hsp.gap_openings; m.hsp.gaps = hsp.gaps; m.hsp.transcript_len = hsp.transcript_len;
+	m.hsp.transcript_off = -1;
+}
+
 hipError_t ensure_tmp(void** tmp, size_t* have, size_t need)
 {
 	if (need <= *have) return hipSuccess;
@@ -962,6 +1184,38 @@ hipError_t launch_ext_records(const ExtArgs& a, uint32_t n_kept, hipStream_t st)
 {
 	if (n_kept == 0) return hipSuccess;
 	hipLaunchKernelGGL(ext_records_kernel, dim3(a.n_queries), dim3(64), (size_t)a.k * sizeof(SelSlot), st, a);
+	return hipGetLastError();
+}
+
+hipError_t launch_ext_top_append(const ExtArgs& a, uint32_t n_items, bool kept, int64_t rel, bool last, hipStream_t st)
+{
+	if (n_items > 0 && (!kept || rel != 0)) hipLaunchKernelGGL(ext_rebase_kernel, dim3((n_items + 255) / 256), dim3(256), 0, st, a, n_items, rel, kept ? 1 : 0);
+	hipLaunchKernelGGL(ext_top_append_kernel, dim3(a.n_queries), dim3(64), 0, st, a, last ? 1 : 0);
+	// speculatively (the host only uses it when no query is left ranking): the last cut, the list the walk runs over
+	hipLaunchKernelGGL(ext_top_final_kernel, dim3(a.n_queries), dim3(64), 0, st, a);
+	return list_kept(a, st);
+}
+
+hipError_t launch_ext_top_records(const ExtArgs& a, uint32_t n_walked, hipStream_t st)
+{
+	hipError_t e = hipMemsetAsync(&a.ctr->n_records, 0, sizeof(uint32_t), st);
+	if (e != hipSuccess) return e;
+	if (n_walked == 0) return hipSuccess;
+	if (n_walked > a.r2_cap) return hipErrorInvalidValue;
+	if (filters_on(a.filt)) {
+		hipLaunchKernelGGL(ext_filter_kernel, dim3((n_walked + 255) / 256), dim3(256), 0, st, a, n_walked);
+		hipLaunchKernelGGL(ext_top_ffinal_kernel, dim3(a.n_queries), dim3(64), 0, st, a);
+	}
+	size_t need = 0;
+	e = rocprim::radix_sort_pairs(nullptr, need, a.okeys, a.okeys_sorted, a.oidx, a.rperm, (size_t)n_walked, 0, 64, st);
+	if (e != hipSuccess) return e;
+	e = ensure_tmp(a.scan_tmp, a.scan_tmp_bytes, need);
+	if (e != hipSuccess) return e;
+	const unsigned blocks = (n_walked + 255) / 256;
+	hipLaunchKernelGGL(ext_top_keys_kernel, dim3(blocks), dim3(256), 0, st, a, n_walked);
+	e = rocprim::radix_sort_pairs(*a.scan_tmp, need, a.okeys, a.okeys_sorted, a.oidx, a.rperm, (size_t)n_walked, 0, 64, st);
+	if (e != hipSuccess) return e;
+	hipLaunchKernelGGL(ext_top_records_kernel, dim3(blocks), dim3(256), 0, st, a, n_walked);
 	return hipGetLastError();
 }
 

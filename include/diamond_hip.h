@@ -323,7 +323,10 @@ int dmnd_extend_plan(const dmnd_params* params, const int8_t* qdata, const int64
 	const int8_t* tdata, const int64_t* tlimits, int64_t nt, const dmnd_seed_hit* hits, int64_t n_hits, int threads, int query_contexts,
 	int8_t* cbs_out, dmnd_plan_target* out, int64_t cap, int64_t* n_out);
 /* Whole extension stage on the uploaded blocks (qdata/tdata: the caller's host copies of the same blocks). hits must be
- * sorted by query. Matches come out ordered by query, then as the reference orders them (e-value, score, target).
+ * sorted by query. Matches come out ordered by query, then as the reference orders them (e-value, score, target; under
+ * dmnd_set_top_percent score, target). The default search of a protein query block -- one HSP per target, -k or --top culling,
+ * Hauser bias or none, with or without the HSP filters, no transcripts -- is extended in HBM (dmnd_extend_device_stats); the queries
+ * the device half hands back, and every other mode, take the host path. The records are the same either way.
  * transcript may be NULL (then dmnd_hsp::transcript_off = -1). Blastp defaults: max_target_seqs 25, max_hsps 1.
  * threads bounds the host threads: blocks with >= 2048 queries run as up to 8 runners (own HIP stream each), worker threads
  * under a runner only when its share of the seed hits is large. Without transcripts round 1 keeps its trace rows in HBM and
@@ -620,8 +623,7 @@ typedef struct {
 } dmnd_plan_device_info;
 int dmnd_extend_plan_device(dmnd_ctx* ctx, const dmnd_seed_hit* hits, int64_t n_hits, dmnd_plan_target* rows, int64_t row_cap,
 	dmnd_plan_group* groups, int64_t group_cap, dmnd_plan_device_info* info);
-/* Round 6: for the queries whose targets fit one ranking chunk (src/align/extend.cpp:79-92) the rest of the extension stage runs in
- * HBM as well -- DpTargets and their launch order from the bands (DP::BandedSwipe::bin, src/dp/swipe/swipe_wrapper.cpp:75-102), best
+/* Round 6: the rest of the extension stage runs in HBM as well, ranking chunk by ranking chunk (src/align/extend.cpp:79-92, 289-336) -- DpTargets and their launch order from the bands (DP::BandedSwipe::bin, src/dp/swipe/swipe_wrapper.cpp:75-102), best
  * HSP per target and report cutoff (src/align/gapped_score.cpp:182-268), culling (src/align/culling.cpp:97-113,189-203), round 2 as a
  * walk of the kept traces (src/align/gapped_final.cpp:66-160), match records in output order (src/align/extend.h:51-56). The host
  * writes its own e-value and bit score into the records. Of the last dmnd_extend: [0] queries extended that way, [1] of them handed
@@ -629,13 +631,17 @@ int dmnd_extend_plan_device(dmnd_ctx* ctx, const dmnd_seed_hit* hits, int64_t n_
  * the device takes), [2] round-1 DpTargets,
  * [3] records, [4] sum over the round-1 DpTargets of band diagonals x anti-diagonal steps and [5] of the 128 P diagonals their wavefront
  * holds x steps ([4] / [5] = lane use of the sweeps), [6] DP cells of the device half's round-2 targets, [7] of those swept again in
- * round 2 (their round-1 sweep kept no trace rows), [8] device ms of those sweeps, [9] of [1] the queries still ranking after the last chunk; all 0 = every query took the host path (other modes: --max-hsps != 1, --top,
+ * round 2 (their round-1 sweep kept no trace rows), [8] device ms of those sweeps, [9] of [1] the queries still ranking after the last chunk; all 0 = every query took the host path (other modes: --max-hsps != 1,
  * --no-self-hits, matrix adjustment, --ext full, transcripts wanted, translated queries). Under the filters of dmnd_set_filters /
- * dmnd_set_approx_id [1] also counts the queries of dmnd_extend_filter_stats [1]. */
+ * dmnd_set_approx_id [1] also counts the queries of dmnd_extend_filter_stats [1]. Under dmnd_set_top_percent the culling is the
+ * reference's --top culling (src/align/culling.cpp:92-144, src/basic/config.h:428-454): cuts by a threshold against the best bit
+ * score, a chunk appended by an integer comparison of scores, no limit on the aligned targets of a query but the groups; [1] then
+ * counts a query with a score within 1e-9 relative of the --top cutoff with the ambiguous ones, and [3] may exceed -k per query. */
 int dmnd_extend_device_stats(const dmnd_ctx* ctx, double out[10]);
 /* The device half under the filters of dmnd_set_filters / dmnd_set_approx_id (it applies them in HBM: every target of a ranking chunk
  * that passes the report cutoff is walked before the culling, a filter kernel reads the walk's statistics, and a target that fails
- * takes none of the -k places). Of the last dmnd_extend: [0] records a filter removed on the device (of the queries it finished),
+ * takes none of the -k places; under --top the survivors of the last cut are walked once, and the matches that passed are cut
+ * against the best of them). Of the last dmnd_extend: [0] records a filter removed on the device (of the queries it finished),
  * [1] queries handed back to the host path because a filter value lay on its threshold (within 1e-9 relative; counted in
  * dmnd_extend_device_stats [1] as well). Both 0 without filters or when every query took the host path. */
 int dmnd_extend_filter_stats(const dmnd_ctx* ctx, double out[2]);

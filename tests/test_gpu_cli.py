@@ -1130,6 +1130,32 @@ def test_cli_frameshift_matches_reference(tmp_path):
             assert r.returncode != 0 and msg in r.stderr + r.stdout, (binary, cmd)
 
 
+def test_cli_frameshift_small_trace_budget_and_other_matrix(tmp_path):
+    """blastx -F 15 with the three-frame sweep's trace budget at its minimum (DMND_TRACE_ARENA_MB=8: the traceback calls of a query
+    block may be cut into chunks) gives the committed golden byte for byte -- parity only, the CLI shows no chunk count:
+    tests/test_gpu_frameshift_edges.py proves the cut --, and -F 15 under BLOSUM45 14/2 equals the reference binary on the synthetic
+    reads of test_cli_frameshift_matches_reference."""
+    g = os.path.join(ROOT, "tests", "golden")
+    r = subprocess.run([CLI, "blastx", "-q", os.path.join(g, "fs_reads.fna"), "-d", os.path.join(g, "fs_db.faa"), "-p", "4", "-F", "15", "-o", str(tmp_path / "hip.out")],
+                       capture_output=True, text=True, timeout=600, env=dict(os.environ, DMND_TRACE_ARENA_MB="8"))
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert open(tmp_path / "hip.out").read() == open(os.path.join(g, "fs_f15.tsv")).read()
+    if not os.path.exists(REF):
+        pytest.fail("oracle/_ref/diamond is missing: under -m gpu the reference binary is the checker, its absence is a failure (__graft_entry__.build() makes it where the reference's sources are present)")
+    db, doff, q, qoff = synth.generate(150, members=8, queries=220, seed=81)
+    synth.write_fasta(str(tmp_path / "db.faa"), "t", db, doff)
+    dna, off = synth.back_translate(q, qoff, seed=82)
+    synth.write_dna_fasta(str(tmp_path / "reads.fna"), "r", *synth.indel_reads(dna, off, seed=83, deletion=0.004, insertion=0.004))
+    args = ["blastx", "-q", str(tmp_path / "reads.fna"), "-d", str(tmp_path / "db.faa"), "-p", "4", "-F", "15", "--matrix", "BLOSUM45", "--gapopen", "14", "--gapextend", "2"]
+    _run([REF] + args + ["-o", str(tmp_path / "ref.out")])
+    _run([CLI] + args + ["-o", str(tmp_path / "hip.out")])
+    ref, got = open(tmp_path / "ref.out").read(), open(tmp_path / "hip.out").read()
+    assert len(ref) > 1000
+    if got != ref:
+        a, b = set(ref.splitlines()), set(got.splitlines())
+        raise AssertionError("%d lines only in the reference's output, %d only in ours; e.g. %s | %s" % (len(a - b), len(b - a), sorted(a - b)[:2], sorted(b - a)[:2]))
+
+
 def test_cli_frameshift_blocked_range_culling_matches_reference(tmp_path):
     """blastx -F with a database of several reference blocks (round 5, dmnd_join_blocks_range): the join of the per-block records
     uses the culler TargetCulling::get picks -- RangeCulling with --range-culling / --long-reads (a target is kept unless the part

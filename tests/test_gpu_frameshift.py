@@ -1,7 +1,13 @@
 """-m gpu parity tests of the three-frame banded sweep kernels (frameshift alignment, blastx -F) through the C ABI
 (dmnd_frameshift_swipe): the reference's own calls (tests/golden/f3_*.tap, tapped at banded_3frame_swipe, src/dp/dp.h:296) --
 score-only with its 16-channel vector batches, traceback with read coordinates, statistics and transcripts incl. the frameshift
-operations -- and random items against the oracle."""
+operations -- and random items against the oracle. These run one launch per call, BLOSUM62 11/1, letters 0-20, reads of at least
+four codons, scores far below 65535. tests/test_gpu_frameshift_edges.py covers the rest of the entry with items from
+tests/test_frameshift.py: the chunk loop of run_launch (traceback calls cut by a 4 MiB trace budget, with chunk ends on and off
+wavefront boundaries; score-only calls cut at 1 GiB of interleaved state), the saturation at 65535 and the re-run of such an item
+on its own band, letters 0-25 under four matrices / gap penalties and three frameshift penalties, reads of 3-14 nucleotides against
+targets of 1-4 letters on every band, and every refusal of the entry followed by a valid call. Not covered: the 4 Mi-item chunk
+limit, letters with the soft-mask bit (the reference's sweep does not mask them either)."""
 import os
 import numpy as np
 import pytest

@@ -338,6 +338,7 @@ extern "C" void dmnd_destroy(dmnd_ctx* c)
 	c->plan_dev.release(); c->plan_host.release();
 	c->ext_dev.release(); c->ext_trace.release(); c->ext_host.release(); c->ext_ev.release();
 	for (DevBuf& b : c->ext_trace_more) b.release();
+	c->ext_tr.release(); c->ext_tr_raw.release(); c->ext_tr_store.release(); c->ext_tr_out.release();
 	if (c->plan_tmp) { (void)hipFree(c->plan_tmp); c->plan_tmp = nullptr; c->plan_tmp_bytes = 0; }
 	for (int i = 0; i < 2; ++i) { c->up_stage[i].release(); if (c->up_ev[i]) (void)hipEventDestroy(c->up_ev[i]); c->up_ev[i] = nullptr; }
 	for (int i = 0; i < 2; ++i) { c->t_stage[i].release(); if (c->t_ev[i]) (void)hipEventDestroy(c->t_ev[i]); c->t_ev[i] = nullptr; }

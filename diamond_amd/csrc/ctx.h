@@ -107,6 +107,7 @@ struct dmnd_ctx {
 	void* plan_tmp = nullptr; size_t plan_tmp_bytes = 0;      // rocPRIM scan scratch of the planner
 	dmnd::DevBuf ext_dev, ext_trace;          // device half of dmnd_extend behind the planner (extend_kernels.hip): work arrays, kept traces
 	std::vector<dmnd::DevBuf> ext_trace_more; // ... the kept traces of the ranking chunks behind the first
+	dmnd::DevBuf ext_tr, ext_tr_raw, ext_tr_store, ext_tr_out;      // ... with a transcript arena: the transcript arrays (extend_core.h tr_layout), the raw slots of one walked piece, the store of the kept transcripts, the gathered output
 	dmnd::DevBuf ext_ev;                      // the host's (e-value, bit score) pairs on their way into the device copy of the records
 	const dmnd_match* ext_records_dev = nullptr; int64_t ext_records_n = -1;      // the records of the last dmnd_extend where they lie in HBM (complete: host e-values in); n = -1: part of them only exists on the host
 	dmnd::PinBuf ext_host;                    // ... its counters, records and query states on the host

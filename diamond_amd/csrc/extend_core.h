@@ -1,7 +1,7 @@
 // extend_core.h -- the HIP-free part of the device half of the extension stage (extend_kernels.h): its constants, its counters and
 // the layout of its work arrays in one buffer (extend_on_device, extend_device.hip). Plain C++, so that the CPU tests
 // (tests/emu/extend_layout_emu.cpp) check the same numbers the launchers use: every array, and every extent the device half clears,
-// inside its region of the buffer.
+// inside its region of the buffer. The arrays of a call that returns transcripts have a layout of their own (tr_layout, below).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -110,6 +110,55 @@ inline int ext_regions(const ExtLayout& L, ExtRegion* r)
 	add("r2_tr", L.o_r2_tr, L.r2_tr_clear * 8);                   // (launch_ext_begin's clear)
 	add("r2_group", L.o_r2_group, nS * 4); add("records", L.o_records, nR * sizeof(dmnd_match));
 	add("ctr", L.o_ctr, sizeof(ExtCounters));                     // (launch_ext_begin's clear, reset_iteration's)
+	return n;
+}
+
+// ---- transcripts (a call with a transcript arena; transcript_core.h) ----
+// The arrays between the trace walk and the caller's arena live in a buffer of their own, laid out here the same way: nG groups,
+// nS = the capacity of the walked list, nR = the capacity of the records (ExtLayout::nS, nR of the same call).
+struct TrCounters {
+	uint32_t n_pieces;                       // of the current walk: its pieces (tr_piece_end), their bounds in `pieces`
+	uint32_t missing;                        // != 0: the gather step met a record whose group has no transcript in the store (the call fails)
+	long long raw_total, raw_max;            // ... raw-slot bytes of the whole list and of its largest piece
+	long long pad2[5];
+};
+
+struct TrLayout {
+	size_t nG, nS, nR;
+	size_t o_g_store;       // per group: where its transcript lies in the store (valid once its chunk has been walked)
+	size_t o_k_len, o_k_off;        // (+ 1) per entry of the current piece: slot widths before the walk, kept lengths behind it / their scan
+	size_t o_r_len, o_r_off;        // (+ 1) per record: bytes in the output / their scan = the records' transcript offsets
+	size_t o_pieces;        // (+ 1) first entry of each piece of the current walk
+	size_t o_ctr;
+	size_t bytes;
+};
+
+inline TrLayout tr_layout(size_t nG, size_t nS, size_t nR)
+{
+	TrLayout T;
+	T.nG = nG; T.nS = nS; T.nR = nR;
+	size_t at = 0;
+	auto take = [&](size_t bytes) { const size_t o = at; at = (at + bytes + 63) & ~(size_t)63; return o; };
+	T.o_g_store = take(nG * 8);
+	T.o_k_len = take((nS + 1) * 8); T.o_k_off = take((nS + 1) * 8);
+	T.o_r_len = take((nR + 1) * 8); T.o_r_off = take((nR + 1) * 8);
+	T.o_pieces = take((nS + 1) * 4);
+	T.o_ctr = take(sizeof(TrCounters));
+	T.bytes = at;
+	return T;
+}
+
+enum { TR_REGIONS = 7 };
+
+inline int tr_regions(const TrLayout& T, ExtRegion* r)
+{
+	int n = 0;
+	auto add = [&](const char* name, size_t off, size_t used) { r[n++] = ExtRegion{ name, off, used }; };
+	add("g_store", T.o_g_store, T.nG * 8);
+	add("k_len", T.o_k_len, (T.nS + 1) * 8); add("k_off", T.o_k_off, (T.nS + 1) * 8);      // (the scans: entries + 1)
+	add("r_len", T.o_r_len, (T.nR + 1) * 8); add("r_off", T.o_r_off, (T.nR + 1) * 8);
+	add("pieces", T.o_pieces, (T.nS + 1) * 4);                                              // (a piece has at least one entry)
+	add("tr_ctr", T.o_ctr, sizeof(TrCounters));
 	return n;
 }
 

@@ -43,6 +43,11 @@ int plan_fetch_lists(dmnd_ctx* c, DevPlan& plan);
 // The extension of the planned queries in HBM, from the planner's bands to the match records (extend_kernels.h). records: those
 // queries' matches in output order with the HOST's e-value and bit score; qstate[k] (k = index into plan.queries): EXT_Q_DEVICE =
 // done here, anything else = the host path has to extend the query. done = false: nothing was done here, every query goes to the host path.
-int extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan, int threads, std::vector<dmnd_match>& records, std::vector<uint8_t>& qstate, bool& done);
+// transcript != NULL: the caller's transcript arena of transcript_cap bytes. The records' packed transcripts (transcript_len bytes
+// and a 0 terminator each) are written to it from offset 0 on in record order, hsp.transcript_off of each record points at its own,
+// *transcript_used = their bytes; more than transcript_cap: DMND_E_CAP, nothing written. The records then do not stay in HBM for a
+// join (c->ext_records_dev stays NULL). transcript == NULL: no transcripts, hsp.transcript_off = -1.
+int extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan, int threads, std::vector<dmnd_match>& records, std::vector<uint8_t>& qstate, bool& done,
+	uint8_t* transcript = nullptr, int64_t transcript_cap = 0, int64_t* transcript_used = nullptr);
 
 }  // namespace dmnd

@@ -4,6 +4,8 @@
 // (extend_kernels.hip: /root/reference/src/align/extend.cpp:289-336, gapped_score.cpp:182-268, culling.cpp:97-113, gapped_final.cpp:66-160)
 // -- per iteration one counter read-back, the sweeps of its band classes (api.hip dmnd_sweep_classes), append_hits on the device --
 // then round 2, the records, the host's own e-value and bit score written back into the records where they stay for the join.
+// A call with a transcript arena walks each list in pieces, keeps every piece's packed transcripts in a dense store and gathers the
+// records' transcripts into the arena once the records exist (extend_kernels.h TrArgs, transcript_core.h).
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -56,6 +58,39 @@ int ext_max_chunks()
 	const char* e = std::getenv("DMND_EXTEND_MAX_CHUNKS");
 	return e ? std::max(1, std::min(atoi(e), (int)EXT_MAX_ITERATIONS)) : (int)EXT_MAX_ITERATIONS;
 }
+
+// DMND_EXTEND_PIECE_KB (a capacity knob, read per call): with a transcript arena a walked list is walked in consecutive pieces whose
+// raw transcript slots (query + target + 2 bytes per entry) come to at most this many KB -- at least one entry per piece; each
+// piece's transcripts are kept in the dense store before the next piece is walked. Default 256 MB.
+int64_t tr_piece_bytes()
+{
+	const char* e = std::getenv("DMND_EXTEND_PIECE_KB");
+	return (e ? std::max<int64_t>(1, std::min<int64_t>(std::atoll(e), (int64_t)1 << 32)) : (int64_t)256 << 10) << 10;
+}
+
+// more room in a buffer whose first keep_bytes bytes stay (the store of the kept transcripts grows piece by piece)
+int grow_keeping(DevBuf& b, size_t need, size_t keep_bytes, hipStream_t st)
+{
+	if (need <= b.cap && b.own) return DMND_OK;
+	DevBuf nb;
+	if (int rc = nb.ensure(std::max(need, 2 * b.cap))) return rc;
+	if (keep_bytes > 0) {
+		const hipError_t e = copy_now(st, nb.p, b.p, keep_bytes, hipMemcpyDeviceToDevice);
+		if (e != hipSuccess) { nb.release(); return fail(DMND_E_DEVICE, std::string("the store of the kept transcripts: ") + hipGetErrorString(e)); }
+	}
+	else HIP_TRY(sync_stream(st));                      // (no kernel of the stream still reads the old one)
+	b.release();
+	b = nb;
+	return DMND_OK;
+}
+
+// events of the transcript steps' kernel times (DMND_TRACE only)
+struct TrEvents {
+	hipEvent_t e[2] = { nullptr, nullptr };
+	bool on = false;
+	int init() { for (hipEvent_t& x : e) HIP_TRY(hipEventCreate(&x)); on = true; return DMND_OK; }
+	~TrEvents() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+};
 
 // DMND_PLAN_SMALL_HITS (a test hook, read per call): a call of at least this many hits chains its groups of up to four segments
 // with the small workspace first (the two-kernel form of plan_kernels.hip); 0 = every call
@@ -148,9 +183,11 @@ static bool keep_traces_dev() { static const bool v = [] { const char* e = std::
 // target) with the HOST's e-value and bit score; qstate[k] (k = index into plan.queries): EXT_Q_DEVICE = done here, anything else = the host path
 // has to extend the query. done = false: nothing was done here (no eligible query, or the kept traces would not fit the context's
 // trace budget), every query goes to the host path.
-int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan, int threads, std::vector<dmnd_match>& records, std::vector<uint8_t>& qstate, bool& done)
+int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan, int threads, std::vector<dmnd_match>& records, std::vector<uint8_t>& qstate, bool& done,
+	uint8_t* transcript, int64_t transcript_cap, int64_t* transcript_used)
 {
 	done = false;
+	if (transcript_used) *transcript_used = 0;
 	TraceLaps tr("dmnd_extend (device half)");
 	const int64_t chunk = h.ranking_chunk;
 	if (chunk > EXT_MAX_CHUNK || plan.n_bands == 0) return DMND_OK;
@@ -165,9 +202,30 @@ int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan,
 	if (int rc = c->ext_dev.ensure(L.bytes)) return rc;
 	Guard guard(c->ext_dev, L.bytes, c->stream);
 	if (int rc = guard.arm()) return rc;
+	// with a transcript arena: the arrays between the trace walk and the arena, in a buffer of their own (extend_core.h tr_layout)
+	const bool with_tr = transcript != nullptr;
+	const TrLayout T = tr_layout(L.nG, L.nS, nR);
+	if (with_tr) if (int rc = c->ext_tr.ensure(T.bytes)) return rc;
+	Guard guard_tr(c->ext_tr, T.bytes, c->stream);
+	if (with_tr) if (int rc = guard_tr.arm()) return rc;
+	TrArgs ta{};
+	if (with_tr) {
+		char* dt = c->ext_tr.as<char>();
+		ta.g_store = reinterpret_cast<int64_t*>(dt + T.o_g_store); ta.k_len = reinterpret_cast<int64_t*>(dt + T.o_k_len); ta.k_off = reinterpret_cast<int64_t*>(dt + T.o_k_off);
+		ta.r_len = reinterpret_cast<int64_t*>(dt + T.o_r_len); ta.r_off = reinterpret_cast<int64_t*>(dt + T.o_r_off);
+		ta.pieces = reinterpret_cast<uint32_t*>(dt + T.o_pieces); ta.ctr = reinterpret_cast<TrCounters*>(dt + T.o_ctr);
+		HIP_TRY(hipMemsetAsync(ta.g_store, 0xff, L.nG * sizeof(int64_t), c->stream));      // (-1: no transcript of the group in the store)
+		HIP_TRY(hipMemsetAsync(ta.ctr, 0, sizeof(TrCounters), c->stream));
+	}
+	const int64_t piece_limit = tr_piece_bytes();
+	size_t tr_pieces = 0, tr_raw = 0, tr_kept = 0, tr_gathered = 0;      // of the call: pieces walked, raw-slot bytes, bytes in the store, bytes in the arena
+	double ms_tr_walk = 0, ms_tr_keep = 0, ms_tr_gather = 0;
+	TrEvents tev;
+	if (with_tr && tr.on) if (int rc = tev.init()) return rc;
 	tr.lap("work arrays");
 	char* d = c->ext_dev.as<char>();
 	ExtArgs a;
+	a.tr_on = with_tr ? 1 : 0;
 	a.groups = plan.dev.groups; a.queries = plan.dev.queries; a.bands = plan.dev.bands;
 	a.n_groups = plan.n_groups; a.n_queries = plan.n_queries; a.n_bands = plan.n_bands;
 	a.hits = plan.dev.hits; a.qlimits = plan.dev.qlimits; a.tlimits = plan.dev.tlimits;
@@ -202,7 +260,9 @@ int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan,
 	a.ctr = reinterpret_cast<ExtCounters*>(d + L.o_ctr);
 	a.scan_tmp = &c->plan_tmp; a.scan_tmp_bytes = &c->plan_tmp_bytes;
 	hipStream_t st = c->stream;
-	if (int rc = c->ext_host.ensure(sizeof(ExtCounters))) return rc;
+	// (page-locked, behind the counters: the transcript counters, one 64-bit value, the bounds of a walk's pieces)
+	const size_t h_trc = (sizeof(ExtCounters) + 63) & ~(size_t)63, h_val = h_trc + ((sizeof(TrCounters) + 63) & ~(size_t)63), h_pieces = h_val + 64;
+	if (int rc = c->ext_host.ensure(h_pieces + 64)) return rc;
 	// Round 1 sweeps in traceback mode and keeps the trace rows (round 2 then only walks them) while the iterations' rows fit the
 	// context's trace budget: the first iteration's in ext_trace, every later one's in an arena of its own, all addressed from
 	// ext_trace's base (64-bit offsets). An iteration that does not fit is swept for scores only, and round 2 sweeps its survivors
@@ -224,6 +284,9 @@ int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan,
 	HIP_TRY(launch_ext_begin(a, st));
 	ExtCounters ctr;
 	// the trace walk over the first n entries of the round-2 list
+	// (with a transcript arena: piece by piece, each piece's transcripts written into raw slots and kept in the store -- a chunk's
+	// trace rows may be gone after the next sweep, so this is the one place where transcripts are made, in every mode)
+	size_t store_used = 0;
 	auto walk = [&](uint32_t n) -> int {
 		TracebackArgs t;
 		t.qblock = c->block[DMND_QUERY].as<int8_t>(); t.tblock = c->block[DMND_TARGET].as<int8_t>(); t.cbs = c->cbs_len > 0 ? c->cbs.as<int8_t>() : nullptr;
@@ -231,8 +294,59 @@ int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan,
 		t.items = a.items; t.order = a.r2_order; t.p_of_slot = a.r2_p; t.trace_off = a.r2_off; t.transcript_off = a.r2_tr;
 		t.trace = c->ext_trace.as<uint8_t>(); t.transcript = nullptr; t.ends = a.ends; t.hsps = a.hsps; t.status = &a.ctr->tb_status;
 		t.n = n; t.gap_open = c->params.gap_open; t.gap_extend = c->params.gap_extend;
-		HIP_TRY(launch_traceback(t, st));
-		return DMND_OK;
+		if (!with_tr) {
+			HIP_TRY(launch_traceback(t, st));
+			return DMND_OK;
+		}
+		// 1. the slots: r2_tr = scan of the entries' slot widths; the list cut into pieces of at most piece_limit raw bytes
+		HIP_TRY(launch_tr_slots(a, ta, n, piece_limit, st));
+		HIP_TRY(copy_now(st, c->ext_host.as<char>() + h_trc, ta.ctr, sizeof(TrCounters), hipMemcpyDeviceToHost));
+		const TrCounters tc = *reinterpret_cast<const TrCounters*>(c->ext_host.as<char>() + h_trc);
+		if (tc.n_pieces == 0 || tc.n_pieces > n || tc.raw_max <= 0 || tc.raw_max > tc.raw_total) return fail(DMND_E_DEVICE, "dmnd_extend: the pieces of the transcript walk are inconsistent");
+		std::vector<uint32_t> bounds{ 0u, n };
+		if (tc.n_pieces > 1) {
+			const size_t bytes = ((size_t)tc.n_pieces + 1) * sizeof(uint32_t);
+			if (int rc = c->ext_host.ensure(h_pieces + bytes)) return rc;
+			HIP_TRY(copy_now(st, c->ext_host.as<char>() + h_pieces, ta.pieces, bytes, hipMemcpyDeviceToHost));
+			const uint32_t* b = reinterpret_cast<const uint32_t*>(c->ext_host.as<char>() + h_pieces);
+			bounds.assign(b, b + tc.n_pieces + 1);
+		}
+		if (int rc = c->ext_tr_raw.ensure((size_t)tc.raw_max)) return rc;
+		Guard guard_raw(c->ext_tr_raw, (size_t)tc.raw_max, st);
+		if (int rc = guard_raw.arm()) return rc;
+		tr_raw += (size_t)tc.raw_total;
+		for (uint32_t p = 0; p < tc.n_pieces; ++p) {
+			const uint32_t s0 = bounds[p], s1 = bounds[p + 1];
+			if (s1 <= s0 || s1 > n) return fail(DMND_E_DEVICE, "dmnd_extend: the pieces of the transcript walk are inconsistent");
+			const uint32_t m = s1 - s0;
+			// 2. the walk of the piece; its offsets count from the piece's first entry
+			t.order = a.r2_order + s0; t.p_of_slot = a.r2_p + s0; t.trace_off = a.r2_off + s0; t.transcript_off = a.r2_tr + s0;
+			t.transcript = c->ext_tr_raw.as<uint8_t>(); t.transcript_from_first = 1; t.n = m;
+			if (tev.on) HIP_TRY(hipEventRecord(tev.e[0], st));
+			HIP_TRY(launch_traceback(t, st));
+			if (tev.on) HIP_TRY(hipEventRecord(tev.e[1], st));
+			// 3. the keep step: lengths, their scan, the copy into the store behind the earlier pieces
+			HIP_TRY(launch_tr_keep_sizes(a, ta, s0, m, st));
+			HIP_TRY(copy_now(st, c->ext_host.as<char>() + h_val, ta.k_off + m, sizeof(int64_t), hipMemcpyDeviceToHost));
+			const int64_t kept_bytes = *reinterpret_cast<const int64_t*>(c->ext_host.as<char>() + h_val);
+			if (kept_bytes < (int64_t)m || kept_bytes > tc.raw_max) return fail(DMND_E_DEVICE, "dmnd_extend: the kept transcripts of a piece are inconsistent");
+			if (tev.on) { float ms = 0.f; HIP_TRY(hipEventElapsedTime(&ms, tev.e[0], tev.e[1])); ms_tr_walk += ms; }
+			if (int rc = grow_keeping(c->ext_tr_store, store_used + (size_t)kept_bytes, store_used, st)) return rc;
+			Guard guard_store(c->ext_tr_store, store_used + (size_t)kept_bytes, st);
+			if (int rc = guard_store.arm()) return rc;
+			if (tev.on) HIP_TRY(hipEventRecord(tev.e[0], st));
+			HIP_TRY(launch_tr_keep(a, ta, s0, m, c->ext_tr_raw.as<uint8_t>(), c->ext_tr_store.as<uint8_t>(), (int64_t)store_used, st));
+			if (tev.on) {
+				HIP_TRY(hipEventRecord(tev.e[1], st));
+				HIP_TRY(sync_stream(st));
+				float ms = 0.f; HIP_TRY(hipEventElapsedTime(&ms, tev.e[0], tev.e[1])); ms_tr_keep += ms;
+			}
+			if (int rc = guard_store.check("dmnd_extend (device half, transcript store)")) return rc;
+			store_used += (size_t)kept_bytes;
+			++tr_pieces;
+		}
+		tr_kept = store_used;
+		return guard_raw.check("dmnd_extend (device half, raw transcript slots)");
 	};
 	// the list's entries whose round-1 sweep kept no trace rows, swept again with traceback as one more iteration (copies of their items)
 	auto resweep = [&](uint32_t n_listed, double& ms) -> int {
@@ -361,6 +475,29 @@ int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan,
 		if (n_out > n_kept) return fail(DMND_E_CAP, "dmnd_extend: more device records than walked targets");
 	}
 	else HIP_TRY(launch_ext_records(a, ctr.n_kept, st));
+	// 4b. the gather step: the records' transcripts from the store into one output buffer in record order, their offsets into the
+	// records; then straight into the caller's arena
+	if (with_tr && n_out > 0) {
+		if (n_out > nR) return fail(DMND_E_CAP, "dmnd_extend: more device records than -k allows");
+		HIP_TRY(launch_tr_gather_sizes(a, ta, n_out, st));
+		HIP_TRY(copy_now(st, c->ext_host.as<char>() + h_val, ta.r_off + n_out, sizeof(int64_t), hipMemcpyDeviceToHost));
+		const int64_t bytes = *reinterpret_cast<const int64_t*>(c->ext_host.as<char>() + h_val);
+		if (bytes < (int64_t)n_out || (size_t)bytes > store_used) return fail(DMND_E_DEVICE, "dmnd_extend: the gathered transcripts are inconsistent");
+		if (bytes > transcript_cap) return fail(DMND_E_CAP, "dmnd_banded_swipe: transcript arena too small");
+		if (int rc = c->ext_tr_out.ensure((size_t)bytes)) return rc;
+		Guard guard_out(c->ext_tr_out, (size_t)bytes, st);
+		if (int rc = guard_out.arm()) return rc;
+		if (tev.on) HIP_TRY(hipEventRecord(tev.e[0], st));
+		HIP_TRY(launch_tr_gather(a, ta, n_out, c->ext_tr_store.as<uint8_t>(), c->ext_tr_out.as<uint8_t>(), st));
+		if (tev.on) HIP_TRY(hipEventRecord(tev.e[1], st));
+		HIP_TRY(copy_now(st, c->ext_host.as<char>() + h_trc, ta.ctr, sizeof(TrCounters), hipMemcpyDeviceToHost));
+		if (reinterpret_cast<const TrCounters*>(c->ext_host.as<char>() + h_trc)->missing) return fail(DMND_E_DEVICE, "dmnd_extend: a device record without a kept transcript");
+		if (tev.on) { float ms = 0.f; HIP_TRY(hipEventElapsedTime(&ms, tev.e[0], tev.e[1])); ms_tr_gather += ms; }
+		if (int rc = guard_out.check("dmnd_extend (device half, gathered transcripts)")) return rc;
+		if (int rc = download_bytes(c, transcript, c->ext_tr_out.p, (size_t)bytes)) return rc;
+		tr_gathered = (size_t)bytes;
+	}
+	if (transcript_used) *transcript_used = (int64_t)tr_gathered;
 	const size_t h_ctr = 0, h_qstate = (sizeof(ExtCounters) + 63) & ~(size_t)63, h_records = (h_qstate + nQ + 63) & ~(size_t)63,
 		h_bytes = h_records + (size_t)n_out * sizeof(dmnd_match);
 	if (int rc = c->ext_host.ensure(h_bytes)) return rc;
@@ -401,7 +538,8 @@ int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan,
 	}
 	// 5. ... and back into the copy in HBM: the records stay there, complete, for a join on the device (dmnd_extend_records_device,
 	// dmnd_join_contexts_device) -- 16 bytes per record up instead of 104 down and up again
-	if (n > 0) {
+	// (a call with a transcript arena is joined on the host: its records do not go back up)
+	if (n > 0 && !with_tr) {
 		if (reordered) HIP_TRY(hipMemcpyAsync(a.records, records.data(), n * sizeof(dmnd_match), hipMemcpyHostToDevice, st));
 		else {
 			if (int rc = c->ext_ev.ensure(n * 2 * sizeof(double))) return rc;
@@ -413,7 +551,7 @@ int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan,
 		}
 		HIP_TRY(sync_stream(st));
 	}
-	c->ext_records_dev = a.records; c->ext_records_n = (int64_t)n;
+	if (!with_tr) { c->ext_records_dev = a.records; c->ext_records_n = (int64_t)n; }
 	tr.lap("host e-values, order check");
 	c->ext_stats[0] += (double)items_total; c->ext_stats[1] += (double)ctr.n_kept;
 	c->ext_stats[2] += (double)ctr.cells1; c->ext_stats[3] += (double)ctr.cells2;
@@ -432,7 +570,10 @@ int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan,
 	}
 	if (tr.on) std::fprintf(stderr, "dmnd_extend (device half): %zu queries, %u handed back to the host (%u ambiguous, %u saturated, %u at the chunk cap of %d), %zu records; %u groups, %u bands, %zu bytes of work arrays\n",
 		n_eligible, ctr.n_ambiguous + ctr.n_saturated + ctr.n_capped, ctr.n_ambiguous, ctr.n_saturated, ctr.n_capped, max_chunks, n, plan.n_groups, plan.n_bands, L.bytes);
+	if (tr.on && with_tr) std::fprintf(stderr, "dmnd_extend (device half) transcripts: %zu pieces of at most %lld raw bytes, %zu raw bytes, %zu kept bytes, %zu gathered bytes; walk %.3f ms, keep %.3f ms, gather %.3f ms\n",
+		tr_pieces, (long long)piece_limit, tr_raw, tr_kept, tr_gathered, ms_tr_walk, ms_tr_keep, ms_tr_gather);
 	if (int rc = guard.check("dmnd_extend (device half)")) return rc;
+	if (with_tr) if (int rc = guard_tr.check("dmnd_extend (device half, transcript arrays)")) return rc;
 	done = true;
 	return DMND_OK;
 }

@@ -1,9 +1,10 @@
 // extend_host.hip -- the extension stage above the GPU Smith-Waterman: what Extension::extend does per query
 // (/root/reference/src/align/extend.cpp:226-420), re-organised for the GPU as block-wide batches.
 // Since round 6 dmnd_extend has TWO halves behind one entry. The default protein search (one query context, one HSP per target,
-// -k culling by e-value, Hauser bias or none, banded extension, no transcripts) is planned (plan_kernels.hip) and extended
+// -k culling by e-value or --top, Hauser bias or none, banded extension, with or without a transcript arena) is planned (plan_kernels.hip) and extended
 // (extend_kernels.hip; extend_device.hip drives it) entirely in HBM: the host reads a few counters per ranking iteration, writes
-// its own e-value and bit score into the records and leaves them on the device for the join. Every other mode, and the queries the
+// its own e-value and bit score into the records and leaves them on the device for the join (with a transcript arena: copies the
+// gathered transcripts into its front instead; the host path fills the rest). Every other mode, and the queries the
 // device half hands back, take the HOST PATH described next (extend_range) -- same records either way; the two outputs are merged by query.
 // The host path: the queries with seed hits go through
 //   prelude     :  Hauser bias of the whole query block                              (GPU, bias_kernels.hip; once per call)
@@ -1453,7 +1454,7 @@ extern "C" int dmnd_extend(dmnd_ctx* c, const int8_t* qdata, const int8_t* tdata
 	const DevPlan* dp = planned ? &plan : nullptr;
 	// The queries are extended in HBM from here on (extend_kernels.hip), ranking chunk by ranking chunk: the default search of a
 	// protein query block -- one HSP per target, -k culling by e-value or --top culling by score, Hauser bias or none, with or without
-	// the HSP filters, no transcripts (the caller formats from the statistics). The queries the device half hands back, and every
+	// the HSP filters, with or without a transcript arena (its transcripts come first in the arena). The queries the device half hands back, and every
 	// query of any other mode, take the host path below.
 	// DMND_EXTEND_DEVICE=0: all queries on the host path, as up to round 5. Read per call, like the hooks of extend_device.hip
 	// (DESIGN.md 9): a test compares the two paths in one process.
@@ -1465,18 +1466,19 @@ extern "C" int dmnd_extend(dmnd_ctx* c, const int8_t* qdata, const int8_t* tdata
 	bool on_device = false;
 	for (double& x : c->ext_dev_stats) x = 0;
 	c->ext_filter_stats[0] = c->ext_filter_stats[1] = 0;
-	if (ext_gpu && planned && h.max_hsps == 1 && !cbs_matrix_adjust(h.cbs_mode) && !h.ext_full && !transcript
+	int64_t used_dev = 0;                                 // bytes of the caller's transcript arena the device half filled (from offset 0 on)
+	if (ext_gpu && planned && h.max_hsps == 1 && !cbs_matrix_adjust(h.cbs_mode) && !h.ext_full
 		&& h.global_ranking == 0 && !c->same_title && h.max_target_seqs > 0) {
 		std::vector<uint8_t> qstate;
 		double kept[12];
 		for (int i = 0; i < 12; ++i) kept[i] = c->ext_stats[i];
-		if (int rc = extend_on_device(c, device_cfg(h), plan, threads, dev_records, qstate, on_device)) return rc;
+		if (int rc = extend_on_device(c, device_cfg(h), plan, threads, dev_records, qstate, on_device, transcript, transcript_cap, &used_dev)) return rc;
 		bias_pending = false;                               // (it has waited for the stream)
 		if (on_device) {
 			for (size_t k = 0; k < qr.size(); ++k)
 				if (qstate[k] != EXT_Q_DEVICE) { qr_host.push_back(qr[k]); pq_host.push_back((uint32_t)k); }
 		}
-		else for (int i = 0; i < 12; ++i) c->ext_stats[i] = kept[i];
+		else { for (int i = 0; i < 12; ++i) c->ext_stats[i] = kept[i]; used_dev = 0; }
 	}
 	const std::vector<Range>& qr_all = qr;
 	const std::vector<Range>& qr_run = on_device ? qr_host : qr_all;
@@ -1512,6 +1514,7 @@ extern "C" int dmnd_extend(dmnd_ctx* c, const int8_t* qdata, const int8_t* tdata
 	const int team = tuning().extend_team;
 	if (on_device && qr_run.empty()) {
 		if (bias_pending) HIP_TRY(sync_stream(c->stream));      // every query was extended on the device
+		if (transcript_used) *transcript_used = used_dev;
 	}
 	else if (split == 1 && cbs_matrix_adjust(h.cbs_mode)) {
 		// --comp-based-stats 2-5: every planned (query, target) pair owns a 1 KB adjusted matrix for the whole extend_range call
@@ -1541,8 +1544,13 @@ extern "C" int dmnd_extend(dmnd_ctx* c, const int8_t* qdata, const int8_t* tdata
 		if (transcript_used) *transcript_used = t_used;
 	}
 	else if (split == 1) {
-		rcs[0] = extend_range(c, c, h, qr_run, 0, qr_run.size(), hits, gf, qdata, tdata, cbs, std::min(threads, team), hsp_values, parts[0], transcript, transcript_cap, transcript_used,
-			bias_pending ? c->stream : nullptr, xd, dp, pq_index);
+		// (the host path fills the rest of the arena behind the device half's transcripts; its offsets count from there)
+		rcs[0] = extend_range(c, c, h, qr_run, 0, qr_run.size(), hits, gf, qdata, tdata, cbs, std::min(threads, team), hsp_values, parts[0], transcript ? transcript + used_dev : nullptr,
+			transcript ? transcript_cap - used_dev : 0, transcript_used, bias_pending ? c->stream : nullptr, xd, dp, pq_index);
+		if (rcs[0] == DMND_OK && used_dev > 0) {
+			for (dmnd_match& m : parts[0]) if (m.hsp.transcript_off >= 0) m.hsp.transcript_off += used_dev;
+			if (transcript_used) *transcript_used += used_dev;
+		}
 	}
 	else {
 		if (bias_pending) HIP_TRY(sync_stream(c->stream));

@@ -8,6 +8,7 @@
 //   culling: sort by (e-value, score, target), first -k targets            (/root/reference/src/align/culling.cpp:97-113, 189-203)
 //   round 2 = a walk of the kept traces of the survivors                     (/root/reference/src/align/gapped_final.cpp:66-160)
 //   match records in (query, e-value, score, target) order                   (/root/reference/src/align/extend.h:51-56, extend.cpp:341)
+//   with a transcript arena: the walk's packed transcripts kept in a dense store, gathered in record order (TrArgs below)
 // The e-value is double arithmetic with exp / erfc (evalue.h); the device's versions of those differ from the host library's in the
 // last bits, so the device value only DECIDES (cutoff, order, first k) and a decision that two values closer than 1e-9 relative
 // could flip marks the query `ambiguous`: the host redoes that query (two values that are 0.0 on both sides are ordered by score and
@@ -21,6 +22,7 @@
 #include "extend_core.h"
 #include "filter_core.h"
 #include "top_core.h"
+#include "transcript_core.h"
 #include "plan_kernels.h"
 #include "swipe_kernels.h"
 
@@ -87,7 +89,35 @@ struct ExtArgs {
 	dmnd_match* records;
 	ExtCounters* ctr;
 	void** scan_tmp; size_t* scan_tmp_bytes;
+	int tr_on;                     // the call returns transcripts: a record leaves the records kernels with its GROUP in hsp.transcript_off
+	                               // (launch_tr_gather turns it into the offset); 0: -1, as ever
 };
+
+// The transcripts of a call with a transcript arena (transcript_core.h; layout: extend_core.h tr_layout). The trace walk writes each
+// walked entry's packed transcript into a raw slot; the KEEP step behind every walk copies them into a dense, append-only store
+// (a chunk's trace rows are gone once the next chunk is swept, its transcripts stay); the GATHER step, once the records exist,
+// copies each record's transcript from the store into the output in record order. One wavefront per entry, byte copies, offsets
+// from scans: no atomics, the same layout in every run. Raw slots, store and output are three allocations, each addressed from its
+// own base by offsets >= 0.
+struct TrArgs {
+	int64_t* g_store;              // per group: offset of its transcript in the store
+	int64_t* k_len; int64_t* k_off;          // per entry of the current piece (+ 1)
+	int64_t* r_len; int64_t* r_off;          // per record (+ 1)
+	uint32_t* pieces;              // first entry of each piece of the current walk (+ 1: the list's end)
+	TrCounters* ctr;
+};
+
+// before a walk of the first n entries of the round-2 list: a.r2_tr[0 .. n] = exclusive scan of the entries' slot widths
+// (tr_slot_bytes), and the list cut into consecutive pieces of at most `limit` raw bytes (at least one entry): t.pieces, t.ctr
+hipError_t launch_tr_slots(const ExtArgs& a, const TrArgs& t, uint32_t n, int64_t limit, hipStream_t st);
+// behind the walk of the piece [s0, s0 + m): the kept lengths of its entries and their scan, t.k_off[m] = the piece's bytes in the store ...
+hipError_t launch_tr_keep_sizes(const ExtArgs& a, const TrArgs& t, uint32_t s0, uint32_t m, hipStream_t st);
+// ... and the copy raw -> store + base (store holds base + t.k_off[m] bytes at least), the store offset of each entry's group
+hipError_t launch_tr_keep(const ExtArgs& a, const TrArgs& t, uint32_t s0, uint32_t m, const uint8_t* raw, uint8_t* store, int64_t base, hipStream_t st);
+// behind the records kernels (a.tr_on): the records' output sizes and their scan, t.r_off[n] = bytes of the output ...
+hipError_t launch_tr_gather_sizes(const ExtArgs& a, const TrArgs& t, uint32_t n, hipStream_t st);
+// ... and the copy store -> out (t.r_off[n] bytes at least), records[r].hsp.transcript_off = t.r_off[r]
+hipError_t launch_tr_gather(const ExtArgs& a, const TrArgs& t, uint32_t n, const uint8_t* store, uint8_t* out, hipStream_t st);
 
 enum { EXT_F_PASS = 0, EXT_F_FAIL = 1, EXT_F_THRESHOLD = 2 };
 enum { EXT_Q_HOST = 0, EXT_Q_DEVICE = 1, EXT_Q_AMBIGUOUS = 2, EXT_Q_CAPPED = 3 };      // CAPPED: still ranking after the last allowed chunk

@@ -531,7 +531,7 @@ __global__ __launch_bounds__(64) void ext_records_kernel(ExtArgs a)
 		m.hsp.score = hsp.score; m.hsp.q_begin = hsp.q_begin; m.hsp.q_end = hsp.q_end; m.hsp.s_begin = hsp.s_begin; m.hsp.s_end = hsp.s_end;
 		m.hsp.length = hsp.length; m.hsp.identities = hsp.identities; m.hsp.mismatches = hsp.mismatches; m.hsp.positives = hsp.positives;
 		m.hsp.gap_openings = hsp.gap_openings; m.hsp.gaps = hsp.gaps; m.hsp.transcript_len = hsp.transcript_len;
-		m.hsp.transcript_off = -1;
+		m.hsp.transcript_off = a.tr_on ? (int64_t)g : -1;      // (tr_on: its group, for launch_tr_gather)
 	}
 }
 
@@ -984,7 +984,7 @@ __global__ __launch_bounds__(256) void ext_top_records_kernel(ExtArgs a, uint32_
 	m.hsp.score = hsp.score; m.hsp.q_begin = hsp.q_begin; m.hsp.q_end = hsp.q_end; m.hsp.s_begin = hsp.s_begin; m.hsp.s_end = hsp.s_end;
 	m.hsp.length = hsp.length; m.hsp.identities = hsp.identities; m.hsp.mismatches = hsp.mismatches; m.hsp.positives = hsp.positives;
 	m.hsp.gap_openings = hsp.gap_openings; m.hsp.gaps = hsp.gaps; m.hsp.transcript_len = hsp.transcript_len;
-	m.hsp.transcript_off = -1;
+	m.hsp.transcript_off = a.tr_on ? (int64_t)g : -1;          // (tr_on: its group, for launch_tr_gather)
 }
 
 hipError_t ensure_tmp(void** tmp, size_t* have, size_t need)
@@ -1216,6 +1216,145 @@ hipError_t launch_ext_top_records(const ExtArgs& a, uint32_t n_walked, hipStream
 	e = rocprim::radix_sort_pairs(*a.scan_tmp, need, a.okeys, a.okeys_sorted, a.oidx, a.rperm, (size_t)n_walked, 0, 64, st);
 	if (e != hipSuccess) return e;
 	hipLaunchKernelGGL(ext_top_records_kernel, dim3(blocks), dim3(256), 0, st, a, n_walked);
+	return hipGetLastError();
+}
+
+// ---- transcripts (extend_kernels.h TrArgs; arithmetic: transcript_core.h) ----
+
+namespace {
+
+// slot widths of the first n entries of the round-2 list (entry n: 0, the scan's total). Bound: n <= r2_cap = nS, k_len holds nS + 1
+__global__ __launch_bounds__(256) void ext_tr_widths_kernel(ExtArgs a, TrArgs t, uint32_t n)
+{
+	const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+	if (k > n) return;
+	int64_t w = 0;
+	if (k < n) {
+		const dmnd_dp_target d = a.items[a.r2_order[k]];
+		w = tr_slot_bytes(d.query_len, d.target_len);
+	}
+	t.k_len[k] = w;
+}
+
+// The pieces of the walk, one thread: a binary search over the scan per piece (pieces are few: the limit is hundreds of MB by
+// default). Bound: a piece has at least one entry, so at most n + 1 <= nS + 1 entries of `pieces` are written.
+__global__ __launch_bounds__(64) void ext_tr_pieces_kernel(ExtArgs a, TrArgs t, uint32_t n, int64_t limit)
+{
+	if (blockIdx.x != 0 || threadIdx.x != 0) return;
+	uint32_t np = 0, s = 0;
+	long long raw_max = 0;
+	t.pieces[0] = 0;
+	while (s < n) {
+		const uint32_t e = tr_piece_end(a.r2_tr, n, s, limit);
+		const long long bytes = (long long)tr_raw_off(a.r2_tr[e], a.r2_tr[s]);
+		raw_max = bytes > raw_max ? bytes : raw_max;
+		t.pieces[++np] = e;
+		s = e;
+	}
+	t.ctr->n_pieces = np;
+	t.ctr->raw_total = (long long)a.r2_tr[n];
+	t.ctr->raw_max = raw_max;
+}
+
+// kept lengths of the piece [s0, s0 + m) behind its walk (entry m: 0). Bound: m <= nS, k_len holds nS + 1
+__global__ __launch_bounds__(256) void ext_tr_keep_sizes_kernel(ExtArgs a, TrArgs t, uint32_t s0, uint32_t m)
+{
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i > m) return;
+	t.k_len[i] = i < m ? tr_kept_bytes(a.hsps[a.r2_order[s0 + i]].transcript_len) : 0;
+}
+
+// raw slot -> store, one wavefront per entry of the piece. Reads k_len[i] <= the slot's width bytes from the slot at
+// r2_tr[s0 + i] - r2_tr[s0] (inside the piece's raw bytes); writes them at base + k_off[i] (the host sized the store to
+// base + k_off[m]); one g_store entry per entry, index r2_group < n_groups.
+__global__ __launch_bounds__(256) void ext_tr_keep_kernel(ExtArgs a, TrArgs t, uint32_t s0, uint32_t m, const uint8_t* raw, uint8_t* store, int64_t base)
+{
+	const uint32_t i = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+	if (i >= m) return;
+	const int64_t src = tr_raw_off(a.r2_tr[s0 + i], a.r2_tr[s0]), dst = tr_dense_off(base, t.k_off[i]);
+	const int64_t width = a.r2_tr[s0 + i + 1] - a.r2_tr[s0 + i];
+	int64_t bytes = t.k_len[i];
+	if (bytes > width) bytes = width;            // (never: the walk fails a transcript that does not fit its slot)
+	tr_copy_lane(store + dst, raw + src, bytes, (int)lane);
+	if (lane == 0) t.g_store[a.r2_group[s0 + i]] = dst;
+}
+
+// output sizes of the n records (entry n: 0). Bound: n <= nR, r_len holds nR + 1
+__global__ __launch_bounds__(256) void ext_tr_gather_sizes_kernel(ExtArgs a, TrArgs t, uint32_t n)
+{
+	const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+	if (r > n) return;
+	t.r_len[r] = r < n ? tr_kept_bytes(a.records[r].hsp.transcript_len) : 0;
+}
+
+// store -> output, one wavefront per record; the record carries its group in hsp.transcript_off (a.tr_on) and leaves with its
+// offset in the output. Reads r_len[r] bytes of the store at g_store[group] (what ext_tr_keep_kernel wrote for that group:
+// the same length, the same transcript_len), writes them at r_off[r] (the host sized the output to r_off[n]).
+__global__ __launch_bounds__(256) void ext_tr_gather_kernel(ExtArgs a, TrArgs t, uint32_t n, const uint8_t* store, uint8_t* out)
+{
+	const uint32_t r = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+	if (r >= n) return;
+	const int64_t g = a.records[r].hsp.transcript_off;
+	const int64_t src = g >= 0 && g < (int64_t)a.n_groups ? t.g_store[g] : -1;
+	if (src < 0) {                               // (never: every record's group was walked and kept; the host fails the call)
+		if (lane == 0) t.ctr->missing = 1;
+		return;
+	}
+	const int64_t dst = tr_dense_off(0, t.r_off[r]);
+	tr_copy_lane(out + dst, store + src, t.r_len[r], (int)lane);
+	__builtin_amdgcn_wave_barrier();             // (every lane has read the group before lane 0 overwrites it)
+	if (lane == 0) a.records[r].hsp.transcript_off = dst;
+}
+
+hipError_t scan64(const ExtArgs& a, int64_t* in, int64_t* out, size_t n, hipStream_t st)
+{
+	size_t need = 0;
+	hipError_t e = rocprim::exclusive_scan(nullptr, need, in, out, (int64_t)0, n, rocprim::plus<int64_t>(), st);
+	if (e != hipSuccess) return e;
+	e = ensure_tmp(a.scan_tmp, a.scan_tmp_bytes, need);
+	if (e != hipSuccess) return e;
+	return rocprim::exclusive_scan(*a.scan_tmp, need, in, out, (int64_t)0, n, rocprim::plus<int64_t>(), st);
+}
+
+}  // namespace
+
+hipError_t launch_tr_slots(const ExtArgs& a, const TrArgs& t, uint32_t n, int64_t limit, hipStream_t st)
+{
+	if (n > a.r2_cap) return hipErrorInvalidValue;
+	hipLaunchKernelGGL(ext_tr_widths_kernel, dim3((n + 1 + 255) / 256), dim3(256), 0, st, a, t, n);
+	const hipError_t e = scan64(a, t.k_len, a.r2_tr, (size_t)n + 1, st);
+	if (e != hipSuccess) return e;
+	hipLaunchKernelGGL(ext_tr_pieces_kernel, dim3(1), dim3(64), 0, st, a, t, n, limit);
+	return hipGetLastError();
+}
+
+hipError_t launch_tr_keep_sizes(const ExtArgs& a, const TrArgs& t, uint32_t s0, uint32_t m, hipStream_t st)
+{
+	if ((uint64_t)s0 + m > a.r2_cap) return hipErrorInvalidValue;
+	hipLaunchKernelGGL(ext_tr_keep_sizes_kernel, dim3((m + 1 + 255) / 256), dim3(256), 0, st, a, t, s0, m);
+	return scan64(a, t.k_len, t.k_off, (size_t)m + 1, st);
+}
+
+hipError_t launch_tr_keep(const ExtArgs& a, const TrArgs& t, uint32_t s0, uint32_t m, const uint8_t* raw, uint8_t* store, int64_t base, hipStream_t st)
+{
+	if (m == 0) return hipSuccess;
+	if ((uint64_t)s0 + m > a.r2_cap || base < 0) return hipErrorInvalidValue;
+	hipLaunchKernelGGL(ext_tr_keep_kernel, dim3((m + 3) / 4), dim3(256), 0, st, a, t, s0, m, raw, store, base);
+	return hipGetLastError();
+}
+
+hipError_t launch_tr_gather_sizes(const ExtArgs& a, const TrArgs& t, uint32_t n, hipStream_t st)
+{
+	if (n > a.r2_cap) return hipErrorInvalidValue;      // (r2_cap = the capacity of the records, ExtLayout::nR)
+	hipLaunchKernelGGL(ext_tr_gather_sizes_kernel, dim3((n + 1 + 255) / 256), dim3(256), 0, st, a, t, n);
+	return scan64(a, t.r_len, t.r_off, (size_t)n + 1, st);
+}
+
+hipError_t launch_tr_gather(const ExtArgs& a, const TrArgs& t, uint32_t n, const uint8_t* store, uint8_t* out, hipStream_t st)
+{
+	if (n == 0) return hipSuccess;
+	if (n > a.r2_cap) return hipErrorInvalidValue;
+	hipLaunchKernelGGL(ext_tr_gather_kernel, dim3((n + 3) / 4), dim3(256), 0, st, a, t, n, store, out);
 	return hipGetLastError();
 }
 

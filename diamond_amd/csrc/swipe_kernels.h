@@ -54,6 +54,8 @@ struct TracebackArgs {
 	int32_t* status;             // min over items of the walk status (0 = ok)
 	int64_t n;
 	int32_t gap_open, gap_extend;
+	int32_t transcript_from_first = 0; // 1: the offsets count from transcript_off[0] -- slot s writes at transcript + (transcript_off[s] -
+	                             // transcript_off[0]) (a walk over a stretch of a longer list whose offsets are one scan over the whole list)
 };
 
 // packed-int16 sweep, two items per wavefront (swipe16_kernels.hip; eight for the row classes P = 3, 5): band classes P <= 5, at most 65535 pair-steps per item,

@@ -278,7 +278,8 @@ __global__ __launch_bounds__(256) void traceback_kernel(TracebackArgs args)
 	h.q_begin = h.q_end = h.s_begin = h.s_end = 0;
 	h.length = h.identities = h.mismatches = h.positives = h.gap_openings = h.gaps = 0;
 	h.transcript_len = 0;
-	h.transcript_off = args.transcript_off[slot];
+	const int64_t tr_base = args.transcript_from_first ? args.transcript_off[0] : 0;
+	h.transcript_off = args.transcript_off[slot] - tr_base;
 	if (e.pad[0]) h.transcript_len = -1;          // saturated 16-bit sweep: nothing to walk, the host re-runs the item
 	if (e.score > 0 && !e.pad[0]) {
 		const Geom g = make_geom(it.query_len, it.target_len, it.d_begin, it.d_end);
@@ -289,7 +290,7 @@ __global__ __launch_bounds__(256) void traceback_kernel(TracebackArgs args)
 		const int PC = args.p_of_slot[slot];
 		const int cap = (int)(args.transcript_off[slot + 1] - args.transcript_off[slot]);
 		const WalkResult r = traceback_walk_wave(args.trace + args.trace_off[slot], g, PC, v, args.gap_open, args.gap_extend,
-			e.score, e.end_i, e.end_j, args.transcript ? args.transcript + args.transcript_off[slot] : nullptr, cap, lane);
+			e.score, e.end_i, e.end_j, args.transcript ? args.transcript + (args.transcript_off[slot] - tr_base) : nullptr, cap, lane);
 		h.q_begin = r.q_begin; h.s_begin = r.s_begin; h.q_end = e.end_i + 1; h.s_end = e.end_j + 1;
 		h.length = r.length; h.identities = r.identities; h.mismatches = r.mismatches; h.positives = r.positives;
 		h.gap_openings = r.gap_openings; h.gaps = r.gaps; h.transcript_len = r.transcript_len;
@@ -297,7 +298,7 @@ __global__ __launch_bounds__(256) void traceback_kernel(TracebackArgs args)
 			atomicMin(args.status, r.status);
 	}
 	else if (args.transcript && lane == 0 && args.transcript_off[slot + 1] > args.transcript_off[slot])
-		args.transcript[args.transcript_off[slot]] = 0;
+		args.transcript[args.transcript_off[slot] - tr_base] = 0;
 	if (lane == 0) args.hsps[item_idx] = h;
 }
 

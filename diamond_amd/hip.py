@@ -895,14 +895,17 @@ class Context:
         self._check(self.lib.dmnd_seed_kernel_ms(self.h, ms))
         return list(ms)
 
-    def extend(self, qdata, tdata, hits, threads=8, hsp_values=510, with_transcripts=False):
-        """Extension::extend for every query of the block (hits sorted by query). Returns (matches, transcripts|None)."""
+    def extend(self, qdata, tdata, hits, threads=8, hsp_values=510, with_transcripts=False, transcript_cap=None):
+        """Extension::extend for every query of the block (hits sorted by query). Returns (matches, transcripts|None).
+        with_transcripts: every record's hsp.transcript_off points at its packed transcript (transcript_len bytes and a 0 terminator)
+        in the returned byte array; transcript_cap: bytes of the arena handed to the library (default max(1 MiB, 64 per seed hit);
+        an arena that is too small fails with DMND_E_CAP)."""
         qd = np.ascontiguousarray(qdata, dtype=np.int8)
         td = np.ascontiguousarray(tdata, dtype=np.int8)
         hits = np.ascontiguousarray(hits, dtype=SEED_HIT_DTYPE)
         cap = max(1024, hits.size)
         v = ctypes.c_void_p
-        tr = np.zeros(max(1 << 20, 64 * hits.size) if with_transcripts else 0, np.uint8)
+        tr = np.zeros((max(1 << 20, 64 * hits.size) if transcript_cap is None else int(transcript_cap)) if with_transcripts else 0, np.uint8)
         while True:
             out = np.empty(cap, dtype=MATCH_DTYPE)
             n, used = ctypes.c_int64(0), ctypes.c_int64(0)

@@ -325,9 +325,11 @@ int dmnd_extend_plan(const dmnd_params* params, const int8_t* qdata, const int64
 /* Whole extension stage on the uploaded blocks (qdata/tdata: the caller's host copies of the same blocks). hits must be
  * sorted by query. Matches come out ordered by query, then as the reference orders them (e-value, score, target; under
  * dmnd_set_top_percent score, target). The default search of a protein query block -- one HSP per target, -k or --top culling,
- * Hauser bias or none, with or without the HSP filters, no transcripts -- is extended in HBM (dmnd_extend_device_stats); the queries
- * the device half hands back, and every other mode, take the host path. The records are the same either way.
- * transcript may be NULL (then dmnd_hsp::transcript_off = -1). Blastp defaults: max_target_seqs 25, max_hsps 1.
+ * Hauser bias or none, with or without the HSP filters, with or without a transcript arena -- is extended in HBM
+ * (dmnd_extend_device_stats); the queries the device half hands back, and every other mode, take the host path. The records are the same
+ * either way. transcript: an arena of transcript_cap bytes for the packed transcripts (transcript_len bytes and a 0 terminator at
+ * dmnd_hsp::transcript_off of each record; *transcript_used = bytes written; both halves fill the one arena; too small: DMND_E_CAP,
+ * nothing is written past transcript_cap). transcript may be NULL (then dmnd_hsp::transcript_off = -1). Blastp defaults: max_target_seqs 25, max_hsps 1.
  * threads bounds the host threads: blocks with >= 2048 queries run as up to 8 runners (own HIP stream each), worker threads
  * under a runner only when its share of the seed hits is large. Without transcripts round 1 keeps its trace rows in HBM and
  * round 2 only walks them (dmnd_extend_stats[10] = 0 then); the records are the same either way. */

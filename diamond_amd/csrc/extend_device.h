@@ -21,13 +21,16 @@ struct DeviceCfg {
 	double min_bit_score = 0.0;          // --min-score
 	FilterCfg filters;                   // --id, --approx-id, --query-cover, --subject-cover (filter_core.h)
 	double top = -1.0;                   // --top: >= 0 = the targets within this percentage of the best bit score, -k plays no part
+	int contexts = 1;                    // 6: translated queries -- the planner groups per read, the records carry the winning frame
 };
 
 // What the device planner hands over (page-locked host copies of its lists; valid until the context's next dmnd_extend)
 struct DevPlan {
-	const PlanGroup* groups = nullptr;
+	const PlanGroup* groups = nullptr;        // translated queries: the (read, target) pairs (PlanArgs::pairs), n_groups of them
 	const PlanQuery* queries = nullptr;       // n_queries + 1 entries
 	const PlanBand* bands = nullptr;
+	const uint32_t* band_query = nullptr;     // translated queries: the context of every band, and per group (= pair) the ungapped score of context 0
+	const uint16_t* ungapped0 = nullptr;
 	uint32_t n_groups = 0, n_queries = 0, n_bands = 0, n_on_host = 0;
 	uint32_t n_chain = 0, n_chain_big = 0, n_relisted = 0;      // PlanCounters: the two chaining lists as the kernels left them
 	bool unsorted = false;                    // the hits were not in (query, location, seed offset) order: nothing was planned

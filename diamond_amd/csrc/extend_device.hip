@@ -115,7 +115,15 @@ int dmnd::plan_on_device(dmnd_ctx* c, const DeviceCfg& h, int64_t n_hits, bool g
 		o_segs = align(o_queries + (n + 1) * sizeof(PlanQuery)), o_slots = align(o_segs + n * 4 * sizeof(int32_t)),
 		o_count = align(o_slots + n * sizeof(PlanBand)), o_off = align(o_count + (n + 1) * sizeof(uint32_t)),
 		o_bands = align(o_off + (n + 1) * sizeof(uint32_t)), o_counters = align(o_bands + n * sizeof(PlanBand)),
-		o_chain = align(o_counters + sizeof(PlanCounters)), bytes = o_chain + (n + 2) * sizeof(uint32_t);      // (both chaining lists, and a small group listed again)
+		o_chain = align(o_counters + sizeof(PlanCounters)), o_tr = align(o_chain + (n + 2) * sizeof(uint32_t));      // (both chaining lists, and a small group listed again)
+	// translated queries: the sort, the permuted lists, the pairs (plan_kernels.h)
+	const bool translated = h.contexts > 1;
+	const size_t t_hits = o_tr, t_xd = align(t_hits + n * sizeof(dmnd_seed_hit)), t_gf = align(t_xd + n * sizeof(XdropSeg)), t_keys = align(t_gf + n),
+		t_keys2 = align(t_keys + n * sizeof(uint64_t)), t_perm_in = align(t_keys2 + n * sizeof(uint64_t)), t_perm = align(t_perm_in + n * sizeof(uint32_t)),
+		t_pheads = align(t_perm + n * sizeof(uint32_t)), t_pscan = align(t_pheads + n * sizeof(uint32_t)), t_pairs = align(t_pscan + n * sizeof(uint32_t)),
+		t_pair_unit = align(t_pairs + (n + 1) * sizeof(PlanGroup)), t_unit_pair = align(t_pair_unit + (n + 1) * sizeof(uint32_t)),
+		t_ungapped = align(t_unit_pair + n * sizeof(uint32_t)), t_band_query = align(t_ungapped + n * sizeof(uint16_t)), t_end = align(t_band_query + n * sizeof(uint32_t));
+	const size_t bytes = translated ? t_end : o_tr;
 	TraceLaps tr("dmnd_extend (planner)");
 	if (int rc = c->plan_dev.ensure(bytes)) return rc;
 	Guard guard(c->plan_dev, bytes, c->stream);
@@ -139,6 +147,22 @@ int dmnd::plan_on_device(dmnd_ctx* c, const DeviceCfg& h, int64_t n_hits, bool g
 	a.bands = reinterpret_cast<PlanBand*>(d + o_bands); a.counters = reinterpret_cast<PlanCounters*>(d + o_counters);
 	a.chain_list = reinterpret_cast<uint32_t*>(d + o_chain); a.chain_cap = (uint32_t)(n + 2);
 	a.scan_tmp = &c->plan_tmp; a.scan_tmp_bytes = &c->plan_tmp_bytes;
+	a.contexts = h.contexts;
+	a.hits_in = nullptr; a.gf_in = nullptr; a.xd_in = nullptr; a.hits_sorted = nullptr; a.gf_sorted = nullptr; a.xd_sorted = nullptr;
+	a.keys = nullptr; a.keys_sorted = nullptr; a.perm_in = nullptr; a.perm = nullptr; a.target_bits = 0; a.key_bits = 0;
+	a.pheads = nullptr; a.phead_scan = nullptr; a.pairs = nullptr; a.pair_unit = nullptr; a.unit_pair = nullptr; a.ungapped0 = nullptr; a.band_query = nullptr;
+	if (translated) {
+		a.hits_in = a.hits; a.gf_in = a.gf_flags; a.xd_in = a.xd;
+		a.hits_sorted = reinterpret_cast<dmnd_seed_hit*>(d + t_hits); a.xd_sorted = reinterpret_cast<XdropSeg*>(d + t_xd); a.gf_sorted = reinterpret_cast<uint8_t*>(d + t_gf);
+		a.hits = a.hits_sorted; a.xd = a.xd_sorted; a.gf_flags = gf_on ? a.gf_sorted : nullptr;
+		a.keys = reinterpret_cast<uint64_t*>(d + t_keys); a.keys_sorted = reinterpret_cast<uint64_t*>(d + t_keys2);
+		a.perm_in = reinterpret_cast<uint32_t*>(d + t_perm_in); a.perm = reinterpret_cast<uint32_t*>(d + t_perm);
+		const PlanKeyBits kb = plan_key_bits((uint64_t)((c->limits[DMND_QUERY].size() - 1 + (size_t)h.contexts - 1) / (size_t)h.contexts), (uint64_t)a.n_targets);      // (extend_cfg refuses a block that is no multiple of the contexts; rounded up all the same)
+		a.target_bits = kb.target_bits; a.key_bits = kb.target_bits + kb.read_bits;
+		a.pheads = reinterpret_cast<uint32_t*>(d + t_pheads); a.phead_scan = reinterpret_cast<uint32_t*>(d + t_pscan);
+		a.pairs = reinterpret_cast<PlanGroup*>(d + t_pairs); a.pair_unit = reinterpret_cast<uint32_t*>(d + t_pair_unit); a.unit_pair = reinterpret_cast<uint32_t*>(d + t_unit_pair);
+		a.ungapped0 = reinterpret_cast<uint16_t*>(d + t_ungapped); a.band_query = reinterpret_cast<uint32_t*>(d + t_band_query);
+	}
 	HIP_TRY(launch_plan(a, c->stream));
 	tr.lap("launched");
 	if (int rc = c->plan_host.ensure(sizeof(PlanCounters))) return rc;
@@ -152,6 +176,11 @@ int dmnd::plan_on_device(dmnd_ctx* c, const DeviceCfg& h, int64_t n_hits, bool g
 	plan.n_groups = cn.n_groups; plan.n_queries = cn.n_queries; plan.n_bands = cn.n_bands; plan.n_on_host = cn.n_on_host;
 	plan.n_chain = cn.n_chain; plan.n_chain_big = cn.n_chain_big; plan.n_relisted = cn.n_relisted;
 	plan.dev = a;
+	if (translated) {
+		// the device half and the callers see the pairs: what is ranked, extended and reported per read
+		plan.n_groups = cn.n_pairs; plan.n_on_host = cn.n_pairs_on_host;
+		plan.dev.groups = a.pairs;
+	}
 	planned = true;
 	return DMND_OK;
 }
@@ -162,13 +191,18 @@ int dmnd::plan_fetch_lists(dmnd_ctx* c, DevPlan& plan)
 	if (plan.groups) return DMND_OK;
 	auto align = [](size_t x) { return (x + 63) & ~(size_t)63; };
 	const size_t h_groups = align(sizeof(PlanCounters)), h_queries = align(h_groups + (size_t)plan.n_groups * sizeof(PlanGroup)),
-		h_bands = align(h_queries + ((size_t)plan.n_queries + 1) * sizeof(PlanQuery)), h_bytes = h_bands + (size_t)plan.n_bands * sizeof(PlanBand);
+		h_bands = align(h_queries + ((size_t)plan.n_queries + 1) * sizeof(PlanQuery)), h_bq = align(h_bands + (size_t)plan.n_bands * sizeof(PlanBand)),
+		h_ug = align(h_bq + (plan.dev.band_query ? (size_t)plan.n_bands * sizeof(uint32_t) : 0)), h_bytes = h_ug + (plan.dev.ungapped0 ? (size_t)plan.n_groups * sizeof(uint16_t) : 0);
 	if (int rc = c->plan_host.ensure(h_bytes)) return rc;
 	char* hp = c->plan_host.as<char>();
 	HIP_TRY(hipMemcpyAsync(hp + h_groups, plan.dev.groups, (size_t)plan.n_groups * sizeof(PlanGroup), hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(hipMemcpyAsync(hp + h_queries, plan.dev.queries, ((size_t)plan.n_queries + 1) * sizeof(PlanQuery), hipMemcpyDeviceToHost, c->stream));
 	if (plan.n_bands) HIP_TRY(hipMemcpyAsync(hp + h_bands, plan.dev.bands, (size_t)plan.n_bands * sizeof(PlanBand), hipMemcpyDeviceToHost, c->stream));
+	if (plan.dev.band_query && plan.n_bands) HIP_TRY(hipMemcpyAsync(hp + h_bq, plan.dev.band_query, (size_t)plan.n_bands * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+	if (plan.dev.ungapped0) HIP_TRY(hipMemcpyAsync(hp + h_ug, plan.dev.ungapped0, (size_t)plan.n_groups * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(sync_stream(c->stream));
+	if (plan.dev.band_query) plan.band_query = reinterpret_cast<const uint32_t*>(hp + h_bq);
+	if (plan.dev.ungapped0) plan.ungapped0 = reinterpret_cast<const uint16_t*>(hp + h_ug);
 	plan.groups = reinterpret_cast<const PlanGroup*>(hp + h_groups);
 	plan.queries = reinterpret_cast<const PlanQuery*>(hp + h_queries);
 	plan.bands = reinterpret_cast<const PlanBand*>(hp + h_bands);
@@ -229,6 +263,7 @@ int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan,
 	a.groups = plan.dev.groups; a.queries = plan.dev.queries; a.bands = plan.dev.bands;
 	a.n_groups = plan.n_groups; a.n_queries = plan.n_queries; a.n_bands = plan.n_bands;
 	a.hits = plan.dev.hits; a.qlimits = plan.dev.qlimits; a.tlimits = plan.dev.tlimits;
+	a.contexts = h.contexts; a.band_query = plan.dev.band_query; a.ungapped0 = plan.dev.ungapped0;
 	a.use_cbs = h.use_cbs ? 1 : 0; a.row_min_items = (uint32_t)std::min<int64_t>(sweep_rows_min_items(), 0xffffffffll); a.chunk_size = (uint32_t)chunk; a.k = h.max_target_seqs; a.max_swipe_dp = h.max_swipe_dp;
 	const Evaluer& E = c->evaluer;
 	a.min_bit_score = h.min_bit_score; a.filt = h.filters; a.filt_on = filt ? 1 : 0;
@@ -523,7 +558,8 @@ int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan,
 	parallel_for(n_chunks, std::max(1, std::min(threads, (int)((n + 16383) / 16384))), [&](size_t ci, int) {
 		for (size_t i = ci * per; i < std::min(n, (ci + 1) * per); ++i) {
 			dmnd_match& m = records[i];
-			m.evalue = E.evalue(m.hsp.score, (unsigned)(ql[m.query + 1] - ql[m.query] - 1), (unsigned)(tl[m.target + 1] - tl[m.target] - 1));
+			const size_t qc = (size_t)m.query * (size_t)h.contexts + (size_t)m.frame;      // (the HSP's own context: extend_host.hip make())
+			m.evalue = E.evalue(m.hsp.score, (unsigned)(ql[qc + 1] - ql[qc] - 1), (unsigned)(tl[m.target + 1] - tl[m.target] - 1));
 			m.bit_score = E.bitscore(m.hsp.score);
 		}
 	});

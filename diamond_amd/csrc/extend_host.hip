@@ -170,6 +170,7 @@ DeviceCfg device_cfg(const HostCfg& h)      // what the device half reads of the
 	d.ranking_chunk = ranking_chunk_size(h.ref_letters, h.max_target_seqs, h.ranking_block_letters, h.top >= 0.0);
 	d.max_swipe_dp = h.max_swipe_dp; d.use_cbs = h.use_cbs; d.max_evalue = h.max_evalue; d.min_bit_score = h.min_bit_score;
 	d.filters.min_id = h.min_id; d.filters.approx_id = h.approx_id; d.filters.query_cover = h.query_cover; d.filters.subject_cover = h.subject_cover;
+	d.contexts = h.contexts;
 	return d;
 }
 
@@ -1293,8 +1294,10 @@ struct ExtendFront {
 	std::vector<uint8_t> gf;              // gapped filter flags on the host (only when the host plans)
 	DevPlan plan;
 };
+// plan_translated: a call of six query contexts is planned on the device too (per read, plan_kernels.hip) -- asked for where the
+// device half will extend it (device_takes below) and by dmnd_extend_plan_device; otherwise the host plans it as ever.
 template<typename Lap>
-int extend_front(dmnd_ctx* c, const HostCfg& h, const dmnd_seed_hit* hits, int64_t n_hits, size_t n_queries, Lap lap, TraceLaps& trp, ExtendFront& f)
+int extend_front(dmnd_ctx* c, const HostCfg& h, const dmnd_seed_hit* hits, int64_t n_hits, size_t n_queries, Lap lap, TraceLaps& trp, ExtendFront& f, bool plan_translated)
 {
 	const std::vector<int64_t>& ql = c->limits[DMND_QUERY];
 	f.cbs = nullptr;
@@ -1353,9 +1356,9 @@ int extend_front(dmnd_ctx* c, const HostCfg& h, const dmnd_seed_hit* hits, int64
 		f.xd = reinterpret_cast<const XdropSeg*>(1);          // (set below, once it is known whether the host needs the copy)
 	}
 	lap(4, 1);
-	// The groups, segments, chains and bands of every (query, target) pair on the device (plan_kernels.hip; one query context, banded
-	// extension). DMND_EXTEND_PLAN_GPU=0: the host plans, as up to round 5.
-	f.try_plan = env_plan_gpu() && f.xd && h.contexts == 1 && n_hits < ((int64_t)1 << 31);
+	// The groups, segments, chains and bands of every (query, target) pair on the device (plan_kernels.hip; banded extension; six
+	// query contexts: per (read, target) pair). DMND_EXTEND_PLAN_GPU=0: the host plans, as up to round 5.
+	f.try_plan = env_plan_gpu() && f.xd && (h.contexts == 1 || plan_translated) && n_hits < ((int64_t)1 << 31);
 	// 1b. gapped filter of every seed hit in one launch (only --sensitive and above; extend.cpp:205-213)
 	f.gf.clear();
 	c->gf_ms = 0;
@@ -1437,28 +1440,35 @@ extern "C" int dmnd_extend(dmnd_ctx* c, const int8_t* qdata, const int8_t* tdata
 	trp.lap("queries split");
 	// One launch over the whole query block (bias_kernels.hip: closed-form window per position), result kept in HBM next to
 	// the block for the swipe kernels and the gapped filter, and copied into a pinned host buffer for the host's x-drop stage.
+	// DMND_EXTEND_DEVICE=0: all queries on the host path, as up to round 5. Read per call, like the hooks of extend_device.hip
+	// (DESIGN.md 9): a test compares the two paths in one process.
+	const bool ext_gpu = [] { const char* e = std::getenv("DMND_EXTEND_DEVICE"); return !e || e[0] != '0'; }();
+	// what the device half extends: one HSP per target, Hauser bias or none, banded extension, -k or --top; with six query contexts
+	// (blastx) only without the HSP filters -- there --query-cover is measured on the DNA read, whose length the device half does not hold
+	const bool device_takes = ext_gpu && h.max_hsps == 1 && !cbs_matrix_adjust(h.cbs_mode) && !h.ext_full
+		&& h.global_ranking == 0 && !c->same_title && h.max_target_seqs > 0 && (h.contexts == 1 || !h.have_filters());
 	ExtendFront f;
-	if (int rc = extend_front(c, h, hits, n_hits, qr.size(), lap, trp, f)) return rc;
+	if (int rc = extend_front(c, h, hits, n_hits, qr.size(), lap, trp, f, device_takes)) return rc;
 	const int8_t* const cbs = f.cbs;
 	bool bias_pending = f.bias_pending;
 	const XdropSeg* xd = f.xd;
 	const std::vector<uint8_t>& gf = f.gf;
 	DevPlan& plan = f.plan;
 	const bool planned = f.planned;
-	if (xd && (!planned || plan.n_on_host > 0)) {
+	// a translated call that was planned on the device: its lists lie there in (read, target) order, and a read that comes back to the
+	// host path is planned by the host from the call's own hits, as ever (dp stays NULL; x-drop results and filter flags are fetched then)
+	const bool tr_planned = planned && h.contexts > 1;
+	if (xd && (!planned || (plan.n_on_host > 0 && !tr_planned))) {
 		if (int rc = c->xd_host.ensure((size_t)n_hits * sizeof(XdropSeg))) return rc;      // (page-locked: allocated when first needed)
 		HIP_TRY(hipMemcpyAsync(c->xd_host.p, c->xd_out.p, (size_t)n_hits * sizeof(XdropSeg), hipMemcpyDeviceToHost, c->stream));
 		bias_pending = true;
 	}
-	if (xd) xd = c->xd_host.as<XdropSeg>();              // (NULL while no group was left to the host: nothing reads it then)
-	const DevPlan* dp = planned ? &plan : nullptr;
+	if (xd) xd = tr_planned ? nullptr : c->xd_host.as<XdropSeg>();      // (NULL while no group was left to the host: nothing reads it then; a planned translated call fetches below)
+	const DevPlan* dp = planned && !tr_planned ? &plan : nullptr;
 	// The queries are extended in HBM from here on (extend_kernels.hip), ranking chunk by ranking chunk: the default search of a
 	// protein query block -- one HSP per target, -k culling by e-value or --top culling by score, Hauser bias or none, with or without
 	// the HSP filters, with or without a transcript arena (its transcripts come first in the arena). The queries the device half hands back, and every
 	// query of any other mode, take the host path below.
-	// DMND_EXTEND_DEVICE=0: all queries on the host path, as up to round 5. Read per call, like the hooks of extend_device.hip
-	// (DESIGN.md 9): a test compares the two paths in one process.
-	const bool ext_gpu = [] { const char* e = std::getenv("DMND_EXTEND_DEVICE"); return !e || e[0] != '0'; }();
 	c->ext_records_dev = nullptr; c->ext_records_n = -1;
 	std::vector<dmnd_match> dev_records;
 	std::vector<Range> qr_host;
@@ -1467,8 +1477,7 @@ extern "C" int dmnd_extend(dmnd_ctx* c, const int8_t* qdata, const int8_t* tdata
 	for (double& x : c->ext_dev_stats) x = 0;
 	c->ext_filter_stats[0] = c->ext_filter_stats[1] = 0;
 	int64_t used_dev = 0;                                 // bytes of the caller's transcript arena the device half filled (from offset 0 on)
-	if (ext_gpu && planned && h.max_hsps == 1 && !cbs_matrix_adjust(h.cbs_mode) && !h.ext_full
-		&& h.global_ranking == 0 && !c->same_title && h.max_target_seqs > 0) {
+	if (device_takes && planned) {
 		std::vector<uint8_t> qstate;
 		double kept[12];
 		for (int i = 0; i < 12; ++i) kept[i] = c->ext_stats[i];
@@ -1482,7 +1491,18 @@ extern "C" int dmnd_extend(dmnd_ctx* c, const int8_t* qdata, const int8_t* tdata
 	}
 	const std::vector<Range>& qr_all = qr;
 	const std::vector<Range>& qr_run = on_device ? qr_host : qr_all;
-	if (planned && !qr_run.empty()) { if (int rc = plan_fetch_lists(c, plan)) return rc; bias_pending = false; }
+	if (planned && !tr_planned && !qr_run.empty()) { if (int rc = plan_fetch_lists(c, plan)) return rc; bias_pending = false; }
+	if (tr_planned && !qr_run.empty()) {
+		if (int rc = c->xd_host.ensure((size_t)n_hits * sizeof(XdropSeg))) return rc;
+		HIP_TRY(hipMemcpyAsync(c->xd_host.p, c->xd_out.p, (size_t)n_hits * sizeof(XdropSeg), hipMemcpyDeviceToHost, c->stream));
+		if (f.gf_on) {
+			f.gf.resize((size_t)n_hits);
+			HIP_TRY(hipMemcpyAsync(f.gf.data(), c->gf_flags.p, (size_t)n_hits, hipMemcpyDeviceToHost, c->stream));
+		}
+		HIP_TRY(sync_stream(c->stream));
+		bias_pending = false;
+		xd = c->xd_host.as<XdropSeg>();                      // (taken once the buffer exists: ensure() may have allocated or replaced it)
+	}
 	const uint32_t* pq_index = on_device ? pq_host.data() : nullptr;
 	double dev_stats[12];
 	for (int i = 0; i < 12; ++i) dev_stats[i] = on_device ? c->ext_stats[i] : 0.0;
@@ -1913,9 +1933,9 @@ extern "C" int dmnd_extend_plan_device(dmnd_ctx* c, const dmnd_seed_hit* hits, i
 	TraceLaps trp("dmnd_extend_plan_device");
 	const std::vector<Range> qr = split_by_query(hits, n_hits, h.contexts);
 	ExtendFront f;
-	if (int rc = extend_front(c, h, hits, n_hits, qr.size(), [](int, int = -1) {}, trp, f)) return rc;
+	if (int rc = extend_front(c, h, hits, n_hits, qr.size(), [](int, int = -1) {}, trp, f, true)) return rc;
 	if (f.bias_pending) HIP_TRY(sync_stream(c->stream));
-	if (n_hits > 0 && !f.try_plan) return fail(DMND_E_ARG, "dmnd_extend_plan_device: this configuration is planned by the host (translated queries, --ext full, DMND_EXTEND_PLAN_GPU=0 or DMND_EXTEND_XDROP_GPU=0)");
+	if (n_hits > 0 && !f.try_plan) return fail(DMND_E_ARG, "dmnd_extend_plan_device: this configuration is planned by the host (--ext full, DMND_EXTEND_PLAN_GPU=0 or DMND_EXTEND_XDROP_GPU=0)");
 	info->unsorted = f.plan.unsorted ? 1 : 0;
 	if (!f.planned) return DMND_OK;
 	DevPlan& plan = f.plan;
@@ -1925,17 +1945,24 @@ extern "C" int dmnd_extend_plan_device(dmnd_ctx* c, const dmnd_seed_hit* hits, i
 	info->n_chain = plan.n_chain; info->n_chain_big = plan.n_chain_big; info->n_relisted = plan.n_relisted;
 	if ((int64_t)plan.n_groups > group_cap || (int64_t)plan.n_bands > row_cap) return fail(DMND_E_CAP, "dmnd_extend_plan_device: output buffer too small");
 	int64_t n_rows = 0;
+	const bool translated = h.contexts > 1;      // groups = (read, target) pairs, `query` of a group = the read's context 0; rows carry their own context
+	uint32_t q_at = 0;
 	for (uint32_t g = 0; g < plan.n_groups; ++g) {
 		const PlanGroup& pg = plan.groups[g];
-		const uint32_t query = hits[pg.hit_begin].query;
+		while (translated && plan.queries[q_at + 1].group_begin <= g) ++q_at;
+		// (translated: hit_begin counts in the planner's (read, target) order, not in the caller's list)
+		const uint32_t query = translated ? plan.queries[q_at].query * (uint32_t)h.contexts : hits[pg.hit_begin].query;
 		const bool on_host = pg.n_bands == PLAN_ON_HOST;
 		groups[g] = dmnd_plan_group{ query, pg.target, pg.n_hits, on_host ? 0u : (uint32_t)pg.n_bands, pg.pass, (uint8_t)(on_host ? 1 : 0), { 0, 0 } };
 		if (on_host) continue;
 		if (pg.band_begin + (uint32_t)pg.n_bands > plan.n_bands) return fail(DMND_E_CAP, "dmnd_extend_plan_device: a group's bands lie outside the band list");
 		for (uint32_t k = 0; k < pg.n_bands; ++k)
-			rows[n_rows++] = dmnd_plan_target{ query, pg.target, plan.bands[pg.band_begin + k].d_begin, plan.bands[pg.band_begin + k].d_end, (int32_t)pg.score };
+			rows[n_rows++] = dmnd_plan_target{ translated ? plan.band_query[pg.band_begin + k] : query, pg.target, plan.bands[pg.band_begin + k].d_begin, plan.bands[pg.band_begin + k].d_end,
+				translated ? (int32_t)plan.ungapped0[g] : (int32_t)pg.score };
 	}
-	if (n_rows != (int64_t)plan.n_bands) return fail(DMND_E_CAP, "dmnd_extend_plan_device: the groups' band counts do not add up to the band list");
+	// (translated: a pair left to the host because of one frame has no rows here, while the band list still holds its other frames' bands)
+	if (translated) info->n_bands = n_rows;
+	else if (n_rows != (int64_t)plan.n_bands) return fail(DMND_E_CAP, "dmnd_extend_plan_device: the groups' band counts do not add up to the band list");
 	return DMND_OK;
 }
 

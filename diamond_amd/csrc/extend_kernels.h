@@ -40,6 +40,10 @@ struct ExtArgs {
 	uint32_t n_groups, n_queries, n_bands;
 	const dmnd_seed_hit* hits;
 	const int64_t* qlimits; const int64_t* tlimits;
+	// translated queries (contexts = 6; NULL otherwise): a group is a (read, target) pair, a query a read; every band carries its
+	// context, and the record's ungapped score is context 0's
+	int contexts;
+	const uint32_t* band_query; const uint16_t* ungapped0;
 	int use_cbs;
 	uint32_t row_min_items;        // items of an iteration from which on the row classes of the packed 16-bit sweeps are used (sweep_rows_min_items)
 	uint32_t chunk_size;           // ranking_chunk_size

@@ -93,11 +93,12 @@ __global__ __launch_bounds__(64) void ext_mark_kernel(ExtArgs a)
 	const uint32_t q = blockIdx.x, lane = threadIdx.x;
 	const uint32_t g0 = a.queries[q].group_begin, g1 = a.queries[q + 1].group_begin, ng = g1 - g0;
 	const uint32_t query = a.queries[q].query;
-	const int qlen = (int)(a.qlimits[query + 1] - a.qlimits[query] - 1);
+	// (translated queries: every band is checked with the length of its own context, below)
+	const int qlen1 = a.band_query ? 1 : (int)(a.qlimits[query + 1] - a.qlimits[query] - 1);
 	// more groups than a chunk: ranked in chunks (extend.cpp:289-336). A first chunk smaller than -k would grow by the e-value of
 	// the seed-hit scores (extend.cpp:262-268): those queries stay on the host
 	// (--top: the chunk is 128 x block_mult whatever -k is, and the growth rule does not apply)
-	bool bad = ng > EXT_MAX_GROUPS || qlen <= 0 || (!a.top_on && ng > a.chunk_size && (uint32_t)a.k > a.chunk_size);
+	bool bad = ng > EXT_MAX_GROUPS || qlen1 <= 0 || (!a.top_on && ng > a.chunk_size && (uint32_t)a.k > a.chunk_size);
 	if (!bad)
 		for (uint32_t g = g0 + lane; g < g1; g += 64) {
 			const PlanGroup grp = a.groups[g];
@@ -108,8 +109,10 @@ __global__ __launch_bounds__(64) void ext_mark_kernel(ExtArgs a)
 			for (uint32_t k = 0; k < grp.n_bands; ++k) {
 				const PlanBand b = a.bands[grp.band_begin + k];
 				const int band = b.d_end - b.d_begin;
+				int qlen = qlen1;
+				if (a.band_query) { const uint32_t bq = a.band_query[grp.band_begin + k]; qlen = (int)(a.qlimits[bq + 1] - a.qlimits[bq] - 1); }
 				const dmnd_dp_target d{ 0, 0, 0, qlen, tlen, b.d_begin, b.d_end };
-				if (band <= 0 || band_class(band) > 32 || ext_cells(d) > a.max_swipe_dp) bad = true;
+				if (qlen <= 0 || band <= 0 || band_class(band) > 32 || ext_cells(d) > a.max_swipe_dp) bad = true;
 			}
 		}
 	const bool ok = __ballot(bad) == 0;
@@ -190,13 +193,19 @@ __global__ __launch_bounds__(256) void ext_items_kernel(ExtArgs a)
 		if (n) {
 			const PlanGroup grp = a.groups[g];
 			const uint32_t query = a.hits[grp.hit_begin].query;
-			const int64_t q0 = a.qlimits[query], t0 = a.tlimits[grp.target];
-			const int qlen = (int)(a.qlimits[query + 1] - q0 - 1), tlen = (int)(a.tlimits[grp.target + 1] - t0 - 1);
+			int64_t q0 = a.qlimits[query];
+			const int64_t t0 = a.tlimits[grp.target];
+			int qlen = (int)(a.qlimits[query + 1] - q0 - 1);
+			const int tlen = (int)(a.tlimits[grp.target + 1] - t0 - 1);
 			const uint32_t local = a.item_off[g], first = a.item_base + local;
 			a.g_first[g] = first; a.g_cnt[g] = n;
 			unsigned long long cells = 0, diag = 0, lanes = 0;
 			for (uint32_t k = 0; k < n; ++k) {
 				const PlanBand b = a.bands[grp.band_begin + k];
+				if (a.band_query) {      // the item reads the sequence, bias and length of its band's context
+					const uint32_t bq = a.band_query[grp.band_begin + k];
+					q0 = a.qlimits[bq]; qlen = (int)(a.qlimits[bq + 1] - q0 - 1);
+				}
 				const dmnd_dp_target d{ q0, t0, a.use_cbs ? q0 : (int64_t)-1, qlen, tlen, b.d_begin, b.d_end };
 				a.items[first + k] = d;
 				const Geom geom = make_geom(qlen, tlen, b.d_begin, b.d_end);
@@ -272,9 +281,11 @@ __device__ inline bool sel_less(const SelSlot& x, const SelSlot& y)      // Targ
 // the host's own e-values could order the two the other way round (equal inputs give equal values on both sides). Two e-values
 // that are 0.0 on both sides are ordered by score and target exactly, as the host orders them; next to the underflow the
 // relative tolerance means nothing, and two tiny values are always flagged
-__device__ inline bool sel_ambiguous(const ExtEvalue& p, const SelSlot& x, const SelSlot& y)
+// (translated queries: equal inputs also means contexts of equal length, read from the best items of the two groups)
+__device__ inline bool sel_ambiguous(const ExtArgs& a, const SelSlot& x, const SelSlot& y)
 {
-	if (x.score == y.score && x.tlen == y.tlen) return false;
+	const ExtEvalue& p = a.ev;
+	if (x.score == y.score && x.tlen == y.tlen && (a.contexts <= 1 || a.items[a.cand_item[x.g]].query_len == a.items[a.cand_item[y.g]].query_len)) return false;
 	const int ux = ext_underflow(p, x.score), uy = ext_underflow(p, y.score);
 	if (ux == 2 && uy == 2) return false;
 	if ((ux == 1 || uy == 1) && fmax(x.ev, y.ev) < 1e-250) return true;
@@ -316,8 +327,6 @@ __global__ __launch_bounds__(64) void ext_append_kernel(ExtArgs a, int last)
 	const uint32_t cap_al = (uint32_t)a.k + a.chunk_size;
 	const uint32_t g0 = a.queries[q].group_begin, g1 = a.queries[q + 1].group_begin, ng = g1 - g0;
 	const uint32_t i0 = a.q_i0[q], i1 = a.q_i1[q];
-	const uint32_t query = a.queries[q].query;
-	const int qlen = (int)(a.qlimits[query + 1] - a.qlimits[query] - 1);
 	if (lane == 0) { n_v_sh = 0; flags_sh = 0; }
 	__syncthreads();
 	bool amb = false, sat = false;
@@ -326,16 +335,17 @@ __global__ __launch_bounds__(64) void ext_append_kernel(ExtArgs a, int last)
 		const uint32_t target = a.groups[g].target;
 		const int tlen = (int)(a.tlimits[target + 1] - a.tlimits[target] - 1);
 		// best HSP of the target among its bands that pass the report cutoff (gapped_score.cpp:182-268; Target::add_hit + inner_culling:
-		// the highest score, of equal ones the band that starts first)
+		// the highest score, of equal ones the band that starts first; over several contexts best_hsp_replaces, plan_core.h)
 		bool have = false;
 		int best = 0; uint32_t bi = 0; double bev = 0;
 		for (uint32_t k = 0; k < n; ++k) {
 			const SwipeEnd e = a.ends[first + k];
 			if (e.pad[0]) sat = true;
 			if (e.score <= 0) continue;
-			const double ev = ext_evalue(a.ev, e.score, qlen, tlen);
+			const dmnd_dp_target it = a.items[first + k];      // (the e-value is that of the item's own context)
+			const double ev = ext_evalue(a.ev, e.score, it.query_len, tlen);
 			if (!ext_reported(a, e.score, ev, amb)) continue;
-			if (!have || e.score > best || (e.score == best && a.items[first + k].d_begin < a.items[bi].d_begin)) { have = true; best = e.score; bi = first + k; bev = ev; }
+			if (!have || best_hsp_replaces(e.score, it.query_off, it.d_begin, best, a.items[bi].query_off, a.items[bi].d_begin)) { have = true; best = e.score; bi = first + k; bev = ev; }
 		}
 		a.cand_item[g] = bi;
 		a.cand_ev[g] = bev;
@@ -356,7 +366,7 @@ __global__ __launch_bounds__(64) void ext_append_kernel(ExtArgs a, int last)
 				uint32_t rank = 0;
 				for (uint32_t y = 0; y < na; ++y) {
 					if (y == x) continue;
-					if (sel_ambiguous(a.ev, al[y], me)) amb = true;
+					if (sel_ambiguous(a, al[y], me)) amb = true;
 					rank += sel_less(al[y], me) ? 1u : 0u;
 				}
 				if (rank >= (uint32_t)a.k) a.aligned[me.g] = 0;
@@ -367,7 +377,7 @@ __global__ __launch_bounds__(64) void ext_append_kernel(ExtArgs a, int last)
 			const SelSlot ks = kth_slot;
 			bool reach = false;
 			for (uint32_t x = lane; x < n_v; x += 64) {
-				if (sel_ambiguous(a.ev, vs[x], ks)) amb = true;
+				if (sel_ambiguous(a, vs[x], ks)) amb = true;
 				reach |= vs[x].ev <= kth;
 			}
 			if (__ballot(reach) != 0) new_hits = true;
@@ -424,7 +434,7 @@ __global__ __launch_bounds__(64) void ext_final_kernel(ExtArgs a)
 				uint32_t rank = 0;
 				for (uint32_t y = 0; y < na; ++y) {
 					if (y == x) continue;
-					if (sel_ambiguous(a.ev, lds[y], me)) amb = true;
+					if (sel_ambiguous(a, lds[y], me)) amb = true;
 					rank += sel_less(lds[y], me) ? 1u : 0u;
 				}
 				keep = rank < (uint32_t)a.k;
@@ -505,6 +515,14 @@ __global__ __launch_bounds__(256) void ext_rewalk_kernel(ExtArgs a, uint32_t n_k
 	if (k < n_kept && a.r2_off[k] < 0) a.r2_off[k] = a.off_item[a.r2_order[k]];
 }
 
+// the frame of a record: the context of the read whose sequence the winning item reads (0 for an untranslated query)
+__device__ inline int32_t ext_frame(const ExtArgs& a, uint32_t read, const dmnd_dp_target& d)
+{
+	for (int f = a.contexts - 1; f > 0; --f)
+		if (a.qlimits[(size_t)read * (size_t)a.contexts + (size_t)f] == d.query_off) return f;
+	return 0;
+}
+
 __global__ __launch_bounds__(64) void ext_records_kernel(ExtArgs a)
 {
 	extern __shared__ SelSlot lds[];
@@ -524,8 +542,8 @@ __global__ __launch_bounds__(64) void ext_records_kernel(ExtArgs a)
 		const dmnd_dp_target d = a.items[item];
 		dmnd_match& m = a.records[first + rank];             // (field by field into HBM: a local record would live in scratch memory)
 		m.query = query; m.target = me.target;
-		m.ungapped_score = (int32_t)a.groups[g].score; m.d_begin = d.d_begin; m.d_end = d.d_end;
-		m.frame = 0; m.read_begin = 0; m.read_end = 0;
+		m.ungapped_score = a.ungapped0 ? (int32_t)a.ungapped0[g] : (int32_t)a.groups[g].score; m.d_begin = d.d_begin; m.d_end = d.d_end;
+		m.frame = ext_frame(a, query, d); m.read_begin = 0; m.read_end = 0;
 		m.evalue = me.ev; m.bit_score = 0.0;                  // the host writes its own e-value and the bit score
 		const dmnd_hsp hsp = a.hsps[item];
 		m.hsp.score = hsp.score; m.hsp.q_begin = hsp.q_begin; m.hsp.q_end = hsp.q_end; m.hsp.s_begin = hsp.s_begin; m.hsp.s_end = hsp.s_end;
@@ -553,8 +571,6 @@ __global__ __launch_bounds__(64) void ext_fcand_kernel(ExtArgs a)
 	if (!a.q_active[q]) return;
 	const uint32_t g0 = a.queries[q].group_begin, g1 = a.queries[q + 1].group_begin, ng = g1 - g0;
 	const uint32_t i0 = a.q_i0[q], i1 = a.q_i1[q];
-	const uint32_t query = a.queries[q].query;
-	const int qlen = (int)(a.qlimits[query + 1] - a.qlimits[query] - 1);
 	bool amb = false, sat = false;
 	for (uint32_t w = i0 + lane; w < i1; w += 64) {
 		const uint32_t g = a.gorder[g0 + w], n = a.g_cnt[g], first = a.g_first[g];
@@ -566,9 +582,10 @@ __global__ __launch_bounds__(64) void ext_fcand_kernel(ExtArgs a)
 			const SwipeEnd e = a.ends[first + k];
 			if (e.pad[0]) sat = true;
 			if (e.score <= 0) continue;
-			const double ev = ext_evalue(a.ev, e.score, qlen, tlen);
+			const dmnd_dp_target it = a.items[first + k];      // (the e-value is that of the item's own context)
+			const double ev = ext_evalue(a.ev, e.score, it.query_len, tlen);
 			if (!ext_reported(a, e.score, ev, amb)) continue;
-			if (!have || e.score > best || (e.score == best && a.items[first + k].d_begin < a.items[bi].d_begin)) { have = true; best = e.score; bi = first + k; bev = ev; }
+			if (!have || best_hsp_replaces(e.score, it.query_off, it.d_begin, best, a.items[bi].query_off, a.items[bi].d_begin)) { have = true; best = e.score; bi = first + k; bev = ev; }
 		}
 		a.cand_item[g] = bi;
 		a.cand_ev[g] = bev;
@@ -608,7 +625,7 @@ __device__ inline bool rank_list(const ExtArgs& a, const SelSlot* list, uint32_t
 		uint32_t rank = 0;
 		for (uint32_t y = 0; y < n; ++y) {
 			if (y == x) continue;
-			if (sel_ambiguous(a.ev, list[y], me)) amb = true;
+			if (sel_ambiguous(a, list[y], me)) amb = true;
 			rank += sel_less(list[y], me) ? 1u : 0u;
 		}
 		rank_of[x] = (uint16_t)rank;
@@ -660,7 +677,7 @@ __global__ __launch_bounds__(64) void ext_fappend_kernel(ExtArgs a, int last, ui
 		const SelSlot ks = kth_slot;
 		bool reach = false;
 		for (uint32_t x = na + lane; x < n; x += 64) {
-			if (sel_ambiguous(a.ev, list[x], ks)) amb = true;
+			if (sel_ambiguous(a, list[x], ks)) amb = true;
 			reach |= list[x].ev <= ks.ev;
 		}
 		new_hits = __ballot(reach) != 0;
@@ -757,7 +774,7 @@ __global__ __launch_bounds__(64) void ext_ffinal_kernel(ExtArgs a)
 				uint32_t rank = 0;
 				for (uint32_t y = 0; y < nm; ++y) {
 					if (y == x) continue;
-					if (sel_ambiguous(a.ev, list[y], me)) amb = true;
+					if (sel_ambiguous(a, list[y], me)) amb = true;
 					rank += sel_less(list[y], me) ? 1u : 0u;
 				}
 				keep = rank < (uint32_t)a.k;
@@ -797,8 +814,6 @@ __global__ __launch_bounds__(64) void ext_top_append_kernel(ExtArgs a, int last)
 	if (!a.q_active[q]) return;
 	const uint32_t g0 = a.queries[q].group_begin, g1 = a.queries[q + 1].group_begin, ng = g1 - g0;
 	const uint32_t i0 = a.q_i0[q], i1 = a.q_i1[q];
-	const uint32_t query = a.queries[q].query;
-	const int qlen = (int)(a.qlimits[query + 1] - a.qlimits[query] - 1);
 	bool amb = false, sat = false;
 	int max_v = 0;
 	for (uint32_t w = i0 + lane; w < i1; w += 64) {
@@ -812,9 +827,10 @@ __global__ __launch_bounds__(64) void ext_top_append_kernel(ExtArgs a, int last)
 			const SwipeEnd e = a.ends[first + k];
 			if (e.pad[0]) sat = true;
 			if (e.score <= 0) continue;
-			const double ev = ext_evalue(a.ev, e.score, qlen, tlen);
+			const dmnd_dp_target it = a.items[first + k];      // (the e-value is that of the item's own context)
+			const double ev = ext_evalue(a.ev, e.score, it.query_len, tlen);
 			if (!ext_reported(a, e.score, ev, amb)) continue;
-			if (!have || e.score > best || (e.score == best && a.items[first + k].d_begin < a.items[bi].d_begin)) { have = true; best = e.score; bi = first + k; bev = ev; }
+			if (!have || best_hsp_replaces(e.score, it.query_off, it.d_begin, best, a.items[bi].query_off, a.items[bi].d_begin)) { have = true; best = e.score; bi = first + k; bev = ev; }
 		}
 		a.cand_item[g] = bi;
 		a.cand_ev[g] = bev;
@@ -959,7 +975,7 @@ __global__ __launch_bounds__(256) void ext_top_keys_kernel(ExtArgs a, uint32_t n
 	if (k < n) {
 		const uint32_t g = a.r2_group[k];
 		rec = a.kept[g] != 0;
-		const uint32_t query = a.hits[a.groups[g].hit_begin].query;
+		const uint32_t query = a.hits[a.groups[g].hit_begin].query / (uint32_t)a.contexts;      // (the read)
 		a.okeys[k] = rec ? ((uint64_t)query << 32) | (uint64_t)(0xffffffffu - (uint32_t)a.cand_score[g]) : ~(uint64_t)0;
 		a.oidx[k] = k;
 	}
@@ -976,9 +992,9 @@ __global__ __launch_bounds__(256) void ext_top_records_kernel(ExtArgs a, uint32_
 	const PlanGroup grp = a.groups[g];
 	const dmnd_dp_target d = a.items[item];
 	dmnd_match& m = a.records[i];                            // (field by field into HBM: a local record would live in scratch memory)
-	m.query = a.hits[grp.hit_begin].query; m.target = grp.target;
-	m.ungapped_score = (int32_t)grp.score; m.d_begin = d.d_begin; m.d_end = d.d_end;
-	m.frame = 0; m.read_begin = 0; m.read_end = 0;
+	m.query = a.hits[grp.hit_begin].query / (uint32_t)a.contexts; m.target = grp.target;
+	m.ungapped_score = a.ungapped0 ? (int32_t)a.ungapped0[g] : (int32_t)grp.score; m.d_begin = d.d_begin; m.d_end = d.d_end;
+	m.frame = ext_frame(a, m.query, d); m.read_begin = 0; m.read_end = 0;
 	m.evalue = a.cand_ev[g]; m.bit_score = 0.0;               // the host writes its own e-value and the bit score
 	const dmnd_hsp hsp = a.hsps[item];
 	m.hsp.score = hsp.score; m.hsp.q_begin = hsp.q_begin; m.hsp.q_end = hsp.q_end; m.hsp.s_begin = hsp.s_begin; m.hsp.s_end = hsp.s_end;

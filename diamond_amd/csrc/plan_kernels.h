@@ -10,6 +10,7 @@
 #include <stdint.h>
 #include "../../include/diamond_hip.h"
 #include "xdrop_core.h"
+#include "plan_core.h"
 
 namespace dmnd {
 
@@ -30,8 +31,8 @@ struct PlanGroup {             // the seed hits of one (query, target) pair = Se
 	uint8_t n_bands;           // DpTargets of round 1, or PLAN_ON_HOST
 };
 struct PlanBand { int32_t d_begin, d_end; };
-struct PlanQuery { uint32_t query, group_begin, hit_begin; };      // one per query that has hits, in hit order; one sentinel entry behind the last
-struct PlanCounters { uint32_t n_groups, n_queries, n_bands, unsorted, n_on_host, n_chain, n_chain_big, n_relisted; };      // n_chain / n_chain_big: groups with two to PLAN_SMALL_SEGS / more segments (plan_chain_list_kernel); n_relisted: small ones listed again for the large workspace (counted in n_chain_big too)
+struct PlanQuery { uint32_t query, group_begin, hit_begin; };      // one per query that has hits, in hit order; one sentinel entry behind the last (translated queries: the read, its first PAIR)
+struct PlanCounters { uint32_t n_groups, n_queries, n_bands, unsorted, n_on_host, n_chain, n_chain_big, n_relisted, n_pairs, n_pairs_on_host; };      // n_chain / n_chain_big: groups with two to PLAN_SMALL_SEGS / more segments (plan_chain_list_kernel); n_relisted: small ones listed again for the large workspace (counted in n_chain_big too)
 
 struct PlanArgs {
 	const int8_t* qblock; const int8_t* tblock;
@@ -57,6 +58,21 @@ struct PlanArgs {
 	PlanBand* bands;               // dense
 	PlanCounters* counters;
 	void** scan_tmp; size_t* scan_tmp_bytes;
+	// Translated queries (contexts = 6; every pointer below NULL otherwise). The call's hits arrive context after context; a stable radix
+	// sort by (read, target) (plan_core.h) brings them into (read, target, frame, location, seed offset) order, and hits / gf_flags / xd
+	// above are the permuted copies. `groups` stay the (context, target) units that segments, chaining and bands are made for; one
+	// level above them the (read, target) PAIRS of up to six consecutive units are what the device half ranks and reports.
+	int contexts;
+	const dmnd_seed_hit* hits_in; const uint8_t* gf_in; const XdropSeg* xd_in;      // the call's lists as they arrive
+	dmnd_seed_hit* hits_sorted; uint8_t* gf_sorted; XdropSeg* xd_sorted;
+	uint64_t* keys; uint64_t* keys_sorted; uint32_t* perm_in; uint32_t* perm;         // perm[k]: where sorted hit k lay in the call's list
+	int target_bits, key_bits;
+	uint32_t* pheads; uint32_t* phead_scan;        // pair head flag of every hit, inclusive scan
+	PlanGroup* pairs;              // (+ 1) score: the best over all frames; pass: some hit of the pair passed; n_bands: all its units' bands, which lie one after the other
+	uint32_t* pair_unit;           // (+ 1) first unit of every pair
+	uint32_t* unit_pair;
+	uint16_t* ungapped0;           // per pair: best stage-1 score of context 0, 0 without a hit there (the record's ungapped_score)
+	uint32_t* band_query;          // per band of the dense list: the context (block sequence id) it belongs to
 };
 
 hipError_t launch_plan(const PlanArgs& a, hipStream_t st);

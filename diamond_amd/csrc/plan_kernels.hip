@@ -17,12 +17,20 @@
 //   plan_segments_kernel per group: score, filter flag, sorted segments; single-segment groups are finished here
 //   plan_chain_list_kernel, plan_chain_kernel<small> / <large>    per multi-segment group: chaining + band merge
 //   rocPRIM exclusive scan of the band counts, plan_gather_kernel: dense band list
+// Translated queries (PlanArgs::contexts = 6) arrive context after context and are grouped per READ (load_hits.h:44-127 over the six
+// frames). In front of the kernels above: plan_key_kernel (target, order check, sort key of every hit), a stable rocPRIM radix sort by
+// (read, target), plan_permute_kernel (hits, x-drop results and filter flags in the new order; unit / pair / read head flags). Groups
+// are then the (context, target) units, with four rules read from the pair they belong to (ungapped.cpp:76-116, gapped_score.cpp:107):
+// the pass flag is the pair's, a pair of ONE hit is a one-diagonal chain of that hit's score without x-drop test, a hit is skipped
+// inside the previous segment of its own frame, and the band half-width is that of context 0. Behind them plan_pairs_kernel sums the
+// units of a pair up into the record the device half ranks.
 // A group with more than PLAN_MAX_HITS hits or PLAN_MAX_SEGS segments, or whose chaining outgrows the fixed arrays, is marked
 // PLAN_ON_HOST and planned by the host as before (extend_host.hip plan_groups): same result either way.
 // Compiled with -ffp-contract=off: the chaining truncates double expressions to int (joined_score, faded) exactly as the host does.
 #include <hip/hip_runtime.h>
 #include <climits>
 #include <rocprim/device/device_scan.hpp>
+#include <rocprim/device/device_radix_sort.hpp>
 #include "plan_kernels.h"
 #include "chain_graph.h"
 
@@ -34,6 +42,53 @@ __device__ inline int band_for_dev(int len, bool fast)           // Extension::b
 {
 	if (fast) return len < 50 ? 12 : len < 100 ? 16 : len < 250 ? 30 : len < 350 ? 40 : 64;
 	return len < 50 ? 15 : len < 100 ? 20 : len < 150 ? 30 : len < 200 ? 50 : len < 250 ? 60 : len < 350 ? 100 : len < 500 ? 120 : 150;
+}
+
+// the length Extension::band is asked with: the query's, for a translated read that of its context 0 (gapped_score.cpp:107, extend_host.hip plan_groups)
+__device__ inline int band_len(const PlanArgs& a, uint32_t query, int qlen)
+{
+	if (a.contexts <= 1) return qlen;
+	const uint32_t c0 = query / (uint32_t)a.contexts * (uint32_t)a.contexts;
+	return (int)(a.qlimits[c0 + 1] - a.qlimits[c0] - 1);
+}
+
+// translated queries: target and sort key of every hit of the call's list, order check
+__global__ __launch_bounds__(256) void plan_key_kernel(PlanArgs a)
+{
+	const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (k >= a.n_hits) return;
+	const dmnd_seed_hit h = a.hits_in[k];
+	int64_t lo = 0, hi = a.n_targets;
+	while (lo + 1 < hi) { const int64_t mid = (lo + hi) >> 1; if (a.tlimits[mid] <= h.subject) lo = mid; else hi = mid; }
+	if (k > 0) {
+		const dmnd_seed_hit p = a.hits_in[k - 1];
+		if (p.query > h.query || (p.query == h.query && (p.subject > h.subject || (p.subject == h.subject && p.seed_offset > h.seed_offset)))) a.counters->unsorted = 1;
+	}
+	a.keys[k] = plan_pair_key(h.query / (uint32_t)a.contexts, (uint32_t)lo, a.target_bits);
+	a.perm_in[k] = (uint32_t)k;
+}
+
+// ... and behind the sort: the lists in (read, target, frame, location, seed offset) order, unit | read head flags, pair head flags
+__global__ __launch_bounds__(256) void plan_permute_kernel(PlanArgs a)
+{
+	const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (k >= a.n_hits) return;
+	const uint32_t src = a.perm[k];
+	const dmnd_seed_hit h = a.hits_in[src];
+	const uint64_t key = a.keys_sorted[k];
+	a.hits_sorted[k] = h;
+	a.xd_sorted[k] = a.xd_in[src];
+	if (a.gf_in) a.gf_sorted[k] = a.gf_in[src];
+	a.tgt[k] = plan_key_target(key, a.target_bits);
+	uint64_t gh = 1, qh = 1, ph = 1;
+	if (k > 0) {
+		const uint64_t pkey = a.keys_sorted[k - 1];
+		ph = pkey != key;
+		qh = plan_key_read(pkey, a.target_bits) != plan_key_read(key, a.target_bits);
+		gh = ph || a.hits_in[a.perm[k - 1]].query != h.query;
+	}
+	a.heads[k] = gh | (qh << 32);
+	a.pheads[k] = (uint32_t)ph;
 }
 
 __global__ __launch_bounds__(256) void plan_mark_kernel(PlanArgs a)
@@ -61,6 +116,20 @@ __global__ __launch_bounds__(256) void plan_fill_kernel(PlanArgs a)
 	const uint64_t s = a.head_scan[k], f = a.heads[k];
 	const uint32_t g = (uint32_t)s - 1, q = (uint32_t)(s >> 32) - 1;
 	if (f & 1u) { a.groups[g].hit_begin = (uint32_t)k; a.groups[g].target = a.tgt[k]; }
+	if (a.contexts > 1) {
+		// units, pairs and reads: a read's record points at its first pair
+		const uint32_t p = a.phead_scan[k] - 1;
+		if (f & 1u) a.unit_pair[g] = p;
+		if (a.pheads[k]) { a.pairs[p].hit_begin = (uint32_t)k; a.pairs[p].target = a.tgt[k]; a.pair_unit[p] = g; }
+		if (f >> 32) a.queries[q] = PlanQuery{ a.hits[k].query / (uint32_t)a.contexts, p, (uint32_t)k };
+		if (k == a.n_hits - 1) {
+			a.counters->n_groups = g + 1; a.counters->n_queries = q + 1; a.counters->n_pairs = p + 1;
+			a.groups[g + 1].hit_begin = (uint32_t)a.n_hits;
+			a.pairs[p + 1].hit_begin = (uint32_t)a.n_hits; a.pair_unit[p + 1] = g + 1;
+			a.queries[q + 1] = PlanQuery{ 0xffffffffu, p + 1, (uint32_t)a.n_hits };
+		}
+		return;
+	}
 	if (f >> 32) a.queries[q] = PlanQuery{ a.hits[k].query, g, (uint32_t)k };
 	if (k == a.n_hits - 1) {
 		a.counters->n_groups = g + 1; a.counters->n_queries = q + 1;
@@ -117,6 +186,13 @@ __global__ __launch_bounds__(64) void plan_segments_kernel(PlanArgs a)
 		score = chain_max(score, (int)(uint16_t)a.hits[k].score);
 		if (a.gf_flags) pass |= a.gf_flags[k] != 0;
 	}
+	bool single = false;                       // translated: the one seed hit of a (read, target) pair (ungapped.cpp:76-80)
+	if (a.contexts > 1) {
+		// the pass flag is the pair's: some hit of it, whatever its frame, passed the filter
+		const uint32_t p = a.unit_pair[g], pb = a.pairs[p].hit_begin, pe = a.pairs[p + 1].hit_begin;
+		single = pe - pb == 1;
+		if (a.gf_flags) for (uint32_t k = pb; k < pe && !pass; ++k) pass = a.gf_flags[k] != 0;
+	}
 	grp.n_hits = n; grp.score = (uint16_t)score; grp.pass = pass ? 1 : 0; grp.band_begin = 0; grp.n_bands = 0;
 	if (!pass) { a.groups[g] = grp; return; }                        // dropped before chaining (extend.cpp:205-213)
 	if (n > PLAN_MAX_HITS) { grp.n_bands = PLAN_ON_HOST; a.groups[g] = grp; return; }
@@ -124,6 +200,18 @@ __global__ __launch_bounds__(64) void plan_segments_kernel(PlanArgs a)
 	const int tlen = (int)(a.tlimits[grp.target + 1] - t0 - 1);
 	const uint32_t query = a.hits[b].query;
 	const int qlen = (int)(a.qlimits[query + 1] - a.qlimits[query] - 1);
+	const int base_band = band_for_dev(band_len(a, query, qlen), a.band_fast != 0);
+	if (single) {
+		// a one-diagonal chain of the hit's own score: no x-drop walk, no positive-score test
+		const dmnd_seed_hit h = a.hits[b];
+		const int d = h.seed_offset - (int)(h.subject - t0);
+		const Chain c{ d, d, (int)h.score, 0, 0, 0, 0 };
+		BandOut out{ a.band_slots + b, 1, 0, false };
+		merge_bands(&c, 1, base_band, qlen, tlen, out);
+		grp.n_bands = (uint8_t)out.n;
+		a.groups[g] = grp;
+		return;
+	}
 	// the group's hits sorted by (diagonal, j) -- they arrive sorted by (j, i)
 	for (uint32_t x = 0; x < n; ++x) {
 		const dmnd_seed_hit h = a.hits[b + x];
@@ -147,7 +235,7 @@ __global__ __launch_bounds__(64) void plan_segments_kernel(PlanArgs a)
 		const int d = L.hi[0][lane] - L.hj[0][lane];
 		const Chain c{ d, d, L.ss[0][lane], 0, 0, 0, 0 };
 		BandOut out{ a.band_slots + b, (int)n, 0, false };
-		merge_bands(&c, 1, band_for_dev(qlen, a.band_fast != 0), qlen, tlen, out);
+		merge_bands(&c, 1, base_band, qlen, tlen, out);
 		grp.n_bands = (uint8_t)out.n;
 		a.groups[g] = grp;
 		return;
@@ -251,7 +339,7 @@ __global__ __launch_bounds__(64) void plan_chain_kernel(PlanArgs a)
 	grp.band_begin = 0;
 	insertion_sort(L.chains.begin(), L.chains.end(), [](const Chain& x, const Chain& y) { return x.d_min < y.d_min; });      // std::stable_sort by d_min
 	BandOut out{ a.band_slots + b, (int)grp.n_hits, 0, false };
-	merge_bands(L.chains, (int)L.chains.size(), band_for_dev(qlen, a.band_fast != 0), qlen, tlen, out);
+	merge_bands(L.chains, (int)L.chains.size(), band_for_dev(band_len(a, query, qlen), a.band_fast != 0), qlen, tlen, out);
 	// (a guard no input reaches: at most CHAINS = 16 chains give at most 16 bands, below PLAN_NEED_CHAIN)
 	grp.n_bands = out.overflow || out.n >= PLAN_NEED_CHAIN ? (uint8_t)PLAN_ON_HOST : (uint8_t)out.n;
 	a.groups[g] = grp;
@@ -280,7 +368,41 @@ __global__ __launch_bounds__(256) void plan_gather_kernel(PlanArgs a)
 	const uint32_t off = a.band_off[g];
 	if (grp.n_bands != PLAN_ON_HOST)
 		for (uint32_t k = 0; k < grp.n_bands; ++k) a.bands[off + k] = a.band_slots[grp.hit_begin + k];
+	if (a.band_query && grp.n_bands != PLAN_ON_HOST) {
+		const uint32_t query = a.hits[grp.hit_begin].query;      // every band carries its context
+		for (uint32_t k = 0; k < grp.n_bands; ++k) a.band_query[off + k] = query;
+	}
 	a.groups[g].band_begin = off;
+}
+
+// translated queries: the (read, target) pair over its units -- its bands are its units' bands, which follow each other in the dense
+// list; ranking score = the best over all frames; the score that travels into the record = context 0's; one unit left to the host
+// leaves the pair to the host. (At most six units of at most PLAN_MAX_SEGS bands: the sum stays below PLAN_NEED_CHAIN.)
+__global__ __launch_bounds__(256) void plan_pairs_kernel(PlanArgs a)
+{
+	const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+	if (p >= a.counters->n_pairs) return;
+	const uint32_t u0 = a.pair_unit[p], u1 = a.pair_unit[p + 1];
+	PlanGroup pr = a.pairs[p];
+	const PlanGroup first = a.groups[u0];
+	pr.n_hits = a.pairs[p + 1].hit_begin - pr.hit_begin;
+	pr.band_begin = first.band_begin;
+	pr.pass = first.pass;
+	uint32_t n_bands = 0;
+	int score = 0, ungapped0 = 0;
+	bool on_host = false;
+	for (uint32_t u = u0; u < u1; ++u) {
+		const PlanGroup g = a.groups[u];
+		score = chain_max(score, (int)g.score);
+		if (a.hits[g.hit_begin].query % (uint32_t)a.contexts == 0) ungapped0 = g.score;
+		if (g.n_bands == PLAN_ON_HOST) on_host = true; else n_bands += g.n_bands;
+	}
+	if (n_bands >= PLAN_NEED_CHAIN) on_host = true;
+	pr.score = (uint16_t)score;
+	pr.n_bands = on_host ? (uint8_t)PLAN_ON_HOST : (uint8_t)n_bands;
+	a.pairs[p] = pr;
+	a.ungapped0[p] = (uint16_t)ungapped0;
+	if (on_host) atomicAdd(&a.counters->n_pairs_on_host, 1u);
 }
 
 hipError_t ensure_tmp(void** tmp, size_t* have, size_t need)
@@ -298,7 +420,8 @@ hipError_t ensure_tmp(void** tmp, size_t* have, size_t need)
 void plan_kernel_table(const void** out, int* n)
 {
 	const void* k[] = { (const void*)plan_mark_kernel, (const void*)plan_fill_kernel, (const void*)plan_segments_kernel, (const void*)plan_chain_list_kernel,
-		(const void*)plan_chain_kernel<PLAN_SMALL_SEGS, 16, 4, true>, (const void*)plan_chain_kernel<PLAN_MAX_SEGS, 96, 16, false>, (const void*)plan_count_kernel, (const void*)plan_gather_kernel };
+		(const void*)plan_chain_kernel<PLAN_SMALL_SEGS, 16, 4, true>, (const void*)plan_chain_kernel<PLAN_MAX_SEGS, 96, 16, false>, (const void*)plan_count_kernel, (const void*)plan_gather_kernel,
+		(const void*)plan_key_kernel, (const void*)plan_permute_kernel, (const void*)plan_pairs_kernel };
 	*n = (int)(sizeof(k) / sizeof(k[0]));
 	for (int i = 0; i < *n; ++i) out[i] = k[i];
 }
@@ -310,14 +433,32 @@ hipError_t launch_plan(const PlanArgs& a, hipStream_t st)
 	hipError_t e = hipMemsetAsync(a.counters, 0, sizeof(PlanCounters), st);
 	if (e != hipSuccess) return e;
 	const unsigned b256 = (unsigned)((n + 255) / 256), b64 = (unsigned)((n + 63) / 64), b256g = (unsigned)((n + 1 + 255) / 256);
-	hipLaunchKernelGGL(plan_mark_kernel, dim3(b256), dim3(256), 0, st, a);
-	size_t need = 0, need2 = 0;
+	const bool translated = a.contexts > 1;
+	size_t need = 0, need2 = 0, need3 = 0, need4 = 0;
 	e = rocprim::inclusive_scan(nullptr, need, a.heads, a.head_scan, n, rocprim::plus<uint64_t>(), st);
 	if (e != hipSuccess) return e;
 	e = rocprim::exclusive_scan(nullptr, need2, a.band_count, a.band_off, 0u, n + 1, rocprim::plus<uint32_t>(), st);
 	if (e != hipSuccess) return e;
-	e = ensure_tmp(a.scan_tmp, a.scan_tmp_bytes, need > need2 ? need : need2);
+	if (translated) {
+		e = rocprim::radix_sort_pairs(nullptr, need3, a.keys, a.keys_sorted, a.perm_in, a.perm, n, 0, a.key_bits, st);
+		if (e != hipSuccess) return e;
+		e = rocprim::inclusive_scan(nullptr, need4, a.pheads, a.phead_scan, n, rocprim::plus<uint32_t>(), st);
+		if (e != hipSuccess) return e;
+	}
+	size_t need_all = need > need2 ? need : need2;
+	if (need3 > need_all) need_all = need3;
+	if (need4 > need_all) need_all = need4;
+	e = ensure_tmp(a.scan_tmp, a.scan_tmp_bytes, need_all);
 	if (e != hipSuccess) return e;
+	if (translated) {
+		hipLaunchKernelGGL(plan_key_kernel, dim3(b256), dim3(256), 0, st, a);
+		e = rocprim::radix_sort_pairs(*a.scan_tmp, need3, a.keys, a.keys_sorted, a.perm_in, a.perm, n, 0, a.key_bits, st);
+		if (e != hipSuccess) return e;
+		hipLaunchKernelGGL(plan_permute_kernel, dim3(b256), dim3(256), 0, st, a);
+		e = rocprim::inclusive_scan(*a.scan_tmp, need4, a.pheads, a.phead_scan, n, rocprim::plus<uint32_t>(), st);
+		if (e != hipSuccess) return e;
+	}
+	else hipLaunchKernelGGL(plan_mark_kernel, dim3(b256), dim3(256), 0, st, a);
 	e = rocprim::inclusive_scan(*a.scan_tmp, need, a.heads, a.head_scan, n, rocprim::plus<uint64_t>(), st);
 	if (e != hipSuccess) return e;
 	hipLaunchKernelGGL(plan_fill_kernel, dim3(b256), dim3(256), 0, st, a);
@@ -336,6 +477,7 @@ hipError_t launch_plan(const PlanArgs& a, hipStream_t st)
 	e = rocprim::exclusive_scan(*a.scan_tmp, need2, a.band_count, a.band_off, 0u, n + 1, rocprim::plus<uint32_t>(), st);
 	if (e != hipSuccess) return e;
 	hipLaunchKernelGGL(plan_gather_kernel, dim3(b256g), dim3(256), 0, st, a);
+	if (translated) hipLaunchKernelGGL(plan_pairs_kernel, dim3(b256), dim3(256), 0, st, a);
 	return hipGetLastError();
 }
 

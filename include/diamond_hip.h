@@ -598,16 +598,19 @@ int dmnd_touch_streams(dmnd_ctx* ctx);
 int dmnd_extend_stats(const dmnd_ctx* ctx, double out[12]);
 /* Round 6: the extension stage plans on the device -- grouping the seed hits by target (load_hits, src/align/load_hits.h:44),
  * diagonal segments (src/align/ungapped.cpp:62-126), chaining (src/chaining/greedy_align.cpp:482-497) and band construction
- * (src/align/gapped_score.cpp:107-180) of ALL (query, target) pairs of a block pair in a few launches (one query context, banded
- * modes). Of the last dmnd_extend: [0] (query, target) groups the device found, [1] groups it left to the host (more than 32 hits
- * or 16 segments), [2] round-1 bands it planned; all 0 = the host planned (several contexts, --ext full, hits not in
- * (query, location) order). Lets a test tell which path produced the records. */
+ * (src/align/gapped_score.cpp:107-180) of ALL (query, target) pairs of a block pair in a few launches (banded modes; with six
+ * query contexts per (read, target) pair, where the device half extends the call). Of the last dmnd_extend: [0] (query, target)
+ * groups the device found -- (read, target) pairs of a translated call --, [1] groups it left to the host (more than 32 hits
+ * or 16 segments in one context), [2] round-1 bands it planned; all 0 = the host planned (--ext full, hits not in
+ * (query, location) order, a translated call the device half does not take). Lets a test tell which path produced the records. */
 int dmnd_extend_plan_stats(const dmnd_ctx* ctx, double out[3]);
 /* Test entry: the device planner's own result for a hit list (both blocks uploaded). Runs the front half of dmnd_extend -- Hauser
  * bias, upload of the hits, x-drop extension, gapped filter when it is on, the planner -- and copies the plan out. rows: the bands
  * of the groups the device planned, in group order, in the record of dmnd_extend_plan (row_cap >= n_hits is enough); groups: one
  * record per (query, target) group (group_cap >= n_hits is enough). A list that is not sorted by (query, subject, seed_offset) is
- * not planned: planned = 0, unsorted = 1, no rows. DMND_PLAN_SMALL_HITS (environment, read per call): the number of hits from
+ * not planned: planned = 0, unsorted = 1, no rows. With six query contexts a group is a (read, target) pair -- query = the block id
+ * of the read's context 0, n_hits / n_bands over all its frames --, its rows follow frame by frame with query = the row's own context
+ * id and the ungapped score of context 0, as dmnd_extend_plan returns them, and n_queries counts reads. DMND_PLAN_SMALL_HITS (environment, read per call): the number of hits from
  * which a call chains its groups of up to four segments in a kernel of their own (default 2^18). */
 typedef struct {
 	uint32_t query, target;       /* block sequence ids */
@@ -634,7 +637,7 @@ int dmnd_extend_plan_device(dmnd_ctx* ctx, const dmnd_seed_hit* hits, int64_t n_
  * [3] records, [4] sum over the round-1 DpTargets of band diagonals x anti-diagonal steps and [5] of the 128 P diagonals their wavefront
  * holds x steps ([4] / [5] = lane use of the sweeps), [6] DP cells of the device half's round-2 targets, [7] of those swept again in
  * round 2 (their round-1 sweep kept no trace rows), [8] device ms of those sweeps, [9] of [1] the queries still ranking after the last chunk; all 0 = every query took the host path (other modes: --max-hsps != 1,
- * --no-self-hits, matrix adjustment, --ext full, transcripts wanted, translated queries). Under the filters of dmnd_set_filters /
+ * --no-self-hits, matrix adjustment, --ext full, translated queries with HSP filters). A translated call counts reads. Under the filters of dmnd_set_filters /
  * dmnd_set_approx_id [1] also counts the queries of dmnd_extend_filter_stats [1]. Under dmnd_set_top_percent the culling is the
  * reference's --top culling (src/align/culling.cpp:92-144, src/basic/config.h:428-454): cuts by a threshold against the best bit
  * score, a chunk appended by an integer comparison of scores, no limit on the aligned targets of a query but the groups; [1] then

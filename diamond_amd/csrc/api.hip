@@ -338,7 +338,7 @@ extern "C" void dmnd_destroy(dmnd_ctx* c)
 	c->plan_dev.release(); c->plan_host.release();
 	c->ext_dev.release(); c->ext_trace.release(); c->ext_host.release(); c->ext_ev.release();
 	for (DevBuf& b : c->ext_trace_more) b.release();
-	c->ext_tr.release(); c->ext_tr_raw.release(); c->ext_tr_store.release(); c->ext_tr_out.release();
+	c->ext_tr.release(); c->ext_tr_raw.release(); c->ext_tr_store.release(); c->ext_tr_out.release(); c->ext_source_lens.release();
 	if (c->plan_tmp) { (void)hipFree(c->plan_tmp); c->plan_tmp = nullptr; c->plan_tmp_bytes = 0; }
 	for (int i = 0; i < 2; ++i) { c->up_stage[i].release(); if (c->up_ev[i]) (void)hipEventDestroy(c->up_ev[i]); c->up_ev[i] = nullptr; }
 	for (int i = 0; i < 2; ++i) { c->t_stage[i].release(); if (c->t_ev[i]) (void)hipEventDestroy(c->t_ev[i]); c->t_ev[i] = nullptr; }
@@ -473,7 +473,7 @@ extern "C" int dmnd_share_block(dmnd_ctx* c, int which, const dmnd_ctx* src)
 	c->limits[which] = src->limits[which];
 	c->coarse[which] = src->coarse[which];
 	c->soft_valid[which] = false;
-	if (which == DMND_QUERY) { c->source_lens = src->source_lens; ++c->query_generation; }
+	if (which == DMND_QUERY) { c->source_lens = src->source_lens; c->source_lens_generation = ~(uint64_t)0; ++c->query_generation; }
 	return DMND_OK;
 }
 
@@ -516,7 +516,7 @@ extern "C" int dmnd_upload_block(dmnd_ctx* c, int which, const int8_t* data, int
 	HIP_TRY(sync_stream(lane ? c->t_stream : c->stream));
 	c->block_len[which] = data_len;
 	c->soft_valid[which] = false;
-	if (which == DMND_QUERY) { c->source_lens.clear(); ++c->query_generation; }
+	if (which == DMND_QUERY) { c->source_lens.clear(); c->source_lens_generation = ~(uint64_t)0; ++c->query_generation; }
 	c->limits[which].clear();
 	c->coarse[which].clear();
 	if (limits) {

@@ -189,6 +189,8 @@ struct dmnd_ctx {
 	uint64_t cbs_generation = ~(uint64_t)0;    // query_generation the Hauser bias in `cbs` was computed for by dmnd_extend (all sequences); ~0: none / someone else's
 	std::string qindex_signature;              // what the resident query seed index was built for (empty: nothing resident)
 	std::vector<int32_t> source_lens;          // translated queries: DNA read lengths of the query block (query cover)
+	dmnd::DevBuf ext_source_lens;              // ... their copy in HBM for the filter kernel of the device half, made by a translated call with HSP filters
+	uint64_t source_lens_generation = ~(uint64_t)0;      // query_generation that copy was made for; ~0: none, or dmnd_set_query_source_lengths was called since
 	int ext_mode = -1;                         // --ext: DMND_EXT_DEFAULT = what the sensitivity selects
 	int band_mode_fast = 1;                    // Extension::Mode::BANDED_FAST up to --sensitive, BANDED_SLOW from --more-sensitive up (align/extend.cpp:62-75)
 	std::vector<unsigned long long> seed_trace;   // DMND_TRACE: per shape Hamming survivors and deferred pairs of the last seed search

@@ -231,11 +231,31 @@ int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan,
 	// (with filters: the aligned targets of a query and a chunk, and the matches of all rounds -- fewer than 2 k --, fit the LDS list)
 	if (!top && filt && ((size_t)h.max_target_seqs + (size_t)chunk > EXT_FILTER_LIST || 2 * (size_t)h.max_target_seqs > EXT_FILTER_LIST)) return DMND_OK;
 	const bool fchunk = filt && !top;                   // the chunk-by-chunk walk of the -k filter path (under --top the filters come after the one walk)
+	// translated queries with filters: the filter kernel measures the query cover on the DNA read, one length per read of the block
+	// (a call without them is not taken: dmnd_extend's gate; checked here again, the kernel indexes the array by read)
+	const bool read_lens = filt && h.contexts > 1;
+	const size_t n_reads = (c->limits[DMND_QUERY].size() - 1) / (size_t)h.contexts;
+	if (read_lens && (n_reads == 0 || c->source_lens.size() != n_reads)) return DMND_OK;
 	const ExtLayout L = ext_layout(plan.n_groups, plan.n_queries, plan.n_bands, h.max_target_seqs, filt, top);
 	const size_t nQ = L.nQ, nR = L.nR;
 	if (int rc = c->ext_dev.ensure(L.bytes)) return rc;
 	Guard guard(c->ext_dev, L.bytes, c->stream);
 	if (int rc = guard.arm()) return rc;
+	// The read lengths in HBM: exactly one int32 per read, copied on the call's stream when the query block or the lengths themselves
+	// have changed since the copy was made (dmnd_upload_block, dmnd_share_block and dmnd_set_query_source_lengths all void it)
+	const size_t sl_bytes = read_lens ? n_reads * sizeof(int32_t) : 0;
+	if (read_lens) {
+		if (c->ext_source_lens.cap < sl_bytes || !c->ext_source_lens.own) c->source_lens_generation = ~(uint64_t)0;      // (the buffer is about to be replaced)
+		if (int rc = c->ext_source_lens.ensure(sl_bytes)) return rc;
+	}
+	Guard guard_sl(c->ext_source_lens, sl_bytes, c->stream);
+	if (read_lens) {
+		if (int rc = guard_sl.arm()) return rc;
+		if (c->source_lens_generation != c->query_generation) {
+			HIP_TRY(copy_now(c->stream, c->ext_source_lens.p, c->source_lens.data(), sl_bytes, hipMemcpyHostToDevice));
+			c->source_lens_generation = c->query_generation;
+		}
+	}
 	// with a transcript arena: the arrays between the trace walk and the arena, in a buffer of their own (extend_core.h tr_layout)
 	const bool with_tr = transcript != nullptr;
 	const TrLayout T = tr_layout(L.nG, L.nS, nR);
@@ -264,6 +284,7 @@ int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan,
 	a.n_groups = plan.n_groups; a.n_queries = plan.n_queries; a.n_bands = plan.n_bands;
 	a.hits = plan.dev.hits; a.qlimits = plan.dev.qlimits; a.tlimits = plan.dev.tlimits;
 	a.contexts = h.contexts; a.band_query = plan.dev.band_query; a.ungapped0 = plan.dev.ungapped0;
+	a.source_lens = read_lens ? c->ext_source_lens.as<int32_t>() : nullptr;
 	a.use_cbs = h.use_cbs ? 1 : 0; a.row_min_items = (uint32_t)std::min<int64_t>(sweep_rows_min_items(), 0xffffffffll); a.chunk_size = (uint32_t)chunk; a.k = h.max_target_seqs; a.max_swipe_dp = h.max_swipe_dp;
 	const Evaluer& E = c->evaluer;
 	a.min_bit_score = h.min_bit_score; a.filt = h.filters; a.filt_on = filt ? 1 : 0;
@@ -610,6 +631,7 @@ int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan,
 		tr_pieces, (long long)piece_limit, tr_raw, tr_kept, tr_gathered, ms_tr_walk, ms_tr_keep, ms_tr_gather);
 	if (int rc = guard.check("dmnd_extend (device half)")) return rc;
 	if (with_tr) if (int rc = guard_tr.check("dmnd_extend (device half, transcript arrays)")) return rc;
+	if (read_lens) if (int rc = guard_sl.check("dmnd_extend (device half, read lengths)")) return rc;
 	done = true;
 	return DMND_OK;
 }

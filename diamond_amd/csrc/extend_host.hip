@@ -994,8 +994,8 @@ static int extend_range(const dmnd_ctx* c, dmnd_ctx* w, const HostCfg& h, const 
 					const int tlen = (int)(tl[m.target + 1] - tl[m.target] - 1);
 					const uint32_t qc = q * C + (uint32_t)m.frame;
 					const int qlen = (int)(ql[qc + 1] - ql[qc] - 1);
-					if (h.have_filters() && filter_fails(fcfg, filter_values(hsp.score, hsp.identities, hsp.length, hsp.q_begin, hsp.q_end, hsp.s_begin, hsp.s_end,
-						C == 1 ? hsp.q_end - hsp.q_begin : 3 * (hsp.q_end - hsp.q_begin), C == 1 ? qlen : (h.source_lens ? h.source_lens[q] : 1), tlen))) return true;
+					if (h.have_filters() && filter_fails(fcfg, filter_values_contexts(hsp.score, hsp.identities, hsp.length, hsp.q_begin, hsp.q_end, hsp.s_begin, hsp.s_end,
+						(int)C, qlen, h.source_lens ? h.source_lens[q] : 0, tlen))) return true;
 					// --no-self-hits: same letters (Sequence::operator==, the query's first context) and same title
 					if (c->same_title && C == 1 && qlen == tlen) {
 						const int8_t* a = qdata + ql[qc];
@@ -1259,7 +1259,8 @@ int extend_cfg(dmnd_ctx* c, HostCfg& h, CbsModel& cbs_model)
 		return fail(DMND_E_ARG, "dmnd_extend: the query cover of translated queries needs the read lengths (dmnd_set_query_source_lengths)");
 	if (h.max_hsps != 1 && c->query_contexts != 1 && c->source_lens.size() != (ql.size() - 1) / (size_t)c->query_contexts)
 		return fail(DMND_E_ARG, "dmnd_extend: several HSPs per target of translated queries need the read lengths (dmnd_set_query_source_lengths)");
-	h.source_lens = c->source_lens.empty() ? nullptr : c->source_lens.data();
+	// (lengths that are not one per read of this block are none: every use indexes them by read)
+	h.source_lens = c->source_lens.empty() || c->source_lens.size() != (ql.size() - 1) / (size_t)c->query_contexts ? nullptr : c->source_lens.data();
 	h.ranking_block_letters = c->ranking_block_letters;
 	h.band_mode_fast = c->band_mode_fast;
 	h.ext_full = c->ext_mode == DMND_EXT_FULL;
@@ -1443,10 +1444,13 @@ extern "C" int dmnd_extend(dmnd_ctx* c, const int8_t* qdata, const int8_t* tdata
 	// DMND_EXTEND_DEVICE=0: all queries on the host path, as up to round 5. Read per call, like the hooks of extend_device.hip
 	// (DESIGN.md 9): a test compares the two paths in one process.
 	const bool ext_gpu = [] { const char* e = std::getenv("DMND_EXTEND_DEVICE"); return !e || e[0] != '0'; }();
-	// what the device half extends: one HSP per target, Hauser bias or none, banded extension, -k or --top; with six query contexts
-	// (blastx) only without the HSP filters -- there --query-cover is measured on the DNA read, whose length the device half does not hold
+	// what the device half extends: one HSP per target, Hauser bias or none, banded extension, -k or --top, one query context or six
+	// (blastx). With six contexts and the HSP filters the query cover is measured on the DNA read: such a call is taken when the context
+	// holds the block's read lengths (dmnd_set_query_source_lengths; the device half copies them to HBM), and stays on the host path as a
+	// whole without them -- there every cover is measured against 1 (--query-cover itself is refused by extend_cfg)
+	const bool have_read_lens = c->source_lens.size() == (ql.size() - 1) / (size_t)h.contexts;
 	const bool device_takes = ext_gpu && h.max_hsps == 1 && !cbs_matrix_adjust(h.cbs_mode) && !h.ext_full
-		&& h.global_ranking == 0 && !c->same_title && h.max_target_seqs > 0 && (h.contexts == 1 || !h.have_filters());
+		&& h.global_ranking == 0 && !c->same_title && h.max_target_seqs > 0 && (h.contexts == 1 || !h.have_filters() || have_read_lens);
 	ExtendFront f;
 	if (int rc = extend_front(c, h, hits, n_hits, qr.size(), lap, trp, f, device_takes)) return rc;
 	const int8_t* const cbs = f.cbs;
@@ -1466,9 +1470,10 @@ extern "C" int dmnd_extend(dmnd_ctx* c, const int8_t* qdata, const int8_t* tdata
 	if (xd) xd = tr_planned ? nullptr : c->xd_host.as<XdropSeg>();      // (NULL while no group was left to the host: nothing reads it then; a planned translated call fetches below)
 	const DevPlan* dp = planned && !tr_planned ? &plan : nullptr;
 	// The queries are extended in HBM from here on (extend_kernels.hip), ranking chunk by ranking chunk: the default search of a
-	// protein query block -- one HSP per target, -k culling by e-value or --top culling by score, Hauser bias or none, with or without
-	// the HSP filters, with or without a transcript arena (its transcripts come first in the arena). The queries the device half hands back, and every
-	// query of any other mode, take the host path below.
+	// protein or translated query block -- one HSP per target, -k culling by e-value or --top culling by score, Hauser bias or none,
+	// with or without the HSP filters (translated: with the block's read lengths), with or without a transcript arena (its transcripts
+	// come first in the arena). The queries the device half hands back, and every query of any other mode (-F, --max-hsps != 1,
+	// --ext full, --global-ranking, matrix adjustment), take the host path below.
 	c->ext_records_dev = nullptr; c->ext_records_n = -1;
 	std::vector<dmnd_match> dev_records;
 	std::vector<Range> qr_host;
@@ -1841,6 +1846,7 @@ extern "C" int dmnd_set_query_source_lengths(dmnd_ctx* c, const int32_t* lengths
 	if (!c || n_queries < 0 || (n_queries > 0 && !lengths)) return fail(DMND_E_ARG, "dmnd_set_query_source_lengths: bad argument");
 	for (int64_t i = 0; i < n_queries; ++i) if (lengths[i] < 1) return fail(DMND_E_ARG, "dmnd_set_query_source_lengths: a read length below 1");
 	c->source_lens.assign(lengths, lengths + n_queries);
+	c->source_lens_generation = ~(uint64_t)0;            // (the copy in HBM, if any, is of other lengths)
 	return DMND_OK;
 }
 

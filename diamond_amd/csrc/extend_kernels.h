@@ -44,6 +44,7 @@ struct ExtArgs {
 	// context, and the record's ungapped score is context 0's
 	int contexts;
 	const uint32_t* band_query; const uint16_t* ungapped0;
+	const int32_t* source_lens;    // translated queries with HSP filters: the DNA length of every read of the block (--query-cover is measured on it); NULL otherwise
 	int use_cbs;
 	uint32_t row_min_items;        // items of an iteration from which on the row classes of the packed 16-bit sweeps are used (sweep_rows_min_items)
 	uint32_t chunk_size;           // ranking_chunk_size

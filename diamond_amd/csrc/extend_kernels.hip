@@ -609,10 +609,15 @@ __global__ __launch_bounds__(256) void ext_filter_kernel(ExtArgs a, uint32_t n)
 	if (k >= n) return;
 	const uint32_t g = a.r2_group[k];
 	const PlanGroup grp = a.groups[g];
-	const uint32_t query = a.hits[grp.hit_begin].query;
-	const int qlen = (int)(a.qlimits[query + 1] - a.qlimits[query] - 1), tlen = (int)(a.tlimits[grp.target + 1] - a.tlimits[grp.target] - 1);
-	const dmnd_hsp h = a.hsps[a.cand_item[g]];
-	const FilterValues v = filter_values(h.score, h.identities, h.length, h.q_begin, h.q_end, h.s_begin, h.s_end, h.q_end - h.q_begin, qlen, tlen);
+	const uint32_t query = a.hits[grp.hit_begin].query, item = a.cand_item[g];
+	const int tlen = (int)(a.tlimits[grp.target + 1] - a.tlimits[grp.target] - 1);
+	// translated queries: a group is a (read, target) pair and `query` one of the read's contexts, not necessarily the one the best
+	// HSP lies in -- the context's length is the walked item's, the read's length that of read query / contexts (< reads of the
+	// block = the entries of source_lens, checked by the host before the call is taken)
+	const int qlen = a.contexts > 1 ? a.items[item].query_len : (int)(a.qlimits[query + 1] - a.qlimits[query] - 1);
+	const int rlen = a.contexts > 1 ? a.source_lens[query / (uint32_t)a.contexts] : 0;
+	const dmnd_hsp h = a.hsps[item];
+	const FilterValues v = filter_values_contexts(h.score, h.identities, h.length, h.q_begin, h.q_end, h.s_begin, h.s_end, a.contexts, qlen, rlen, tlen);
 	a.fverdict[g] = filter_on_threshold(a.filt, v) ? EXT_F_THRESHOLD : filter_fails(a.filt, v) ? EXT_F_FAIL : EXT_F_PASS;
 }
 

@@ -1,5 +1,5 @@
 // filter_core.h -- the arithmetic of the HSP filters (--id, --approx-id, --query-cover, --subject-cover), HIP-free: one statement of it
-// for the host path (extend_host.hip), the filter kernel of the device half (extend_kernels.hip), the output column approx_pident
+// for the host path (extend_host.hip; protein and translated queries: filter_values_contexts), the filter kernel of the device half (extend_kernels.hip), the output column approx_pident
 // (format_api.hip), the CLI's seed configuration and the CPU tests (tests/emu/filter_emu.cpp). The values are compared with what
 // the reference prints, so every expression is spelled operation by operation: IEEE double division and one explicit fused
 // multiply-add, the same on the host and on the device.
@@ -55,6 +55,17 @@ DMND_FILTER_HD inline FilterValues filter_values(int score, int identities, int 
 	v.qcov = (double)q_range_source * 100 / source_len;
 	v.scov = (double)(s_end - s_begin) * 100 / target_len;
 	return v;
+}
+
+// ... of an HSP of a query block of `contexts` contexts per query, in the coordinates of the context it lies in (context_len letters).
+// One context (blastp): the query range against the query's length. Six (blastx): the query range in bases, 3 x the translated
+// range, against the length of the DNA read (Hsp::query_source_range, query_cover_percent(source_query_len)); identity, approximate
+// identity and subject cover from the translated coordinates as they are. read_len < 1: no read lengths are known, the cover is
+// measured against 1 (what the host path did before the read lengths were set; --query-cover is refused without them).
+DMND_FILTER_HD inline FilterValues filter_values_contexts(int score, int identities, int length, int q_begin, int q_end, int s_begin, int s_end, int contexts, int context_len, int read_len, int target_len)
+{
+	return filter_values(score, identities, length, q_begin, q_end, s_begin, s_end,
+		contexts == 1 ? q_end - q_begin : 3 * (q_end - q_begin), contexts == 1 ? context_len : (read_len >= 1 ? read_len : 1), target_len);
 }
 
 // filter_hsp: true = the HSP is removed

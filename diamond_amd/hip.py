@@ -873,6 +873,14 @@ class Context:
         """1 = blastp, 6 = blastx (the query block holds the six frames of every read consecutively)."""
         self._check(self.lib.dmnd_set_query_contexts(self.h, int(contexts)))
 
+    def set_query_source_lengths(self, lengths):
+        """Translated queries: the length in bases of every DNA read of the uploaded query block, one per read (= per six contexts), which
+        --query-cover is measured against (dmnd_set_query_source_lengths). The next upload of the query block clears them. With them a
+        translated extend() under HSP filters runs in the device half; without them it takes the host path."""
+        lens = np.ascontiguousarray(lengths, dtype=np.int32)
+        self.lib.dmnd_set_query_source_lengths.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]
+        self._check(self.lib.dmnd_set_query_source_lengths(self.h, lens.ctypes.data if lens.size else None, ctypes.c_int64(lens.size)))
+
     def set_gapped_filter(self, evalue):
         """Search::Config::gapped_filter_evalue (1.0 for --sensitive; 0 switches the filter off)."""
         self._check(self.lib.dmnd_set_gapped_filter(self.h, float(evalue)))

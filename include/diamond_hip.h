@@ -500,7 +500,9 @@ int dmnd_set_filters(dmnd_ctx* ctx, double min_id, double query_cover, double su
 int dmnd_set_approx_id(dmnd_ctx* ctx, double approx_min_id);
 /* Translated queries: the lengths of the DNA reads of the uploaded query block (one per query = per six contexts), which the
  * query cover of an HSP is measured against (Hsp::query_cover_percent over query_source_range). Cleared by the next upload of
- * the query block. */
+ * the query block. With them a translated dmnd_extend under the HSP filters (dmnd_set_filters, dmnd_set_approx_id) runs in the device
+ * half, which keeps a copy of the lengths in HBM for as long as the block and the lengths stay; without them such a call takes the
+ * host path as a whole, where every cover is measured against 1 (a query cover threshold is refused with DMND_E_ARG). */
 int dmnd_set_query_source_lengths(dmnd_ctx* ctx, const int32_t* lengths, int64_t n_queries);
 /* --no-self-hits (filter_hsp, align/culling.cpp:166-169): an HSP is removed when the query and the target have the same letters
  * AND the same title. The library compares the letters; `same_title` (called only for such pairs, with the block-local query and
@@ -637,7 +639,8 @@ int dmnd_extend_plan_device(dmnd_ctx* ctx, const dmnd_seed_hit* hits, int64_t n_
  * [3] records, [4] sum over the round-1 DpTargets of band diagonals x anti-diagonal steps and [5] of the 128 P diagonals their wavefront
  * holds x steps ([4] / [5] = lane use of the sweeps), [6] DP cells of the device half's round-2 targets, [7] of those swept again in
  * round 2 (their round-1 sweep kept no trace rows), [8] device ms of those sweeps, [9] of [1] the queries still ranking after the last chunk; all 0 = every query took the host path (other modes: --max-hsps != 1,
- * --no-self-hits, matrix adjustment, --ext full, translated queries with HSP filters). A translated call counts reads. Under the filters of dmnd_set_filters /
+ * --no-self-hits, matrix adjustment, --ext full, -F, --global-ranking, translated queries with HSP filters but without the read lengths of
+ * dmnd_set_query_source_lengths). A translated call counts reads. Under the filters of dmnd_set_filters /
  * dmnd_set_approx_id [1] also counts the queries of dmnd_extend_filter_stats [1]. Under dmnd_set_top_percent the culling is the
  * reference's --top culling (src/align/culling.cpp:92-144, src/basic/config.h:428-454): cuts by a threshold against the best bit
  * score, a chunk appended by an integer comparison of scores, no limit on the aligned targets of a query but the groups; [1] then
@@ -648,7 +651,8 @@ int dmnd_extend_device_stats(const dmnd_ctx* ctx, double out[10]);
  * takes none of the -k places; under --top the survivors of the last cut are walked once, and the matches that passed are cut
  * against the best of them). Of the last dmnd_extend: [0] records a filter removed on the device (of the queries it finished),
  * [1] queries handed back to the host path because a filter value lay on its threshold (within 1e-9 relative; counted in
- * dmnd_extend_device_stats [1] as well). Both 0 without filters or when every query took the host path. */
+ * dmnd_extend_device_stats [1] as well). Both 0 without filters or when every query took the host path. Filled for protein and for
+ * translated calls alike (a translated call counts reads in [1]). */
 int dmnd_extend_filter_stats(const dmnd_ctx* ctx, double out[2]);
 /* Round 6: the records of the last dmnd_extend where they lie in HBM, complete (the host's e-values and bit scores are written back
  * into them): *records_dev is valid until the context's next dmnd_extend; *n = -1 (and NULL) when part of the records only exists on the

@@ -4,6 +4,9 @@ resident) through hip.Context: wall time of dmnd_extend per step and process CPU
 warm-up steps, `--repeats` times; beside them the device half's counters and the md5 of the records. One JSON line.
   python tools/top_step.py [--top 10] [--lib PATH]      --top -1: the default -k 25 step; --lib: another build's libdiamond_hip.so
                                                          (the parent commit's, for DESIGN.md 5.0)
+  python tools/top_step.py --blastx --top -1 [--id 50 --query-cover 50]
+                                                         the C4 workload instead (bench.py's: the first 5 000 queries back-translated into
+                                                         DNA reads, six contexts, default sensitivity, read lengths set), with HSP filters
 The seed stage runs once, outside the timed region: every step extends the same seed hits."""
 import argparse
 import hashlib
@@ -28,11 +31,21 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--threads", type=int, default=12)
     ap.add_argument("--lib", default=None)
+    ap.add_argument("--blastx", action="store_true")
+    ap.add_argument("--id", type=float, default=0.0)
+    ap.add_argument("--query-cover", type=float, default=0.0)
     args = ap.parse_args()
     if args.lib:
         hip.LIB_PATH = os.path.abspath(args.lib)
     db, doff, q, qoff = synth.generate(args.families, members=10, queries=args.queries, seed=20260923)
-    qd, ql = workload.sequence_set(q, qoff)
+    source_lens = None
+    if args.blastx:
+        n_reads = min(args.queries, 5000)
+        dna, dna_off = synth.back_translate(q[:qoff[n_reads]], qoff[:n_reads + 1], seed=5)
+        qd, ql = hip.translated_block(dna, dna_off)
+        source_lens = np.diff(dna_off)
+    else:
+        qd, ql = workload.sequence_set(q, qoff)
     td, tl = workload.sequence_set(db, doff)
     params = hip.default_params()
     params.db_letters = float(doff[-1])
@@ -40,8 +53,13 @@ def main():
     try:
         ctx.upload_block(hip.QUERY, qd, ql)
         ctx.upload_block(hip.TARGET, td, tl)
-        sp, gf = hip.seed_params_preset("fast", params, threads=1)
+        sp, gf = hip.seed_params_preset("default" if args.blastx else "fast", params, threads=8 if args.blastx else 1)
+        if args.blastx:
+            sp.query_translated = 1
+            ctx.set_query_contexts(6)
+            ctx.set_query_source_lengths(source_lens)
         ctx.set_gapped_filter(gf)
+        ctx.set_filters(min_id=args.id, query_cover=args.query_cover)
         ctx.set_top_percent(args.top if args.top >= 0 else None)
         hits = ctx.seed_search(sp)
         reps, md5, n_records = [], None, 0
@@ -58,11 +76,11 @@ def main():
             md5, n_records = hashlib.md5(m.tobytes()).hexdigest(), len(m)
         dv = ctx.extend_device_stats()
         w = [x["wall_ms_median"] for x in reps]
-        print(json.dumps(dict(top=args.top, lib=args.lib or "this build", seed_hits=int(len(hits)), records=n_records, records_md5=md5,
+        print(json.dumps(dict(top=args.top, blastx=args.blastx, id=args.id, query_cover=args.query_cover, lib=args.lib or "this build", seed_hits=int(len(hits)), records=n_records, records_md5=md5,
                               wall_ms_median_of_repeats=float(np.median(w)), wall_ms_spread=float(max(w) - min(w)),
                               cpu_ms_median_of_repeats=float(np.median([x["cpu_ms_mean"] for x in reps])), repeats=reps,
                               device=dict(queries=dv["queries"], back_to_host=dv["queries_back_to_host"], capped=dv["queries_capped"],
-                                          records=dv["records"], on_filter_threshold=dv["queries_on_filter_threshold"]))))
+                                          records=dv["records"], records_filtered=dv["records_filtered"], on_filter_threshold=dv["queries_on_filter_threshold"]))))
     finally:
         ctx.close()
 

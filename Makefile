@@ -4,7 +4,7 @@
 # and the test-only helpers: oracle/_ref/* (CPU restatement + reference build), tests/emu/libswipe_emu.so
 HIPCC   ?= /opt/rocm/bin/hipcc
 CSRC    := diamond_amd/csrc
-HIPSRC  := $(CSRC)/api.hip $(CSRC)/swipe_kernels.hip $(CSRC)/swipe16_kernels.hip $(CSRC)/seed_api.hip $(CSRC)/seed_kernels.hip $(CSRC)/extend_host.hip $(CSRC)/gapped_api.hip $(CSRC)/gapped_kernels.hip $(CSRC)/mask_api.hip $(CSRC)/mask_kernels.hip $(CSRC)/bias_kernels.hip $(CSRC)/format_api.hip $(CSRC)/frameshift_api.hip $(CSRC)/frameshift_kernels.hip $(CSRC)/frameshift_host.hip $(CSRC)/join_device.hip $(CSRC)/rank_join.hip $(CSRC)/plan_kernels.hip $(CSRC)/extend_kernels.hip $(CSRC)/extend_device.hip $(CSRC)/join_blocks.hip $(CSRC)/format_tab.hip $(CSRC)/translate.hip
+HIPSRC  := $(CSRC)/api.hip $(CSRC)/swipe_kernels.hip $(CSRC)/swipe16_kernels.hip $(CSRC)/seed_api.hip $(CSRC)/seed_kernels.hip $(CSRC)/extend_host.hip $(CSRC)/gapped_api.hip $(CSRC)/gapped_kernels.hip $(CSRC)/mask_api.hip $(CSRC)/mask_kernels.hip $(CSRC)/seg_kernels.hip $(CSRC)/bias_kernels.hip $(CSRC)/format_api.hip $(CSRC)/frameshift_api.hip $(CSRC)/frameshift_kernels.hip $(CSRC)/frameshift_host.hip $(CSRC)/join_device.hip $(CSRC)/rank_join.hip $(CSRC)/plan_kernels.hip $(CSRC)/extend_kernels.hip $(CSRC)/extend_device.hip $(CSRC)/join_blocks.hip $(CSRC)/format_tab.hip $(CSRC)/translate.hip
 HIPHDR  := $(wildcard $(CSRC)/*.h) include/diamond_hip.h
 HIPFLAGS := --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function
 
@@ -25,7 +25,7 @@ build/%.o: $(CSRC)/%.hip $(HIPHDR)
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
 # the device planner truncates double expressions to int exactly as the host's chaining does: no contraction into fused multiply-adds
-build/plan_kernels.o build/extend_kernels.o: HIPFLAGS += -ffp-contract=off
+build/plan_kernels.o build/extend_kernels.o build/seg_kernels.o: HIPFLAGS += -ffp-contract=off
 
 # host-only double-precision code whose results must be bit-identical to the reference's (composition-based matrix adjustment):
 # plain g++, no contraction of a * b + c into fused multiply-adds
@@ -48,7 +48,7 @@ oracle:
 	$(MAKE) -C oracle all
 
 emu: tests/emu/libswipe_emu.so
-tests/emu/libswipe_emu.so: $(wildcard tests/emu/*.cpp) $(wildcard $(CSRC)/*_core.h)
+tests/emu/libswipe_emu.so: $(wildcard tests/emu/*.cpp) $(wildcard $(CSRC)/*_core.h) $(CSRC)/seg_mask.h
 	g++ -O2 -std=c++17 -ffp-contract=off -fPIC -shared -w -o $@ $(wildcard tests/emu/*.cpp)
 
 clean:

@@ -351,7 +351,7 @@ extern "C" void dmnd_destroy(dmnd_ctx* c)
 	for (DevBuf* b : { &c->block[0], &c->block[1], &c->cbs, &c->matrix, &c->bias_ids, &c->items, &c->order, &c->p_of_slot, &c->trace_off,
 		&c->transcript_off, &c->ends, &c->hsps, &c->trace, &c->transcript, &c->status, &c->pairs, &c->trace_off_item, &c->host_q, &c->host_t, &c->host_cbs,
 		&c->d_limits[0], &c->d_limits[1], &c->qid_of, &c->mask_time, &c->seed_keys, &c->seed_next, &c->seed_qlist, &c->seed_qkeys, &c->seed_slot2, &c->seed_loc2, &c->seed_survivors, &c->seed_scored, &c->seed_need, &c->seed_qfold, &c->seed_tfold, &c->seed_tcodes, &c->seed_tflags, &c->seed_tplanes, &c->seed_tclass,
-		&c->matched_slot, &c->matched_loc, &c->counters, &c->seed_hits, &c->seed_bitmap, &c->seed_deferred, &c->seed_eslot, &c->seed_eloc, &c->seed_hits_sorted, &c->sort_keys[0], &c->sort_keys[1], &c->sort_idx[0], &c->sort_idx[1], &c->gf_tables, &c->gf_hits, &c->gf_flags, &c->gf_scores, &c->gf_units, &c->alt_targets, &c->mask_lr, &c->mask_pb, &c->mask_scale, &c->mask_pos, &c->mask_ids, &c->mask_soff, &c->mask_long_ids, &c->mask_long_soff, &c->mask_long_pb, &c->mask_long_scale, &c->soft[0], &c->soft[1], &c->motif_hit, &c->motif_table, &c->adj_matrices, &c->join_keep, &c->join_pos, &c->join_in, &c->join_out, &c->join_recv })
+		&c->matched_slot, &c->matched_loc, &c->counters, &c->seed_hits, &c->seed_bitmap, &c->seed_deferred, &c->seed_eslot, &c->seed_eloc, &c->seed_hits_sorted, &c->sort_keys[0], &c->sort_keys[1], &c->sort_idx[0], &c->sort_idx[1], &c->gf_tables, &c->gf_hits, &c->gf_flags, &c->gf_scores, &c->gf_units, &c->alt_targets, &c->mask_lr, &c->mask_pb, &c->mask_scale, &c->mask_pos, &c->mask_ids, &c->mask_soff, &c->mask_long_ids, &c->mask_long_soff, &c->mask_long_pb, &c->mask_long_scale, &c->soft[0], &c->soft[1], &c->motif_hit, &c->motif_table, &c->seg_tables, &c->seg_cls, &c->seg_work, &c->seg_handed, &c->seg_ranges, &c->adj_matrices, &c->join_keep, &c->join_pos, &c->join_in, &c->join_out, &c->join_recv })
 		b->release();
 	if (c->ev0) (void)hipEventDestroy(c->ev0);
 	if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -490,6 +490,14 @@ extern "C" int dmnd_copy_block(dmnd_ctx* c, int which, const dmnd_ctx* src)
 	c->soft_valid[which] = false;
 	if (which == DMND_QUERY) ++c->query_generation;
 	return DMND_OK;
+}
+
+extern "C" int dmnd_download_block(dmnd_ctx* c, int which, int8_t* data, int64_t data_len)
+{
+	if (!c || (which != DMND_QUERY && which != DMND_TARGET) || !data || !c->block[which].p || data_len != c->block_len[which])
+		return fail(DMND_E_ARG, "dmnd_download_block: bad argument (the context must hold the block, data_len must be its raw length)");
+	HIP_TRY(hipSetDevice(c->device));
+	return download_bytes(c, data, c->block[which].p, (size_t)data_len);
 }
 
 extern "C" int dmnd_upload_block(dmnd_ctx* c, int which, const int8_t* data, int64_t data_len, const int64_t* limits, int64_t n_seqs)

@@ -7,7 +7,7 @@
 // (pos u64, len u32, pad u32) records), SequenceSet layout (src/data/string_set.h:27-60), tabular output
 // (src/output/blast_tab_format.cpp, sequence ids cut at the first blank).
 // Supported: blastp / blastx (--fast, default sensitivity, --sensitive), tantan masking on the GPU (default) or --masking 0
-// motif soft masking (default; table in motifs.bin next to the binary), --algo 0 / 1 / auto; SEG is not part of this build; -e, -k, -p,
+// motif soft masking (default; table in motifs.bin next to the binary), --algo 0 / 1 / auto; --masking seg (SEG over the reference block, on the GPU); -e, -k, -p,
 // -f 6 [FIELD...] (BLAST tabular with the reference's field names) and -f 0 (BLAST pairwise),
 // -b / -c: query and reference blocks cut as load_seqs cuts them, records of a query block merged over the reference blocks as
 // join_blocks does (output/join_blocks.cpp) -> same text as the reference run with the same -b.
@@ -355,8 +355,8 @@ struct Database {
 				const uint32_t l = len[begin + k];
 				int8_t* dst = data + b.limits[k];
 				const char* src = map + pos[begin + k] + 1;       // record: 0xFF letters 0xFF id 0
-				// the reference's makedb stores its SEG soft mask in bit 7 (src/legacy/dmnd/dmnd.cpp:262-265); with masking off
-				// the search ignores it (Sequence::operator[] & LETTER_MASK), so it is dropped at load time
+				// the reference's makedb stores tantan bit masks in bit 7 (Masking::mask_bit; src/legacy/dmnd/dmnd.cpp:262-265); with
+				// masking off the search ignores them (Sequence::operator[] & LETTER_MASK), so they are dropped at load time
 				for (uint32_t x = 0; x < l; ++x) dst[x] = (int8_t)(src[x] & 31);
 				dst[l] = 31;
 			}
@@ -689,9 +689,12 @@ int run_blastp(const Options& o)
 		throw std::runtime_error("This build implements --fast, default, --mid-sensitive, --sensitive, --more-sensitive, --very-sensitive and --ultra-sensitive (" + o.sens + " is not available).");
 	if (o.fast && !o.sens.empty()) throw std::runtime_error("Conflicting sensitivity options.");
 	// --masking (MaskingMode, run/config.cpp:124-135): tantan = default, on both blocks and on the GPU; seg = NCBI's SEG over the
-	// reference block only, on the host as in the reference (dmnd_seg_mask_block); 0 / none
+	// reference block only -- on the GPU too (dmnd_seg_mask_block_device; the same masks bit for bit), DMND_SEG_HOST=1 selects the host
+	// form as in the reference (dmnd_seg_mask_block) for A/B runs; 0 / none
 	const bool tantan = o.masking.empty() || o.masking == "1" || o.masking == "tantan";
 	const bool seg = o.masking == "seg";
+	const bool seg_host = seg && std::getenv("DMND_SEG_HOST") && std::getenv("DMND_SEG_HOST")[0] == '1';
+	const bool seg_dev = seg && !seg_host;
 	if (!tantan && !seg && o.masking != "0" && o.masking != "none")
 		throw std::runtime_error("Invalid value for --masking: " + o.masking + " (none / 0, seg, tantan / 1)");
 	if (!o.motif_masking.empty() && o.motif_masking != "0" && o.motif_masking != "1") throw std::runtime_error("Permitted values for --motif-masking: 0, 1");
@@ -1027,9 +1030,9 @@ int run_blastp(const Options& o)
 		// when GPU 0 writes the masked letters back into it (a late GPU would upload a partly masked block and mask it again).
 		std::vector<double> up_ms((size_t)n_gpus, 0.0);
 		// first query block: every GPU's first reference block goes to HBM on a helper thread meanwhile (the reference block has its
-		// own transfer lane in the library); SEG masks the host copy before the upload, so not then
+		// own transfer lane in the library); the host form of SEG masks the host copy before the upload, so not then
 		std::vector<std::future<double>> ahead((size_t)n_gpus);
-		if (&qr == &q_blocks.front() && !seg && !std::getenv("DMND_CLI_NO_AHEAD"))
+		if (&qr == &q_blocks.front() && !seg_host && !std::getenv("DMND_CLI_NO_AHEAD"))
 			for (int g = 0; g < n_gpus && (size_t)g < t_blocks.size(); ++g)
 				ahead[(size_t)g] = std::async(std::launch::async, [&, g]() -> double {
 					Held& h = held_blocks[(size_t)g];
@@ -1101,8 +1104,11 @@ int run_blastp(const Options& o)
 			double up = 0, mk = 0;
 			int64_t mt = 0, ml = 0;
 			const int64_t t_seqs = (int64_t)(tr.end - tr.begin);
-			// SEG runs on the host copy: a block that was just read is masked before it goes to HBM (up-front masking)
-			if (seg && !lazy_masking && fresh) { chk(dmnd_seg_mask_block(t.data.data(), t.limits.data(), t_seqs, threads, &mt)); mk += ms_since(t0); t0 = std::chrono::steady_clock::now(); }
+			// the host form of SEG runs on the host copy: a block that was just read is masked before it goes to HBM (up-front masking)
+			if (seg_host && !lazy_masking && fresh) {
+				chk(dmnd_seg_mask_block(t.data.data(), t.limits.data(), t_seqs, threads, &mt)); mk += ms_since(t0); t0 = std::chrono::steady_clock::now();
+				g_timeline.mark("reference block " + std::to_string(bi) + " masked (seg, on the host)");
+			}
 			if (in_hbm) up += ahead_ms;
 			else {
 				chk(dmnd_upload_block(ctx, DMND_TARGET, t.data.data(), (int64_t)t.data.size(), t.limits.data(), t_seqs));
@@ -1113,7 +1119,11 @@ int run_blastp(const Options& o)
 			std::vector<int32_t> lazy_ids;                   // lazy masking: the targets that have seed hits (block sequence ids)
 			auto mask_target = [&] {
 				t0 = std::chrono::steady_clock::now();
-				if (lazy_masking && q_blocks.size() == 1 && !seg) {
+				if (seg_dev && (!lazy_masking || q_blocks.size() == 1)) {
+					// SEG in HBM, the host copy patched from the range list (lazily: the only query block, nobody needs the unmasked letters again)
+					chk(dmnd_seg_mask_block_device(ctx, DMND_TARGET, t.data.data(), &mt));
+				}
+				else if (lazy_masking && q_blocks.size() == 1 && !seg) {
 					// the only query block: nobody needs the unmasked letters again, the host copy is masked in place -- and, as in
 					// the reference (extend.cpp:168-181), only the targets the extension stage will load
 					chk(dmnd_mask_sequences(ctx, DMND_TARGET, t.data.data(), lazy_ids.data(), (int64_t)lazy_ids.size(), &mt));
@@ -1121,7 +1131,9 @@ int run_blastp(const Options& o)
 				else if (lazy_masking) {                       // t.data stays unmasked: the next query block's seed stage needs it so
 					t_masked[(size_t)g].resize(t.data.size());
 					std::memcpy(t_masked[(size_t)g].data(), t.data.data(), t.data.size());
-					if (seg) {                                   // masked copy on the host, then the block in HBM is replaced by it
+					if (seg_dev)                                 // the block in HBM is masked in place (the next query block uploads the unmasked
+						chk(dmnd_seg_mask_block_device(ctx, DMND_TARGET, t_masked[(size_t)g].data(), &mt));      // letters again), the host copy is patched: no second upload
+					else if (seg) {                              // masked copy on the host, then the block in HBM is replaced by it
 						chk(dmnd_seg_mask_block(t_masked[(size_t)g].data(), t.limits.data(), t_seqs, threads, &mt));
 						chk(dmnd_upload_block(ctx, DMND_TARGET, t_masked[(size_t)g].data(), (int64_t)t.data.size(), t.limits.data(), t_seqs));
 					}
@@ -1134,6 +1146,7 @@ int run_blastp(const Options& o)
 			// up-front masking of a block that was just read; a block the GPU kept from the previous query block carries its masked
 			// letters already and is uploaded as it is
 			if (tantan && !lazy_masking && fresh) { mask_target(); g_timeline.mark("reference block " + std::to_string(bi) + " masked (tantan)"); }
+			if (seg_dev && !lazy_masking && fresh) { mask_target(); g_timeline.mark("reference block " + std::to_string(bi) + " masked (seg, on the device)"); }
 			if (motifs && algo == 0) { chk(dmnd_soft_mask_block(ctx, DMND_TARGET, &ml)); g_timeline.mark("reference block " + std::to_string(bi) + " soft-masked (motifs)"); }
 			if ((size_t)g < reserved.size() && reserved[(size_t)g].valid()) (void)reserved[(size_t)g].get();      // an optimisation only: the search allocates what is missing
 			g_timeline.mark("seed stage of block " + std::to_string(bi) + " starts");
@@ -1183,7 +1196,7 @@ int run_blastp(const Options& o)
 					for (size_t i = 0; i + 1 < t.limits.size(); ++i) if (seen[i]) lazy_ids.push_back((int32_t)i);
 				}
 				mask_target();
-				g_timeline.mark("reference block " + std::to_string(bi) + " masked lazily (" + std::to_string(lazy_ids.size()) + " targets)");
+				g_timeline.mark("reference block " + std::to_string(bi) + " masked lazily (" + (seg ? std::string(seg_dev ? "seg, on the device" : "seg, on the host") : std::to_string(lazy_ids.size()) + " targets") + ")");
 			}
 			t0 = std::chrono::steady_clock::now();
 			if (o.no_self_hits) {
@@ -1253,9 +1266,11 @@ int run_blastp(const Options& o)
 				for (uint32_t oid : ordinals) rb.push(db.sequence(oid), std::string());
 				rb.finish();
 				int64_t mt = 0;
-				if (seg) chk(dmnd_seg_mask_block(rb.data.data(), rb.limits.data(), (int64_t)ordinals.size(), threads, &mt));
+				if (seg_host) chk(dmnd_seg_mask_block(rb.data.data(), rb.limits.data(), (int64_t)ordinals.size(), threads, &mt));
 				chk(dmnd_upload_block(ctx, DMND_TARGET, rb.data.data(), (int64_t)rb.data.size(), rb.limits.data(), (int64_t)ordinals.size()));
 				if (tantan) chk(dmnd_mask_block(ctx, DMND_TARGET, rb.data.data(), &mt));
+				if (seg_dev) chk(dmnd_seg_mask_block_device(ctx, DMND_TARGET, rb.data.data(), &mt));
+				if (seg) g_timeline.mark(std::string("ranked targets masked (seg, on the ") + (seg_dev ? "device)" : "host)"));
 				held_blocks[0].index = (size_t)-1; held_blocks[0].ahead = false;      // the reference block this GPU held is no longer in HBM
 				std::vector<dmnd_seed_hit> hits;
 				for (size_t qi = 0; qi < qr.end - qr.begin; ++qi)

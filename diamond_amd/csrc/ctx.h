@@ -195,6 +195,13 @@ struct dmnd_ctx {
 	int band_mode_fast = 1;                    // Extension::Mode::BANDED_FAST up to --sensitive, BANDED_SLOW from --more-sensitive up (align/extend.cpp:62-75)
 	std::vector<unsigned long long> seed_trace;   // DMND_TRACE: per shape Hamming survivors and deferred pairs of the last seed search
 	double ranking_block_letters = 2e9;        // default_letters of ranking_chunk_size (align/extend.cpp:87): 8e8 from --very-sensitive up
+	// SEG masking on the device (mask_api.hip, seg_kernels.hip): class table + ln n! table (uploaded once), a class byte per block letter,
+	// work list, hand-back list, range list; the ranges of the last call on the host (dmnd_seg_ranges_device) and its statistics
+	dmnd::DevBuf seg_tables, seg_cls, seg_work, seg_handed, seg_ranges;
+	bool seg_tables_ready = false;
+	std::vector<int32_t> seg_last;             // (sequence, order, begin, end) per range
+	bool seg_last_sorted = true;
+	double seg_stats[4] = { 0, 0, 0, 0 };      // sequences on the work list, handed back, ranges, kernel ms
 };
 
 // internal (not part of the C ABI)

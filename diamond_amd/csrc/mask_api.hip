@@ -1,4 +1,4 @@
-// mask_api.hip -- C ABI of tantan repeat masking: dmnd_mask_block.
+// mask_api.hip -- C ABI of masking: tantan (dmnd_mask_block), motifs (dmnd_soft_mask_block), SEG on the host and on the device.
 // Replaces mask_seqs(seqs, Masking::get(), true, MaskingAlgo::TANTAN) (src/masking/masking.cpp:225-251) as the reference
 // applies it to the reference block (run/double_indexed.cpp:122-127) and to the query block (:737-740).
 #pragma clang fp contract(off)
@@ -10,6 +10,7 @@
 #include <vector>
 #include "ctx.h"
 #include "mask_kernels.h"
+#include "seg_kernels.h"
 #include "seg_mask.h"
 #include <atomic>
 #include <thread>
@@ -424,3 +425,226 @@ static int mask_impl(dmnd_ctx* c, int which, int8_t* host_data, const int32_t* i
 }
 
 extern "C" double dmnd_mask_kernel_ms(const dmnd_ctx* c) { return c ? c->mask_ms : 0.0; }
+
+// ---- SEG on the device (seg_kernels.hip) -------------------------------------------------------------------------------------------
+namespace {
+
+// every zero-terminated descending count vector with the sum n and parts <= max_part
+template<typename F>
+void seg_partitions(int n, int max_part, int* sv, int depth, F& f)
+{
+	if (n == 0) { sv[depth] = 0; f(sv); return; }
+	for (int k = std::min(n, max_part); k >= 1; --k) { sv[depth] = k; seg_partitions(n - k, k, sv, depth + 1, f); }
+}
+
+enum { SEG_TABLE_BYTES = 512 };      // the class table, padded: the ln n! table lies behind it, aligned
+
+// class table (the host's own seg::entropy for every count vector of 8 - 10 standard residues) and ln n! table, once per context
+int seg_upload_tables(dmnd_ctx* c)
+{
+	if (c->seg_tables_ready) return DMND_OK;
+	static_assert(SEG_CLASS_TABLE <= SEG_TABLE_BYTES, "class table");
+	const std::vector<double>& F = seg::lnfact().table;
+	std::vector<uint8_t> host(SEG_TABLE_BYTES + F.size() * sizeof(double), (uint8_t)SEG_BREAK);
+	std::vector<char> set(SEG_CLASS_TABLE, 0);
+	bool clash = false;
+	auto put = [&](const int* sv) {
+		const int key = seg_class_key(sv);
+		if (key < 0 || key >= SEG_CLASS_TABLE || set[(size_t)key]) { clash = true; return; }
+		set[(size_t)key] = 1;
+		host[(size_t)key] = (uint8_t)seg_entropy_class(seg::entropy(sv));
+	};
+	int sv[seg::ALPHA + 1];
+	for (int n = SEG_WINDOW - SEG_MAX_BOGUS; n <= SEG_WINDOW; ++n) seg_partitions(n, n, sv, 0, put);
+	if (clash) return fail(DMND_E_ARG, "dmnd_seg_mask_block_device: two window states share a class key");
+	std::memcpy(host.data() + SEG_TABLE_BYTES, F.data(), F.size() * sizeof(double));
+	if (int rc = c->seg_tables.ensure(host.size())) return rc;
+	HIP_TRY(copy_now(c->stream, c->seg_tables.p, host.data(), host.size(), hipMemcpyHostToDevice));
+	c->seg_tables_ready = true;
+	return DMND_OK;
+}
+
+int seg_device_impl(dmnd_ctx* c, int which, int8_t* host_data, const int32_t* ids, int64_t n_ids, int64_t* n_masked)
+{
+	const char* call = ids ? "dmnd_seg_mask_sequences_device" : "dmnd_seg_mask_block_device";
+	if (!c || (which != DMND_QUERY && which != DMND_TARGET)) return fail(DMND_E_ARG, std::string(call) + ": bad argument");
+	if (n_masked) *n_masked = 0;
+	c->soft_valid[which] = false;
+	if (which == DMND_QUERY) ++c->query_generation;
+	c->seg_last.clear(); c->seg_last_sorted = true;
+	for (double& x : c->seg_stats) x = 0;
+	if (!c->block[which].p || c->limits[which].size() < 2) return fail(DMND_E_ARG, std::string(call) + ": block must be uploaded with limits");
+	if (!c->block[which].own) return fail(DMND_E_ARG, std::string(call) + ": the block is shared from another context (dmnd_share_block); mask it there");
+	HIP_TRY(hipSetDevice(c->device));
+	hipStream_t st = c->stream;
+	const std::vector<int64_t>& lim = c->limits[which];
+	const int64_t n = (int64_t)lim.size() - 1, raw = c->block_len[which], n_call = ids ? n_ids : n;
+	if (n >= INT32_MAX) return fail(DMND_E_ARG, std::string(call) + ": more than 2^31 sequences");
+	TraceLaps tr(call);
+	int64_t letters = raw;
+	if (ids) {
+		letters = 0;
+		for (int64_t k = 0; k < n_ids; ++k) {
+			if (ids[k] < 0 || ids[k] >= n) return fail(DMND_E_ARG, std::string(call) + ": sequence id outside the block");
+			letters += lim[(size_t)ids[k] + 1] - lim[(size_t)ids[k]];
+		}
+	}
+	for (int64_t i = 0; i < n; ++i)
+		if (lim[(size_t)i + 1] - lim[(size_t)i] - 1 > INT32_MAX) return fail(DMND_E_ARG, std::string(call) + ": a sequence of more than 2^31 letters");
+	if (int rc = seg_upload_tables(c)) return rc;
+	// the range list: one range per 535 letters in real proteins; DMND_SEG_RANGE_CAP (read per call: a test hook) forces it small.
+	// The kernel counts past the end of the list, the call then grows it to the count and runs the segments kernel again.
+	const char* cap_env = std::getenv("DMND_SEG_RANGE_CAP");
+	unsigned long long cap = cap_env && std::atoll(cap_env) > 0 ? (unsigned long long)std::atoll(cap_env) : (unsigned long long)(letters / 128 + 1024);
+	if (int rc = c->seg_cls.ensure((size_t)raw + 64)) return rc;
+	if (int rc = c->seg_work.ensure((size_t)n_call * sizeof(int32_t))) return rc;
+	if (int rc = c->seg_handed.ensure((size_t)n_call * sizeof(int32_t))) return rc;
+	if (int rc = c->seg_ranges.ensure((size_t)cap * sizeof(SegRange))) return rc;
+	if (int rc = c->counters.ensure(64 * sizeof(unsigned long long))) return rc;
+	if (ids) {
+		if (int rc = c->mask_ids.ensure((size_t)n_ids * sizeof(int32_t))) return rc;
+		HIP_TRY(hipMemcpyAsync(c->mask_ids.p, ids, (size_t)n_ids * sizeof(int32_t), hipMemcpyHostToDevice, st));
+	}
+	HIP_TRY(hipMemsetAsync(c->counters.p, 0, SEG_COUNTERS * sizeof(unsigned long long), st));
+	SegArgs a;
+	a.data = c->block[which].as<int8_t>();
+	a.limits = c->d_limits[which].as<int64_t>();
+	a.n_seqs = n_call;
+	a.ids = ids ? c->mask_ids.as<int32_t>() : nullptr;
+	a.cls = c->seg_cls.as<uint8_t>();
+	a.class_table = c->seg_tables.as<uint8_t>();
+	a.lnfact = reinterpret_cast<const double*>(c->seg_tables.as<uint8_t>() + SEG_TABLE_BYTES);
+	a.work = c->seg_work.as<int32_t>();
+	a.handed = c->seg_handed.as<int32_t>();
+	a.ranges = c->seg_ranges.as<SegRange>();
+	a.range_cap = cap;
+	a.counters = c->counters.as<unsigned long long>();
+	tr.lap("tables, buffers");
+	double kernel_ms = 0;
+	unsigned long long cnt[SEG_COUNTERS] = { 0, 0, 0, 0 };
+	// a phase = kernels between two events, then the counters: the host decides what runs next from them
+	auto finish_phase = [&]() -> int {
+		HIP_TRY(hipEventRecord(c->ev1, st));
+		if (int rc = download_bytes(c, cnt, c->counters.p, sizeof(cnt))) return rc;
+		float ms = 0;
+		HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+		kernel_ms += ms;
+		return DMND_OK;
+	};
+	HIP_TRY(hipEventRecord(c->ev0, st));
+	HIP_TRY(launch_seg_classes(a, st));
+	if (int rc = finish_phase()) return rc;
+	const int64_t n_work = (int64_t)cnt[SEG_N_WORK];
+	tr.lap("classes, work list");
+	for (int pass = 0; n_work > 0; ++pass) {
+		HIP_TRY(hipEventRecord(c->ev0, st));
+		HIP_TRY(launch_seg_segments(a, n_work, st));
+		if (int rc = finish_phase()) return rc;
+		if (cnt[SEG_N_RANGES] <= cap) break;
+		if (pass > 0) return fail(DMND_E_DEVICE, std::string(call) + ": the range count changed between two runs");
+		cap = cnt[SEG_N_RANGES];                             // nothing is truncated: the list grows to the count, the kernel runs again
+		if (int rc = c->seg_ranges.ensure((size_t)cap * sizeof(SegRange))) return rc;
+		a.ranges = c->seg_ranges.as<SegRange>();
+		a.range_cap = cap;
+		HIP_TRY(hipMemsetAsync(a.counters + SEG_N_RANGES, 0, 2 * sizeof(unsigned long long), st));
+	}
+	tr.lap("segments");
+	int64_t n_ranges = (int64_t)cnt[SEG_N_RANGES];
+	const int64_t n_handed = (int64_t)cnt[SEG_N_HANDED];
+	std::vector<int32_t>& list = c->seg_last;
+	list.resize((size_t)n_ranges * 4);
+	if (n_ranges) if (int rc = download_bytes(c, list.data(), c->seg_ranges.p, list.size() * sizeof(int32_t))) return rc;
+	if (n_handed > 0) {
+		// sequences the device cannot finish (a raw segment above the ln n! table): the host's seg::segments on their unmasked letters --
+		// nothing has been written yet --, their ranges merged into the list before any is applied
+		std::vector<int32_t> handed((size_t)n_handed);
+		if (int rc = download_bytes(c, handed.data(), c->seg_handed.p, handed.size() * sizeof(int32_t))) return rc;
+		std::sort(handed.begin(), handed.end());
+		std::vector<int32_t> merged;
+		for (size_t k = 0; k < list.size(); k += 4)
+			if (!std::binary_search(handed.begin(), handed.end(), list[k])) merged.insert(merged.end(), list.begin() + (std::ptrdiff_t)k, list.begin() + (std::ptrdiff_t)k + 4);
+		std::vector<int8_t> letters_of;
+		for (int32_t seq : handed) {
+			const int64_t b = lim[(size_t)seq];
+			const int len = (int)(lim[(size_t)seq + 1] - b - 1);
+			const int8_t* s = host_data ? host_data + b : nullptr;
+			if (!s) {
+				letters_of.resize((size_t)len);
+				if (int rc = download_bytes(c, letters_of.data(), c->block[which].as<int8_t>() + b, (size_t)len)) return rc;
+				s = letters_of.data();
+			}
+			int32_t order = 0;
+			for (const seg::Range& r : seg::segments(s, len)) { const int32_t q[4] = { seq, order++, r.begin, r.end }; merged.insert(merged.end(), q, q + 4); }
+		}
+		list.swap(merged);
+		n_ranges = (int64_t)list.size() / 4;
+		if (int rc = c->seg_ranges.ensure(std::max<size_t>(list.size(), 4) * sizeof(int32_t))) return rc;
+		a.ranges = c->seg_ranges.as<SegRange>();
+		if (n_ranges) HIP_TRY(copy_now(st, c->seg_ranges.p, list.data(), list.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+		tr.lap("handed-back sequences redone on the host");
+	}
+	c->seg_last_sorted = false;
+	HIP_TRY(hipEventRecord(c->ev0, st));
+	HIP_TRY(launch_seg_apply(a, n_ranges, st));
+	HIP_TRY(hipEventRecord(c->ev1, st));
+	// the host copy is patched from the range list while the apply kernel runs
+	int64_t masked = 0;
+	for (size_t k = 0; k < list.size(); k += 4) {
+		const int64_t len = (int64_t)list[k + 3] - list[k + 2] + 1;
+		masked += len;                                         // overlapping neighbours count twice, as in dmnd_seg_mask_block and the reference
+		if (host_data) std::memset(host_data + lim[(size_t)list[k]] + list[k + 2], 23, (size_t)len);
+	}
+	HIP_TRY(sync_stream(st));
+	float ms = 0;
+	HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+	kernel_ms += ms;
+	tr.lap("applied, host copy patched");
+	c->seg_stats[0] = (double)n_work; c->seg_stats[1] = (double)n_handed; c->seg_stats[2] = (double)n_ranges; c->seg_stats[3] = kernel_ms;
+	c->mask_ms = kernel_ms;
+	if (n_masked) *n_masked = masked;
+	static const size_t keep_bytes = [] { const char* e = std::getenv("DMND_MASK_SCRATCH_KEEP_MB"); return (size_t)(e ? std::max(0ll, std::atoll(e)) : 16384ll) << 20; }();
+	for (DevBuf* b : { &c->seg_cls, &c->seg_ranges }) if (b->cap > keep_bytes) b->release();
+	return DMND_OK;
+}
+
+}
+
+extern "C" int dmnd_seg_mask_block_device(dmnd_ctx* c, int which, int8_t* host_data, int64_t* n_masked)
+{
+	return seg_device_impl(c, which, host_data, nullptr, 0, n_masked);
+}
+
+extern "C" int dmnd_seg_mask_sequences_device(dmnd_ctx* c, int which, int8_t* host_data, const int32_t* seq_ids, int64_t n, int64_t* n_masked)
+{
+	if (n < 0 || (n > 0 && !seq_ids)) return fail(DMND_E_ARG, "dmnd_seg_mask_sequences_device: bad argument");
+	if (n_masked) *n_masked = 0;
+	if (n == 0) return c && (which == DMND_QUERY || which == DMND_TARGET) ? DMND_OK : fail(DMND_E_ARG, "dmnd_seg_mask_sequences_device: bad argument");
+	return seg_device_impl(c, which, host_data, seq_ids, n, n_masked);
+}
+
+extern "C" int dmnd_seg_ranges_device(dmnd_ctx* c, int which, int32_t* seq_begin_end, int64_t cap, int64_t* n)
+{
+	if (!c || (which != DMND_QUERY && which != DMND_TARGET) || !n || cap < 0 || (cap > 0 && !seq_begin_end)) return fail(DMND_E_ARG, "dmnd_seg_ranges_device: bad argument");
+	std::vector<int32_t>& list = c->seg_last;
+	if (!c->seg_last_sorted) {                                // by sequence, then in the sequence's list order
+		const size_t m = list.size() / 4;
+		std::vector<size_t> order(m);
+		for (size_t k = 0; k < m; ++k) order[k] = k;
+		std::sort(order.begin(), order.end(), [&](size_t x, size_t y) { return list[4 * x] != list[4 * y] ? list[4 * x] < list[4 * y] : list[4 * x + 1] < list[4 * y + 1]; });
+		std::vector<int32_t> sorted(list.size());
+		for (size_t k = 0; k < m; ++k) std::memcpy(&sorted[4 * k], &list[4 * order[k]], 4 * sizeof(int32_t));
+		list.swap(sorted);
+		c->seg_last_sorted = true;
+	}
+	*n = (int64_t)list.size() / 4;
+	if (*n > cap) return fail(DMND_E_CAP, "dmnd_seg_ranges_device: more ranges than the output holds");
+	for (int64_t k = 0; k < *n; ++k) { seq_begin_end[3 * k] = list[(size_t)(4 * k)]; seq_begin_end[3 * k + 1] = list[(size_t)(4 * k + 2)]; seq_begin_end[3 * k + 2] = list[(size_t)(4 * k + 3)]; }
+	return DMND_OK;
+}
+
+extern "C" int dmnd_seg_device_stats(const dmnd_ctx* c, double out[4])
+{
+	if (!c || !out) return fail(DMND_E_ARG, "dmnd_seg_device_stats: bad argument");
+	for (int i = 0; i < 4; ++i) out[i] = c->seg_stats[i];
+	return DMND_OK;
+}

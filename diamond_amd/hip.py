@@ -83,7 +83,7 @@ EXPORTS = ["dmnd_abi_version", "dmnd_last_error", "dmnd_default_params", "dmnd_c
            "dmnd_set_query_contexts", "dmnd_translate", "dmnd_format_tab_translated", "dmnd_mask_block", "dmnd_mask_kernel_ms", "dmnd_seed_params_preset", "dmnd_set_comp_based_stats",
            "dmnd_seed_params_set_index_chunks", "dmnd_join_blocks", "dmnd_set_sensitivity", "dmnd_touch_streams",
            "dmnd_seed_params_set_query_indexed", "dmnd_auto_query_indexed", "dmnd_set_motif_table", "dmnd_motif_table_size",
-           "dmnd_soft_mask_block", "dmnd_output_fields", "dmnd_format_fields", "dmnd_format_pairwise_intro", "dmnd_format_pairwise",
+           "dmnd_soft_mask_block", "dmnd_download_block", "dmnd_seg_mask_block_device", "dmnd_seg_mask_sequences_device", "dmnd_seg_ranges_device", "dmnd_seg_device_stats", "dmnd_output_fields", "dmnd_format_fields", "dmnd_format_pairwise_intro", "dmnd_format_pairwise",
            "dmnd_format_paf", "dmnd_device_count", "dmnd_set_top_percent", "dmnd_join_blocks_top", "dmnd_set_filters", "dmnd_format_sam", "dmnd_set_query_source_lengths", "dmnd_format_fields_unaligned", "dmnd_format_fields_header", "dmnd_set_query_index_reuse", "dmnd_set_no_self_hits", "dmnd_matrix_params", "dmnd_masking_lambda", "dmnd_translate_opts", "dmnd_set_extension_mode", "dmnd_format_xml_header", "dmnd_format_xml_query_intro", "dmnd_format_xml", "dmnd_format_xml_query_epilog", "dmnd_format_daa_header", "dmnd_format_daa_query", "dmnd_format_daa_match", "dmnd_seg_ranges", "dmnd_seg_mask_block", "dmnd_seg_lnfact", "dmnd_daa_match_read", "dmnd_hsp_from_transcript", "dmnd_hsp_from_transcript_frames", "dmnd_set_format_flags", "dmnd_host_alloc", "dmnd_host_free", "dmnd_share_block", "dmnd_copy_block", "dmnd_init", "dmnd_seed_reserve", "dmnd_mask_sequences", "dmnd_set_max_hsps", "dmnd_rank_targets", "dmnd_rank_update", "dmnd_set_global_ranking",
            "dmnd_upload_matrices", "dmnd_frameshift_swipe", "dmnd_set_frameshift", "dmnd_set_context_motif_table", "dmnd_cbs_composition", "dmnd_cbs_rule", "dmnd_cbs_target_matrix", "dmnd_cbs_ideal_lambda", "dmnd_join_blocks_range", "dmnd_join_blocks_device", "dmnd_join_blocks_device_host", "dmnd_join_ranks", "dmnd_join_ranks_plan", "dmnd_xdrop_ungapped"]
 
@@ -726,6 +726,13 @@ class Context:
         self.lib.dmnd_copy_block.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
         self._check(self.lib.dmnd_copy_block(self.h, int(which), src.h))
 
+    def download_block(self, which, raw_len):
+        """The letters of block `which` as they stand in HBM (int8 array of the block's raw length): dmnd_download_block."""
+        out = np.zeros(int(raw_len), np.int8)
+        self.lib.dmnd_download_block.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64]
+        self._check(self.lib.dmnd_download_block(self.h, int(which), out.ctypes.data, ctypes.c_int64(out.size)))
+        return out
+
     def frameshift_swipe(self, items, score_only, frame_shift=15, channels=16, with_transcripts=True):
         """banded_3frame_swipe for many (query strand, target) items (FS_TARGET_DTYPE) -> (FS_HSP_DTYPE[], transcript bytes or None)."""
         items = np.ascontiguousarray(items, dtype=FS_TARGET_DTYPE)
@@ -816,6 +823,47 @@ class Context:
 
     def mask_kernel_ms(self):
         return float(self.lib.dmnd_mask_kernel_ms(self.h))
+
+    def seg_mask_block(self, which, host_data=None):
+        """SEG masking of the uploaded block in HBM (hard mask, letter 23; dmnd_seg_mask_block_device): the masks of the host's
+        seg_mask_block, bit for bit. host_data as for mask_block. Returns the sum of the masked ranges' lengths."""
+        n = ctypes.c_int64(0)
+        ptr = None
+        if host_data is not None:
+            assert host_data.dtype == np.int8 and host_data.flags["C_CONTIGUOUS"]
+            ptr = host_data.ctypes.data
+        self.lib.dmnd_seg_mask_block_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)]
+        self._check(self.lib.dmnd_seg_mask_block_device(self.h, int(which), ptr, ctypes.byref(n)))
+        return n.value
+
+    def seg_mask_sequences(self, which, host_data, seq_ids):
+        """SEG on the given sequences of the block only (dmnd_seg_mask_sequences_device); host_data as for mask_block."""
+        ids = np.ascontiguousarray(seq_ids, dtype=np.int32)
+        n = ctypes.c_int64(0)
+        ptr = None
+        if host_data is not None:
+            assert host_data.dtype == np.int8 and host_data.flags["C_CONTIGUOUS"]
+            ptr = host_data.ctypes.data
+        self.lib.dmnd_seg_mask_sequences_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]
+        self._check(self.lib.dmnd_seg_mask_sequences_device(self.h, int(which), ptr, ids.ctypes.data, ctypes.c_int64(ids.size), ctypes.byref(n)))
+        return n.value
+
+    def seg_ranges(self, which):
+        """The ranges of the last seg_mask_block / seg_mask_sequences as an int32 array of (sequence id, begin, end) rows, sorted by
+        sequence and in the reference's list order within one (dmnd_seg_ranges_device)."""
+        self.lib.dmnd_seg_ranges_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]
+        n = ctypes.c_int64(0)
+        self.lib.dmnd_seg_ranges_device(self.h, int(which), None, 0, ctypes.byref(n))
+        out = np.zeros((max(n.value, 1), 3), np.int32)
+        self._check(self.lib.dmnd_seg_ranges_device(self.h, int(which), out.ctypes.data, ctypes.c_int64(out.shape[0]), ctypes.byref(n)))
+        return out[:n.value]
+
+    def seg_stats(self):
+        """Of the last SEG call on the device: dict(work=sequences with a trigger window, handed_back, ranges, kernel_ms)."""
+        self.lib.dmnd_seg_device_stats.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        out = (ctypes.c_double * 4)()
+        self._check(self.lib.dmnd_seg_device_stats(self.h, out))
+        return dict(work=int(out[0]), handed_back=int(out[1]), ranges=int(out[2]), kernel_ms=float(out[3]))
 
     def soft_mask_block(self, which):
         """Motif soft masking of the uploaded block (after mask_block): builds the view that seeds are generated from; the

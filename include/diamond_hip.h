@@ -147,6 +147,9 @@ int dmnd_share_block(dmnd_ctx* ctx, int which, const dmnd_ctx* src);
  * a working copy in another (dmnd_mask_block works in place) -- the reference re-reads or keeps unmasked letters the same way when
  * a block is searched by several query blocks (Block::soft_mask / remove_soft_masking, src/data/block/block.cpp:164-177). */
 int dmnd_copy_block(dmnd_ctx* ctx, int which, const dmnd_ctx* src);
+/* Copies the letters of block `which` as they stand in HBM (masks included) into data[0, data_len); data_len must be the raw length
+ * the block was uploaded with. For tests and for a caller that kept no host copy; the masking calls patch a host copy on their own. */
+int dmnd_download_block(dmnd_ctx* ctx, int which, int8_t* data, int64_t data_len);
 /* Uploads the per-query Hauser composition-bias vectors (HauserCorrection::int8,
  * src/stats/hauser_correction.cpp:107), concatenated; dmnd_dp_target::cbs_off indexes this buffer. */
 int dmnd_upload_cbs(dmnd_ctx* ctx, const int8_t* cbs, int64_t len);
@@ -414,14 +417,29 @@ double dmnd_mask_kernel_ms(const dmnd_ctx* ctx);
  * the reference then uses too. */
 double dmnd_masking_lambda(const dmnd_params* params);
 /* SEG low-complexity masking (`--masking seg`: the reference then hard-masks the reference block with NCBI's SEG and leaves the queries
- * alone, src/run/config.cpp:125-134, src/masking/masking.cpp:172-192, src/lib/blast/blast_seg.cpp). Host code, as in the reference:
- * the driver masks the block it is about to upload. dmnd_seg_ranges: the segments [begin, end] (inclusive) of one sequence (letters
+ * alone, src/run/config.cpp:125-134, src/masking/masking.cpp:172-192, src/lib/blast/blast_seg.cpp). The host form, as in the reference:
+ * a driver masks the block it is about to upload (the device form follows below). dmnd_seg_ranges: the segments [begin, end] (inclusive) of one sequence (letters
  * 0-25), ascending; *n = their number (DMND_E_CAP if above cap). dmnd_seg_mask_block: letter 23 over every segment of every sequence
  * of a SequenceSet block (data, limits as for dmnd_upload_block), `threads` host threads. dmnd_seg_lnfact: the ln(n!) SEG computes
  * with (six-decimal table up to 10000, Stirling above). */
 int dmnd_seg_ranges(const int8_t* seq, int32_t len, int32_t* ranges, int32_t cap, int32_t* n);
 int dmnd_seg_mask_block(int8_t* data, const int64_t* limits, int64_t n_seqs, int threads, int64_t* n_masked);
 double dmnd_seg_lnfact(uint32_t n);
+/* SEG on the device: the same masks, bit for bit, computed on the block in HBM (csrc/seg_kernels.hip; arithmetic shared with the CPU
+ * emulator in csrc/seg_core.h). Semantics as for dmnd_mask_block / dmnd_mask_sequences: in place, refused on a block shared
+ * from another context, the motif view of the block is dropped, the query generation is bumped for the query block; host_data (may be
+ * NULL) = the caller's host copy of the block, patched from the list of ranges, not by copying the block back; *n_masked (may be NULL)
+ * = the sum of the ranges' lengths -- overlapping neighbours of one sequence count twice, as in dmnd_seg_mask_block and in the reference.
+ * No letter is written before every range of the call is known (trims read the original letters, and neighbouring segments overlap).
+ * A sequence with a raw segment of more than 10 000 letters -- ln n! above the table is Stirling's formula, with a log -- is handed back:
+ * the call runs the host code on its unmasked letters and merges the ranges before they are applied. dmnd_seg_ranges_device: the ranges
+ * of the context's last device call as (sequence id, begin, end) triples, sorted by sequence and in the reference's list order within
+ * one; *n = their number (DMND_E_CAP if above cap). dmnd_seg_device_stats: out[0] = sequences on the work list (they hold a trigger
+ * window), out[1] = sequences handed back to the host, out[2] = ranges, out[3] = kernel milliseconds of the last call. */
+int dmnd_seg_mask_block_device(dmnd_ctx* ctx, int which, int8_t* host_data, int64_t* n_masked);
+int dmnd_seg_mask_sequences_device(dmnd_ctx* ctx, int which, int8_t* host_data, const int32_t* seq_ids, int64_t n, int64_t* n_masked);
+int dmnd_seg_ranges_device(dmnd_ctx* ctx, int which, int32_t* seq_begin_end, int64_t cap, int64_t* n);
+int dmnd_seg_device_stats(const dmnd_ctx* ctx, double out[4]);
 /* Motif soft masking (default on up to --sensitive: sensitivity_traits.motif_masking, search/setup.cpp:40-53,322-335): while seeds
  * are enumerated the reference masks stretches covered by abundant 8-mer motifs (mask_motifs, masking/masking.cpp:110-131; the
  * letters come back before the filters and the extension run, Block::soft_mask / remove_soft_masking, data/block/block.cpp:164-177),

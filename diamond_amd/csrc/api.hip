@@ -49,7 +49,7 @@ static int sync_spin_us()
 	return tuning().sync_spin_us;
 }
 
-hipError_t dmnd::wait_event(hipEvent_t ev)
+hipError_t dmnd::wait_event(hipEvent_t ev, double* hint_us)
 {
 	if (spin_sync()) return hipEventSynchronize(ev);
 	// Poll, then sleep between polls: 0.7 CPU-ms per 50 ms of kernel (tools/probes/wait_probe.hip), as cheap as the runtime's
@@ -57,20 +57,41 @@ hipError_t dmnd::wait_event(hipEvent_t ev)
 	// step in ~100 of the C2 bench took 10 - 50 ms (a wait that slept through its completion until a timeout), with the sleeping
 	// poll none. The sleeps grow from 20 to 200 us: a short kernel is picked up within microseconds, a long one costs a poll per 0.2 ms.
 	const int spin_us = sync_spin_us();
-	const auto t0 = std::chrono::steady_clock::now();
+	// hint_us: how long the same wait of the same context is expected to take (0: unknown; the caller keeps the estimate from the
+	// durations this function reports). The one wait behind a chain of kernels of 2-3 ms would run through the busy poll and all the
+	// growing sleeps and find its completion up to 200 us late: it sleeps ONCE for three quarters of the hint instead, then polls as
+	// every wait does -- busily at first -- but with sleeps that stay at 50 us until twice the hint has passed. The CPU time of a
+	// wait stays bounded: one sleep, the same busy poll, and a query per 50 us instead of per 200 us for a few milliseconds.
+	auto t0 = std::chrono::steady_clock::now();
+	const auto t_wait = t0;
+	double fine_until_us = 0.0;
+	auto finish = [&](hipError_t e) {
+		if (hint_us) *hint_us = e == hipSuccess ? std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_wait).count() : 0.0;
+		return e;
+	};
+	if (hint_us && *hint_us > 2.0 * spin_us) {
+		const hipError_t q = hipEventQuery(ev);
+		if (q != hipErrorNotReady) return finish(q);
+		const long ns = (long)(std::min(*hint_us, 50000.0) * 750.0);
+		timespec ts{ 0, ns };
+		nanosleep(&ts, nullptr);
+		t0 = std::chrono::steady_clock::now();
+		fine_until_us = 2.0 * std::min(*hint_us, 50000.0);
+	}
 	long sleep_ns = 20000;
 	for (;;) {
 		const hipError_t q = hipEventQuery(ev);
-		if (q == hipSuccess) return hipSuccess;
-		if (q != hipErrorNotReady) return q;
+		if (q == hipSuccess) return finish(hipSuccess);
+		if (q != hipErrorNotReady) return finish(q);
 		if (std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count() < spin_us) continue;
 		timespec ts{ 0, sleep_ns };
 		nanosleep(&ts, nullptr);
 		if (sleep_ns < 200000) sleep_ns += sleep_ns / 2;
+		if (fine_until_us > 0.0 && sleep_ns > 50000 && std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_wait).count() < fine_until_us) sleep_ns = 50000;
 	}
 }
 
-hipError_t dmnd::sync_stream(hipStream_t s)
+hipError_t dmnd::sync_stream(hipStream_t s, double* hint_us)
 {
 	if (spin_sync()) return hipStreamSynchronize(s);
 	hipEvent_t ev = nullptr;
@@ -88,7 +109,7 @@ hipError_t dmnd::sync_stream(hipStream_t s)
 	}
 	const hipError_t e = hipEventRecord(ev, s);
 	if (e != hipSuccess) return e;
-	return wait_event(ev);
+	return wait_event(ev, hint_us);
 }
 
 void dmnd::forget_stream(hipStream_t s)
@@ -344,6 +365,7 @@ extern "C" void dmnd_destroy(dmnd_ctx* c)
 	for (int i = 0; i < 2; ++i) { c->t_stage[i].release(); if (c->t_ev[i]) (void)hipEventDestroy(c->t_ev[i]); c->t_ev[i] = nullptr; }
 	if (c->t_stream) { (void)hipStreamSynchronize(c->t_stream); forget_stream(c->t_stream); (void)hipStreamDestroy(c->t_stream); c->t_stream = nullptr; }
 	delete c->kts; c->kts = nullptr;
+	c->seed_ret_h.release();
 	for (dmnd_ctx* a : c->aux) dmnd_destroy(a);
 	c->aux.clear();
 	(void)hipSetDevice(c->device);
@@ -351,7 +373,7 @@ extern "C" void dmnd_destroy(dmnd_ctx* c)
 	for (DevBuf* b : { &c->block[0], &c->block[1], &c->cbs, &c->matrix, &c->bias_ids, &c->items, &c->order, &c->p_of_slot, &c->trace_off,
 		&c->transcript_off, &c->ends, &c->hsps, &c->trace, &c->transcript, &c->status, &c->pairs, &c->trace_off_item, &c->host_q, &c->host_t, &c->host_cbs,
 		&c->d_limits[0], &c->d_limits[1], &c->qid_of, &c->mask_time, &c->seed_keys, &c->seed_next, &c->seed_qlist, &c->seed_qkeys, &c->seed_slot2, &c->seed_loc2, &c->seed_survivors, &c->seed_scored, &c->seed_need, &c->seed_qfold, &c->seed_tfold, &c->seed_tcodes, &c->seed_tflags, &c->seed_tplanes, &c->seed_tclass,
-		&c->matched_slot, &c->matched_loc, &c->counters, &c->seed_hits, &c->seed_bitmap, &c->seed_deferred, &c->seed_eslot, &c->seed_eloc, &c->seed_hits_sorted, &c->sort_keys[0], &c->sort_keys[1], &c->sort_idx[0], &c->sort_idx[1], &c->gf_tables, &c->gf_hits, &c->gf_flags, &c->gf_scores, &c->gf_units, &c->alt_targets, &c->mask_lr, &c->mask_pb, &c->mask_scale, &c->mask_pos, &c->mask_ids, &c->mask_soff, &c->mask_long_ids, &c->mask_long_soff, &c->mask_long_pb, &c->mask_long_scale, &c->soft[0], &c->soft[1], &c->motif_hit, &c->motif_table, &c->seg_tables, &c->seg_cls, &c->seg_work, &c->seg_handed, &c->seg_ranges, &c->adj_matrices, &c->join_keep, &c->join_pos, &c->join_in, &c->join_out, &c->join_recv })
+		&c->matched_slot, &c->matched_loc, &c->counters, &c->seed_hits, &c->seed_bitmap, &c->seed_deferred, &c->seed_eslot, &c->seed_eloc, &c->seed_hits_sorted, &c->seed_ret, &c->sort_keys[0], &c->sort_keys[1], &c->sort_idx[0], &c->sort_idx[1], &c->gf_tables, &c->gf_hits, &c->gf_flags, &c->gf_scores, &c->gf_units, &c->alt_targets, &c->mask_lr, &c->mask_pb, &c->mask_scale, &c->mask_pos, &c->mask_ids, &c->mask_soff, &c->mask_long_ids, &c->mask_long_soff, &c->mask_long_pb, &c->mask_long_scale, &c->soft[0], &c->soft[1], &c->motif_hit, &c->motif_table, &c->seg_tables, &c->seg_cls, &c->seg_work, &c->seg_handed, &c->seg_ranges, &c->adj_matrices, &c->join_keep, &c->join_pos, &c->join_in, &c->join_out, &c->join_recv })
 		b->release();
 	if (c->ev0) (void)hipEventDestroy(c->ev0);
 	if (c->ev1) (void)hipEventDestroy(c->ev1);

@@ -39,8 +39,10 @@ inline bool spin_sync()
 // The event used to be thread-local: the extension stage's runner threads are short-lived, so every dmnd_extend call leaked a
 // handful of events and their interrupt signals, and after a few thousand calls the driver's finite pool of them ran out --
 // waits then returned early ("device not ready" from hipEventElapsedTime, stale results behind copy_now).
-hipError_t sync_stream(hipStream_t s);
-hipError_t wait_event(hipEvent_t ev);      // the wait of sync_stream on an event of the caller's: polls DMND_SYNC_SPIN_US microseconds, then sleeps
+// hint_us (optional): in, the previous duration of the same wait in microseconds (0 = unknown): the wait sleeps once for most of it
+// before it polls; out, how long this wait took
+hipError_t sync_stream(hipStream_t s, double* hint_us = nullptr);
+hipError_t wait_event(hipEvent_t ev, double* hint_us = nullptr);      // the wait of sync_stream on an event of the caller's: polls DMND_SYNC_SPIN_US microseconds, then sleeps
 void forget_stream(hipStream_t s);
 
 inline hipError_t copy_now(hipStream_t s, void* dst, const void* src, size_t bytes, hipMemcpyKind kind)
@@ -149,6 +151,15 @@ struct dmnd_ctx {
 	void* sort_tmp = nullptr; size_t sort_tmp_bytes = 0;      // rocPRIM radix sort scratch
 	dmnd::DevBuf join_keep, join_pos, join_in, join_out, join_recv;      // dmnd_join_blocks_device: survivor flags and their numbers; staging of the host form
 	int64_t n_seed_hits = 0;
+	// chain mode of the seed search (seed_chain.h): the readback (counter block + leading sorted hits) in HBM and page-locked on the
+	// host, how many sorted hits the host copy holds (-1: none, dmnd_seed_hits copies from seed_hits_sorted), the last duration of the chain's one wait
+	dmnd::DevBuf seed_ret;
+	dmnd::PinBuf seed_ret_h;
+	int64_t seed_ret_hits = -1;
+	size_t seed_ret_bytes_header = 0;
+	double seed_chain_wait_us = 0.0;
+	int seed_chain_rest = 0;                   // searches that leave the chain out by default (seed_api.hip chain_by_default)
+	int64_t seed_last_hits = -1;               // hits of the context's last complete seed search (-1: none yet): sizes the chain's readback
 	// gapped filter (gapped_api.hip)
 	dmnd::DevBuf gf_tables, gf_hits, gf_flags, gf_scores, gf_units;
 	double gapped_filter_evalue = 0.0, gf_ms = 0.0;

@@ -398,6 +398,11 @@ static int seed_reserve(dmnd_ctx* c, const SeedParams& sp, const SeedSizes& z, i
 		if (int rc = c->seed_survivors.ensure(((size_t)1 << 20) * sizeof(SeedSurvivor))) return rc;
 		if (int rc = c->seed_qfold.ensure((size_t)(q_block_len + 1) / 2 + 64)) return rc;
 	}
+	else {
+		// chain mode: the survivor and scored lists at the capacity its first search starts from
+		if (int rc = c->seed_survivors.ensure(((size_t)1 << 20) * sizeof(SeedSurvivor))) return rc;
+		if (int rc = c->seed_scored.ensure(((size_t)1 << 20) * sizeof(SeedScored))) return rc;
+	}
 	return DMND_OK;
 }
 
@@ -438,6 +443,35 @@ static int seed_deferred_pass(dmnd_ctx* c, SeedArgs a, int sid, int64_t n_matche
 	return DMND_OK;
 }
 
+// Whether a search that DMND_SEED_CHAIN does not force takes the chain (seed_chain.h). Two measured exceptions:
+//  * long seeds by key class (query blocks above 2^24 positions, C5): with the chain the step went from 35.6 to 38.4-39.5 ms although
+//    the seed calls got shorter -- the extension bounds that step, and a seed stage without idle gaps takes device time from it;
+//  * a context whose last chain met something no buffer growth removes (deferred pairs, the tiled filter, more hits than the padded
+//    sort holds: chain_rests_after) leaves the chain out for the next SEED_CHAIN_REST searches: there the chain only adds its
+//    readback and an unused sort (C4, deferred pairs in every search: 9.2 ms per step this way, 9.55 with the chain tried every time).
+enum { SEED_CHAIN_REST = 15 };
+static bool chain_by_default(dmnd_ctx* c, bool classes_long)
+{
+	if (classes_long) return false;
+	if (c->seed_chain_rest > 0) { --c->seed_chain_rest; return false; }
+	return true;
+}
+static bool chain_rests_after(const ChainPlan& plan, unsigned long long status)
+{
+	return plan.point == CHAIN_FROM_DEFERRED || plan.point == CHAIN_FROM_SORT || (status & CHAIN_TILED) != 0;
+}
+
+// The chain's two sizes: the tuning values (csrc/tuning.h), or per call what the tests' hooks of the same names say
+static int64_t chain_sort_cap()
+{
+	return std::min<int64_t>(seed_cap("DMND_SEED_SORT_CAP", tuning().seed_sort_cap), (int64_t)1 << 24);
+}
+static int64_t chain_readback_bytes()
+{
+	const char* e = getenv("DMND_SEED_READBACK_BYTES");
+	return std::min<int64_t>(e ? std::max<int64_t>(0, atoll(e)) : tuning().seed_readback_bytes, (int64_t)1 << 30);
+}
+
 extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int64_t* n_hits)
 {
 	if (!c || !params || !n_hits) return fail(DMND_E_ARG, "dmnd_seed_search: NULL argument");
@@ -449,6 +483,7 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 	};
 	*n_hits = 0;
 	c->n_seed_hits = 0;                                  // a failed or empty search must not leave the previous search's hits behind
+	c->seed_ret_hits = -1;
 	const std::vector<int64_t>& ql = c->limits[DMND_QUERY];
 	const std::vector<int64_t>& tl = c->limits[DMND_TARGET];
 	if (ql.size() < 2 || tl.size() < 2) return fail(DMND_E_ARG, "dmnd_seed_search: both blocks must be uploaded with limits");
@@ -519,13 +554,13 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 	if (int rc = seed_reserve(c, sp, z, nq_pos, q_end, c->block_len[DMND_QUERY], false)) return rc;
 	lap("buffers ensured");
 	static const bool phases = getenv("DMND_SEED_PHASES") != nullptr;
-	const bool counters_new = c->counters.cap < (size_t)(S + 16) * sizeof(unsigned long long);
-	if (int rc = c->counters.ensure((size_t)(S + 16) * sizeof(unsigned long long))) return rc;      // [S] hits, [S+1] deferred pairs, [S+2] collected positions, [S+3] Hamming survivors, [S+4] scored survivors
+	const bool counters_new = c->counters.cap < (size_t)chain_ctr_words(S) * sizeof(unsigned long long);
+	if (int rc = c->counters.ensure((size_t)chain_ctr_words(S) * sizeof(unsigned long long))) return rc;      // [S] hits, [S+1] deferred pairs, [S+2] collected positions, [S+3] Hamming survivors, [S+4] scored survivors, [S+5 ..] chain mode (seed_chain.h)
 	// everything a search starts from, in ONE launch (launch_seed_clear): the counters, the mask times, the need map and -- unless the
 	// query side is kept from the last call -- bitmaps and table
 	{
 		SeedClear z;
-		z.add(c->counters.p, (size_t)((phases || counters_new) ? S + 16 : S + 5) * sizeof(unsigned long long), 0);
+		z.add(c->counters.p, (size_t)((phases || counters_new) ? S + 16 : S + 8) * sizeof(unsigned long long), 0);
 		z.add(c->mask_time.p, (size_t)c->block_len[DMND_QUERY] + 256, SEED_NEVER);
 		z.add(c->seed_need.p, (size_t)(slots / 32) * sizeof(uint32_t), 0);
 		if (!index_ready) {
@@ -616,6 +651,8 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 	}
 	std::vector<unsigned long long> counts((size_t)S + 1, 0);
 	unsigned long long n_pairs = 0;
+	bool hits_done = false;                              // the sorted hits are in place (chain mode)
+	char path[128] = "host";                             // DMND_TRACE: the path the search took (seed_chain.h)
 	// Short seeds: one pass per shape -- index, stream with the Hamming filter fused in, mask, stage-2 scoring of the survivors,
 	// deferred pairs. A shape's masks only depend on this and earlier shapes, and so does the left-most rule (t_now).
 	if (fused) {
@@ -734,11 +771,148 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 	std::vector<int64_t> m_off((size_t)S + 1, 0);
 	// start from what earlier calls already grew the buffers to: a repeated search of the same scale never takes the overflow path
 	int64_t cap_total = seed_cap("DMND_SEED_MATCHED_CAP", std::max<int64_t>(std::max<int64_t>((int64_t)1 << 22, 4 * nq_pos), (int64_t)std::min(c->matched_loc.cap / sizeof(int64_t), c->matched_slot.cap / sizeof(uint32_t))));
+	// what sort_seed_hits needs to know about the blocks
+	auto bits_of = [](uint64_t v) { int b = 1; while (b < 64 && (v >> b) != 0) ++b; return b; };
+	const std::vector<int64_t>& qlim = c->limits[DMND_QUERY];
+	if (c->max_query_len_generation != c->query_generation || c->max_query_len <= 0) {
+		int64_t m = 1;
+		for (size_t i = 0; i + 1 < qlim.size(); ++i) m = std::max(m, qlim[i + 1] - qlim[i]);
+		c->max_query_len = m; c->max_query_len_generation = c->query_generation;
+	}
+	const int query_bits = bits_of((uint64_t)std::max<size_t>(qlim.size(), 2) - 1), subject_bits = bits_of((uint64_t)c->block_len[DMND_TARGET]), off_bits = bits_of((uint64_t)c->max_query_len);
+	// ---- Chain mode (seed_chain.h; DMND_SEED_CHAIN=0/1 forces the host-driven path or the chain, read per call): everything from
+	// here to the sorted hits is enqueued without a host wait, one copy brings back the counters, the status word and the leading
+	// hits, and the host-driven code below is the continuation where the status word asks for one.
+	const int chain_env = [] { const char* e = getenv("DMND_SEED_CHAIN"); return e ? (atoi(e) != 0 ? 1 : 0) : -1; }();
+	const bool chain_on = chain_env >= 0 ? chain_env != 0 : chain_by_default(c, classes_long);
+	bool phase1_done = false, dirty = false;             // dirty: an abandoned chain has used the counters, tables and filters
+	int p2_first = 0, deferred_sid = -1;                 // continuation of phase 2: first shape of the pair filter; shape whose deferred pass comes first
+	bool p2_keep = false;                                // ... the hits of the shapes before it are in seed_hits
+	unsigned long long deferred_n = 0;
+	int64_t kept_hit_cap = 0, kept_def_cap = 0, grown_hit_cap = 0, grown_def_cap = 0;
+	if (chain_on) {
+		const int64_t surv_cap = seed_cap("DMND_SEED_SURVIVOR_CAP", std::max<int64_t>((int64_t)1 << 20, (int64_t)std::min(c->seed_survivors.cap / sizeof(SeedSurvivor), c->seed_scored.cap / sizeof(SeedScored))));
+		const int64_t hit_cap = seed_cap("DMND_SEED_HIT_CAP", std::max<int64_t>((int64_t)1 << 20, (int64_t)(c->seed_hits.cap / sizeof(dmnd_seed_hit))));
+		const int64_t def_cap = seed_cap("DMND_SEED_DEFERRED_CAP", std::max<int64_t>((int64_t)1 << 18, (int64_t)(c->seed_deferred.cap / sizeof(SeedDeferred))));
+		int64_t tiled_from = (int64_t)1 << 22;
+		if (const char* e = getenv("DMND_SEED_TILED")) tiled_from = atoi(e) != 0 ? 0 : INT64_MAX;
+		const int64_t sort_cap = chain_sort_cap();
+		const int64_t ret_hits = chain_ret_hits(chain_readback_bytes(), (int64_t)sizeof(dmnd_seed_hit), sort_cap);
+		const size_t ret_bytes = chain_ret_header_bytes(S) + (size_t)ret_hits * sizeof(dmnd_seed_hit);
+		if (int rc = c->matched_slot.ensure((size_t)cap_total * sizeof(uint32_t))) return rc;
+		if (int rc = c->matched_loc.ensure((size_t)cap_total * sizeof(int64_t))) return rc;
+		if (int rc = c->seed_survivors.ensure((size_t)surv_cap * sizeof(SeedSurvivor))) return rc;
+		if (int rc = c->seed_scored.ensure((size_t)surv_cap * sizeof(SeedScored))) return rc;
+		if (int rc = c->seed_hits.ensure((size_t)hit_cap * sizeof(dmnd_seed_hit))) return rc;
+		if (int rc = c->seed_deferred.ensure((size_t)def_cap * sizeof(SeedDeferred))) return rc;
+		if (int rc = c->seed_hits_sorted.ensure((size_t)sort_cap * sizeof(dmnd_seed_hit))) return rc;
+		for (int k = 0; k < 2; ++k) {
+			if (int rc = c->sort_keys[k].ensure((size_t)sort_cap * sizeof(uint64_t))) return rc;
+			if (int rc = c->sort_idx[k].ensure((size_t)sort_cap * sizeof(uint32_t))) return rc;
+		}
+		if (int rc = c->seed_ret.ensure(ret_bytes)) return rc;
+		if (int rc = c->seed_ret_h.ensure(ret_bytes)) return rc;
+		SeedChain ch;
+		ch.ctr = c->counters.as<unsigned long long>(); ch.S = S;
+		ch.matched_cap = cap_total; ch.survivor_cap = surv_cap; ch.hit_cap = hit_cap; ch.tiled_from = tiled_from;
+		auto chain_args = [&](int sid) {
+			SeedArgs a = args_for(sid, cap_total, 0);          // the whole shared lists: the shape's range is in the counter block
+			a.hits = c->seed_hits.as<dmnd_seed_hit>(); a.hit_cap = hit_cap;
+			a.deferred = c->seed_deferred.as<SeedDeferred>(); a.deferred_cap = def_cap;
+			a.survivors = c->seed_survivors.as<SeedSurvivor>(); a.survivor_cap = surv_cap;
+			a.scored = c->seed_scored.as<SeedScored>();
+			return a;
+		};
+		for (int sid = 0; sid < S; ++sid) {
+			const SeedArgs a = chain_args(sid);
+			tm.start();
+			if (int rc = query_side(a, sid, !index_ready)) return rc;
+			tm.stop(c->seed_ms[0]);
+			tm.start();
+			HIP_TRY(launch_seed_stream(a, sid, st));
+			tm.stop(c->seed_ms[1]);
+			HIP_TRY(launch_seed_chain_streamed(ch, sid, st));
+		}
+		for (int sid = 0; sid < S && sp.seed_encoding == SEED_SPACED; ++sid) {
+			tm.start();
+			HIP_TRY(launch_seed_chain_mask(chain_args(sid), ch, sid, st));
+			tm.stop(c->seed_ms[2]);
+		}
+		for (int sid = 0; sid < S; ++sid) {
+			tm.start();
+			HIP_TRY(launch_seed_chain_shape(chain_args(sid), ch, sid, st));
+			tm.stop(c->seed_ms[3]);
+		}
+		{
+			uint64_t* keys[2] = { c->sort_keys[0].as<uint64_t>(), c->sort_keys[1].as<uint64_t>() };
+			uint32_t* idx[2] = { c->sort_idx[0].as<uint32_t>(), c->sort_idx[1].as<uint32_t>() };
+			HIP_TRY(launch_seed_chain_sort(ch, true, c->seed_hits.as<dmnd_seed_hit>(), c->seed_hits_sorted.as<dmnd_seed_hit>(), sort_cap, keys, idx, &c->sort_tmp, &c->sort_tmp_bytes, st,
+				query_bits, subject_bits, off_bits, !sp.use_ungapped, c->seed_ret.as<char>(), ret_hits));
+		}
+		// the copy is on the call's serial path: of the hits that the budget allows it carries as many as the context's last search
+		// found plus a quarter (more hits than that: dmnd_seed_hits copies, and the next search's readback is sized for them)
+		const int64_t copy_hits = c->seed_last_hits < 0 ? ret_hits : std::min<int64_t>(ret_hits, c->seed_last_hits + c->seed_last_hits / 4 + 1024);
+		HIP_TRY(hipMemcpyAsync(c->seed_ret_h.p, c->seed_ret.p, chain_ret_header_bytes(S) + (size_t)copy_hits * sizeof(dmnd_seed_hit), hipMemcpyDeviceToHost, st));
+		lap("chain enqueued");
+		{
+			// the expected length of this wait: drops to a shorter wait at once, follows longer ones by an eighth per call (a call
+			// that ran beside a busy extension must not make the next ones sleep through their completion)
+			double d = c->seed_chain_wait_us;
+			HIP_TRY(sync_stream(st, &d));
+			c->seed_chain_wait_us = (c->seed_chain_wait_us <= 0.0 || d < c->seed_chain_wait_us) ? d : c->seed_chain_wait_us + (d - c->seed_chain_wait_us) / 8;
+		}
+		lap("chain waited for");
+		pristine = false;
+		const unsigned long long* r = c->seed_ret_h.as<unsigned long long>();
+		const unsigned long long status = r[chain_ctr_status(S)], done = r[chain_ctr_done(S)];
+		for (int sid = 0; sid < S; ++sid) {
+			m_off[sid] = sid ? (int64_t)r[sid - 1] : 0;
+			counts[sid] = r[sid] - (unsigned long long)m_off[sid];
+		}
+		m_off[S] = (int64_t)r[S - 1];
+		const ChainPlan plan = chain_plan(status, done, S, sort_seed_hits_one_key(query_bits, subject_bits, off_bits));
+		chain_path_name(path, sizeof(path), plan, status);
+		c->seed_trace.assign((size_t)2 * S, 0);
+		for (int sid = 0; sid < S && (unsigned long long)sid < done + ((status & (CHAIN_SURVIVORS_OVER | CHAIN_HITS_OVER | CHAIN_DEFERRED)) ? 1 : 0); ++sid) c->seed_trace[sid] = r[chain_ctr_survivors_of(S) + sid];
+		phase1_done = plan.point != CHAIN_FROM_PHASE1;
+		kept_hit_cap = hit_cap; kept_def_cap = def_cap;
+		if (chain_env < 0 && chain_rests_after(plan, status)) c->seed_chain_rest = SEED_CHAIN_REST;
+		switch (plan.point) {
+		case CHAIN_COMPLETE:
+			hits_done = true;
+			c->n_seed_hits = (int64_t)r[S];
+			if (c->n_seed_hits <= copy_hits) { c->seed_ret_hits = c->n_seed_hits; c->seed_ret_bytes_header = chain_ret_header_bytes(S); }
+			break;
+		case CHAIN_FROM_PHASE1:
+			dirty = true;
+			for (int k = 0; k < 4; ++k) tm.discard(&c->seed_ms[k]);      // the abandoned attempt does not count
+			if (lap_on) std::fprintf(stderr, "dmnd_seed_search: joined-position buffer overflow, %lld positions against a capacity of %lld: phase 1 runs again\n", (long long)m_off[S], (long long)cap_total);
+			cap_total = m_off[S] + m_off[S] / 8 + 1024;
+			break;
+		case CHAIN_FROM_PAIRS:
+			p2_first = plan.shape; p2_keep = true;
+			break;
+		case CHAIN_FROM_DEFERRED:
+			deferred_n = r[S + 1];
+			c->seed_trace[S + plan.shape] = deferred_n;
+			if ((int64_t)deferred_n > def_cap) { grown_def_cap = (int64_t)deferred_n + 1024; tm.discard(&c->seed_ms[3]); }      // an incomplete list: phase 2 again
+			else { deferred_sid = plan.shape; p2_first = plan.shape + 1; p2_keep = true; }
+			break;
+		case CHAIN_FROM_PHASE2:
+			grown_hit_cap = (int64_t)r[S] + 1024;
+			tm.discard(&c->seed_ms[3]);
+			break;
+		case CHAIN_FROM_SORT:
+			p2_first = S; p2_keep = true;
+			break;
+		}
+	}
+	if (!phase1_done) {
 	for (int attempt = 0;; ++attempt) {
 		if (int rc = c->matched_slot.ensure((size_t)cap_total * sizeof(uint32_t))) return rc;
 		if (int rc = c->matched_loc.ensure((size_t)cap_total * sizeof(int64_t))) return rc;
-		if (attempt > 0) {
-			HIP_TRY(hipMemsetAsync(c->counters.p, 0, (size_t)(S + 5) * sizeof(unsigned long long), st));
+		if (attempt > 0 || dirty) {
+			HIP_TRY(hipMemsetAsync(c->counters.p, 0, (size_t)(S + 8) * sizeof(unsigned long long), st));
 			HIP_TRY(hipMemsetAsync(c->seed_keys.p, 0xff, (size_t)S * slot_bytes, st));
 			HIP_TRY(hipMemsetAsync(c->seed_bitmap.p, 0, bm_total, st));
 		}
@@ -749,7 +923,7 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 			// after an overflow the remaining shapes only count (capacity 0): a negative capacity would pass the kernels' unsigned bound test
 			SeedArgs a = args_for(sid, std::max<int64_t>(cap_total - off, 0), std::min(off, cap_total));
 			tm.start();
-			if (int rc = query_side(a, sid, !index_ready || attempt > 0)) return rc;
+			if (int rc = query_side(a, sid, !index_ready || attempt > 0 || dirty)) return rc;
 			tm.stop(c->seed_ms[0]);
 			tm.start();
 			HIP_TRY(launch_seed_stream(a, sid, st));
@@ -771,6 +945,7 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 		HIP_TRY(launch_seed_mask(a, sid, st, (int64_t)counts[sid]));
 		tm.stop(c->seed_ms[2]);
 	}
+	}
 	if (getenv("DMND_TRACE")) {
 		pristine = false;
 		HIP_TRY(hipMemsetAsync(c->counters.as<unsigned long long>() + S + 3, 0, sizeof(unsigned long long), st));
@@ -784,17 +959,29 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 	// phase 2: pair filter per shape; hit and deferred-pair buffers grow on overflow
 	int64_t hit_cap = seed_cap("DMND_SEED_HIT_CAP", std::max<int64_t>(std::max<int64_t>((int64_t)1 << 20, m_off[S] / 8), (int64_t)(c->seed_hits.cap / sizeof(dmnd_seed_hit))));
 	int64_t def_cap = seed_cap("DMND_SEED_DEFERRED_CAP", std::max<int64_t>((int64_t)1 << 18, (int64_t)(c->seed_deferred.cap / sizeof(SeedDeferred))));
-	for (int attempt = 0;; ++attempt) {
+	// the continuation of a chain: the hits (and deferred pairs) it left stay where they are, or the buffer that overflowed has grown
+	if (p2_keep) { hit_cap = kept_hit_cap; def_cap = kept_def_cap; }
+	hit_cap = std::max(hit_cap, grown_hit_cap); def_cap = std::max(def_cap, grown_def_cap);
+	for (int attempt = 0; !hits_done; ++attempt) {
+		const bool keep = attempt == 0 && p2_keep;
 		if (int rc = c->seed_hits.ensure((size_t)hit_cap * sizeof(dmnd_seed_hit))) return rc;
 		if (int rc = c->seed_deferred.ensure((size_t)def_cap * sizeof(SeedDeferred))) return rc;
-		if (!pristine) HIP_TRY(hipMemsetAsync(c->counters.as<unsigned long long>() + S, 0, sizeof(unsigned long long), st));
+		if (!pristine && !keep) HIP_TRY(hipMemsetAsync(c->counters.as<unsigned long long>() + S, 0, sizeof(unsigned long long), st));
 		if (attempt > 0) tm.discard(&c->seed_ms[3]);
 		bool def_overflow = false;
 		unsigned long long hits_seen = 0;                     // the hit counter as last read with a shape's deferred count; fresh: nothing appended since
 		bool hits_fresh = false;
-		c->seed_trace.assign((size_t)2 * S, 0);
+		if (!keep) c->seed_trace.assign((size_t)2 * S, 0);
 		unsigned long long def_max = 0;
-		for (int sid = 0; sid < S; ++sid) {
+		if (keep && deferred_sid >= 0) {
+			SeedArgs a = args_for(deferred_sid, (int64_t)counts[deferred_sid], m_off[deferred_sid]);
+			a.hits = c->seed_hits.as<dmnd_seed_hit>(); a.hit_cap = hit_cap;
+			a.deferred = c->seed_deferred.as<SeedDeferred>(); a.deferred_cap = def_cap;
+			tm.start();
+			if (int rc = seed_deferred_pass(c, a, deferred_sid, (int64_t)counts[deferred_sid], (int64_t)deferred_n, st)) return rc;
+			tm.stop(c->seed_ms[3]);
+		}
+		for (int sid = keep ? p2_first : 0; sid < S; ++sid) {
 			SeedArgs a = args_for(sid, (int64_t)counts[sid], m_off[sid]);
 			a.hits = c->seed_hits.as<dmnd_seed_hit>();
 			a.hit_cap = hit_cap;
@@ -870,7 +1057,7 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 	if (reuse) c->qindex_signature = signature;          // every shape's query side is complete and resident
 	// order the hits by (query, subject, seed_offset, score) on the device: what align_queries needs (hits grouped by query),
 	// made deterministic (the append order of the kernels is not)
-	if (c->n_seed_hits > 0) {
+	if (c->n_seed_hits > 0 && !hits_done) {
 		const int64_t n = c->n_seed_hits;
 		if (n > 0xffffffffLL) return fail(DMND_E_CAP, "dmnd_seed_search: more than 2^32 seed hits in one block pair");
 		if (int rc = c->seed_hits_sorted.ensure((size_t)n * sizeof(dmnd_seed_hit))) return rc;
@@ -907,9 +1094,10 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 		for (int sid = 0; sid < S && (size_t)sid < c->seed_trace.size(); ++sid) std::fprintf(stderr, " %llu", c->seed_trace[sid]);
 		std::fprintf(stderr, " | deferred:");
 		for (int sid = 0; sid < S && (size_t)(S + sid) < c->seed_trace.size(); ++sid) std::fprintf(stderr, " %llu", c->seed_trace[S + sid]);
-		std::fprintf(stderr, " | hits %lld | ms index %.2f stream %.2f mask %.2f pairs %.2f\n", (long long)c->n_seed_hits, c->seed_ms[0], c->seed_ms[1], c->seed_ms[2], c->seed_ms[3]);
+		std::fprintf(stderr, " | hits %lld | ms index %.2f stream %.2f mask %.2f pairs %.2f | path: %s\n", (long long)c->n_seed_hits, c->seed_ms[0], c->seed_ms[1], c->seed_ms[2], c->seed_ms[3], path);
 	}
 	*n_hits = c->n_seed_hits;
+	c->seed_last_hits = c->n_seed_hits;
 	return DMND_OK;
 }
 
@@ -918,6 +1106,11 @@ extern "C" int dmnd_seed_hits(dmnd_ctx* c, dmnd_seed_hit* out, int64_t cap)
 	if (!c || (!out && c->n_seed_hits > 0)) return fail(DMND_E_ARG, "dmnd_seed_hits: NULL argument");
 	if (cap < c->n_seed_hits) return fail(DMND_E_CAP, "dmnd_seed_hits: buffer too small");
 	if (c->n_seed_hits == 0) return DMND_OK;
+	// chain mode: the hits came back with the search's one copy where they fit its byte budget
+	if (c->seed_ret_hits == c->n_seed_hits && c->seed_ret_h.p) {
+		std::memcpy(out, c->seed_ret_h.as<char>() + c->seed_ret_bytes_header, (size_t)c->n_seed_hits * sizeof(dmnd_seed_hit));
+		return DMND_OK;
+	}
 	HIP_TRY(hipSetDevice(c->device));
 	if (int rc = download_bytes(c, out, c->seed_hits_sorted.p, (size_t)c->n_seed_hits * sizeof(dmnd_seed_hit))) return rc;      // sorted by dmnd_seed_search
 	return DMND_OK;

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include "../../include/diamond_hip.h"
 #include "seed_core.h"
+#include "seed_chain.h"
 
 namespace dmnd {
 
@@ -144,5 +145,24 @@ hipError_t sort_keys_u64(const uint64_t* in, uint64_t* out, int64_t n, void** tm
 // permutation (keys/idx: two buffers of n uint64 / uint32 each), then one gather into `out`.
 hipError_t sort_seed_hits(const dmnd_seed_hit* hits, dmnd_seed_hit* out, int64_t n, uint64_t* keys[2], uint32_t* idx[2],
 	void** tmp, size_t* tmp_bytes, hipStream_t st, int query_bits, int subject_bits, int off_bits, bool equal_scores = false);      // bits of the largest query id / subject position / seed offset; equal_scores: every hit carries the same score (no ungapped filter: --fast), the pass over the scores is left out
+
+// ---- chain mode (seed_chain.h): the launches of the non-fused search whose sizes the host does not know. Every SeedArgs here
+// addresses the WHOLE shared joined-position lists (matched_cap = their capacity); shape sid owns [ctr[sid - 1], ctr[sid]).
+struct SeedChain {
+	unsigned long long* ctr;      // the counter block (layout: seed_chain.h)
+	int S;
+	int64_t matched_cap, survivor_cap, hit_cap, tiled_from;      // capacities of matched_*, seed_survivors (= seed_scored), seed_hits; joined positions of a shape from which on its pair filter is the host's
+};
+// behind the stream kernel of shape sid: overflow flag, start of the next shape's range; behind the last one the gate of shape 0
+hipError_t launch_seed_chain_streamed(const SeedChain& ch, int sid, hipStream_t st);
+hipError_t launch_seed_chain_mask(const SeedArgs& a, const SeedChain& ch, int sid, hipStream_t st);
+// pair filter, scoring and left-most rule of shape sid, then its flags and the gate of the next shape
+hipError_t launch_seed_chain_shape(const SeedArgs& a, const SeedChain& ch, int sid, hipStream_t st);
+inline bool sort_seed_hits_one_key(int query_bits, int subject_bits, int off_bits) { return off_bits >= 1 && off_bits <= 24 && query_bits + subject_bits + off_bits <= 64; }
+// sort_seed_hits for a hit count that lies in ch.ctr[S]: the rocPRIM sorts run over sort_cap entries padded with keys that sort
+// last (needs sort_seed_hits_one_key; sorted = false leaves the sort out). Then `ret` receives the counter block
+// (chain_ret_header_bytes) and behind it the first ret_hits sorted hits.
+hipError_t launch_seed_chain_sort(const SeedChain& ch, bool sorted, const dmnd_seed_hit* hits, dmnd_seed_hit* out, int64_t sort_cap, uint64_t* keys[2], uint32_t* idx[2],
+	void** tmp, size_t* tmp_bytes, hipStream_t st, int query_bits, int subject_bits, int off_bits, bool equal_scores, char* ret, int64_t ret_hits);
 
 }  // namespace dmnd

@@ -806,21 +806,30 @@ __global__ void seed_mask_kernel(SeedArgs a, int sid)
 // The same, driven by the list of joined reference positions instead of a scan over all table slots: with long seeds a block
 // pair joins a few 10^4 positions against 8 M slots. Every joined position of a seed finds the same slot; the first one to set
 // ERASED masks the seed's query positions.
-__global__ void seed_mask_joined_kernel(SeedArgs a, int sid, int64_t n_matched)
+// CHAIN (seed_chain.h): the shape's range of the shared lists comes from the counter block, walked by a bounded grid
+template<bool CHAIN>
+__global__ void seed_mask_joined_kernel(SeedArgs a, int sid, int64_t n_matched, SeedChain ch)
 {
-	const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (m >= n_matched) return;
-	const uint32_t slot = a.matched_slot[m];
-	const SeedSlot sl = a.slot(slot);
-	if (sl.flags & SLOT_ERASED) return;
-	const uint32_t count = sl.flags >> 8;
-	if (seed_is_complex(a.params, sid, a.qdata + a.q_begin + (count == 1 ? sl.head : a.qlist[sl.head]))) return;
-	if (atomicOr(&a.slot(slot).flags, (uint32_t)SLOT_ERASED) & SLOT_ERASED) return;
-	const int t = sid * a.params.index_chunks + seed_chunk(a.params, seed_of_key(a.params, sid, sl.key));
-	for (uint32_t i = 0; i < count; ++i) {
-		const uint32_t x = count == 1 ? sl.head : a.qlist[sl.head + i];
-		const uint8_t old = a.mask_time[a.q_begin + x];
-		if (t < old) a.mask_time[a.q_begin + x] = (uint8_t)t;
+	int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, end = n_matched;
+	if (CHAIN) {
+		if (ch.ctr[chain_ctr_status(ch.S)] & CHAIN_MATCHED_OVER) return;      // incomplete lists: phase 1 runs again
+		m += sid ? (int64_t)ch.ctr[sid - 1] : 0;
+		end = (int64_t)ch.ctr[sid];
+	}
+	for (; m < end; m += (int64_t)gridDim.x * blockDim.x) {
+		const uint32_t slot = a.matched_slot[m];
+		const SeedSlot sl = a.slot(slot);
+		if (sl.flags & SLOT_ERASED) continue;
+		const uint32_t count = sl.flags >> 8;
+		if (seed_is_complex(a.params, sid, a.qdata + a.q_begin + (count == 1 ? sl.head : a.qlist[sl.head]))) continue;
+		if (atomicOr(&a.slot(slot).flags, (uint32_t)SLOT_ERASED) & SLOT_ERASED) continue;
+		const int t = sid * a.params.index_chunks + seed_chunk(a.params, seed_of_key(a.params, sid, sl.key));
+		for (uint32_t i = 0; i < count; ++i) {
+			const uint32_t x = count == 1 ? sl.head : a.qlist[sl.head + i];
+			const uint8_t old = a.mask_time[a.q_begin + x];
+			if (t < old) a.mask_time[a.q_begin + x] = (uint8_t)t;
+		}
+		if (!CHAIN) return;                               // (the host-sized grid covers the list)
 	}
 }
 
@@ -912,15 +921,22 @@ __device__ __forceinline__ void filter_pair(const SeedArgs& a, int sid, uint32_t
 // runs a 10^4-iteration loop while the rest of the machine idles.
 // The pairs that pass go to the survivor list (LDS-staged, one atomic per workgroup) for launch_seed_post -- scoring them in
 // place left most lanes of a wavefront waiting for the few that passed.
-__global__ __launch_bounds__(128) void seed_pair_kernel(SeedArgs a, int sid, int64_t n_matched)
+// CHAIN (seed_chain.h): the shape's range of the shared lists comes from the counter block; a bounded grid walks it in tiles of
+// one workgroup (a workgroup-uniform trip count: the staging area is flushed per tile)
+template<bool CHAIN>
+__global__ __launch_bounds__(128) void seed_pair_kernel(SeedArgs a, int sid, int64_t n_matched, SeedChain ch)
 {
 	constexpr uint32_t LIGHT = 8;
 	constexpr unsigned STAGE = 1024;
 	__shared__ SeedSurvivor stage[STAGE];
 	__shared__ unsigned st_n;
 	__shared__ unsigned long long st_base;
-	if (threadIdx.x == 0) st_n = 0;
-	__syncthreads();
+	int64_t first = 0, end = n_matched;
+	if (CHAIN) {
+		if (ch.ctr[chain_ctr_status(ch.S)]) return;       // (written by the one-thread kernels between the shapes only)
+		first = sid ? (int64_t)ch.ctr[sid - 1] : 0;
+		end = (int64_t)ch.ctr[sid];
+	}
 	auto filter = [&](uint32_t slot, int64_t sloc, uint32_t x) {
 		if (fingerprint_id(a.qdata + a.q_begin + x, a.tdata + sloc) < a.params.hamming_filter_id) return;
 		const unsigned k = atomicAdd(&st_n, 1u);
@@ -931,35 +947,42 @@ __global__ __launch_bounds__(128) void seed_pair_kernel(SeedArgs a, int sid, int
 		}
 	};
 	const int lane = threadIdx.x & 63;
-	const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-	uint32_t slot = 0, head = 0, count = 0;
-	int64_t sloc = 0;
-	if (m < n_matched) {
-		slot = a.matched_slot[m];
-		const SeedSlot sl = a.slot(slot);                // key, list start, size and state of the seed in one 16-byte read
-		if (!(sl.flags & SLOT_ERASED)) {
-			head = sl.head; count = sl.flags >> 8;
-			sloc = a.matched_loc[m];
+	for (int64_t tile = first + (int64_t)blockIdx.x * blockDim.x; tile < end; tile += (int64_t)gridDim.x * blockDim.x) {
+		if (threadIdx.x == 0) st_n = 0;
+		__syncthreads();
+		const int64_t m = tile + threadIdx.x;
+		uint32_t slot = 0, head = 0, count = 0;
+		int64_t sloc = 0;
+		if (m < end) {
+			slot = a.matched_slot[m];
+			const SeedSlot sl = a.slot(slot);                // key, list start, size and state of the seed in one 16-byte read
+			if (!(sl.flags & SLOT_ERASED)) {
+				head = sl.head; count = sl.flags >> 8;
+				sloc = a.matched_loc[m];
+			}
 		}
-	}
-	if (count <= LIGHT)
-		for (uint32_t i = 0; i < count; ++i) filter(slot, sloc, count == 1 ? head : a.qlist[head + i]);
-	unsigned long long heavy = __ballot(count > LIGHT);
-	while (heavy) {
-		const int src = __builtin_ctzll(heavy);
-		heavy &= heavy - 1;
-		const uint32_t h_slot = (uint32_t)__shfl((int)slot, src), h_head = (uint32_t)__shfl((int)head, src), h_count = (uint32_t)__shfl((int)count, src);
-		const int64_t h_sloc = (int64_t)__shfl((long long)sloc, src);
-		for (uint32_t i = (uint32_t)lane; i < h_count; i += 64) filter(h_slot, h_sloc, a.qlist[h_head + i]);
-	}
-	__syncthreads();
-	const unsigned n = st_n < STAGE ? st_n : STAGE;
-	if (n == 0) return;
-	if (threadIdx.x == 0) st_base = atomicAdd(a.survivor_count, (unsigned long long)n);
-	__syncthreads();
-	for (unsigned k = threadIdx.x; k < n; k += blockDim.x) {
-		const unsigned long long idx = st_base + k;
-		if (idx < (unsigned long long)a.survivor_cap) a.survivors[idx] = stage[k];
+		if (count <= LIGHT)
+			for (uint32_t i = 0; i < count; ++i) filter(slot, sloc, count == 1 ? head : a.qlist[head + i]);
+		unsigned long long heavy = __ballot(count > LIGHT);
+		while (heavy) {
+			const int src = __builtin_ctzll(heavy);
+			heavy &= heavy - 1;
+			const uint32_t h_slot = (uint32_t)__shfl((int)slot, src), h_head = (uint32_t)__shfl((int)head, src), h_count = (uint32_t)__shfl((int)count, src);
+			const int64_t h_sloc = (int64_t)__shfl((long long)sloc, src);
+			for (uint32_t i = (uint32_t)lane; i < h_count; i += 64) filter(h_slot, h_sloc, a.qlist[h_head + i]);
+		}
+		__syncthreads();
+		const unsigned n = st_n < STAGE ? st_n : STAGE;
+		if (n != 0) {
+			if (threadIdx.x == 0) st_base = atomicAdd(a.survivor_count, (unsigned long long)n);
+			__syncthreads();
+			for (unsigned k = threadIdx.x; k < n; k += blockDim.x) {
+				const unsigned long long idx = st_base + k;
+				if (idx < (unsigned long long)a.survivor_cap) a.survivors[idx] = stage[k];
+			}
+		}
+		if (!CHAIN) return;                               // (the host-sized grid covers the list)
+		__syncthreads();
 	}
 }
 
@@ -1114,48 +1137,60 @@ __device__ __forceinline__ int stage2_score_regs(const SeedArgs& a, const int8_t
 	return score <= cutoff ? -1 : score;
 }
 
-__global__ __launch_bounds__(POST_THREADS) void seed_score_kernel(SeedArgs a, int sid, int64_t n_survivors)
+// CHAIN (seed_chain.h): the survivor count comes from the counter block; a bounded grid walks the list in tiles of one workgroup
+template<bool CHAIN>
+__global__ __launch_bounds__(POST_THREADS) void seed_score_kernel(SeedArgs a, int sid, int64_t n_survivors, SeedChain ch)
 {
 	constexpr unsigned STAGE = POST_THREADS;
 	__shared__ int8_t matrix[32 * 32];
 	__shared__ SeedScored stage[STAGE];
 	__shared__ unsigned st_n;
 	__shared__ unsigned long long st_base;
-	for (int i = threadIdx.x; i < 1024; i += blockDim.x) matrix[i] = a.matrix[i];
-	if (threadIdx.x == 0) st_n = 0;
-	__syncthreads();
-	const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-	// (the kernel argument is not modified: a private copy of the 3 KB struct would live in scratch memory)
-	if (i < n_survivors) {
-		const SeedSurvivor sv = a.survivors[i];
-		const SeedSlot sl = a.slot(sv.slot);
-		if (!(sl.flags & SLOT_ERASED)) {                  // (the fused stream kernel never lets a pair of a non-complex seed through)
-			const int64_t qp = a.q_begin + sv.x;
-			int score;
-			// windows wider than the staged stretch (--ungapped-window above 48; short translated frames use their whole length): from the blocks
-			if (a.params.query_translated || a.params.ungapped_window > POST_BEFORE) score = stage2_score(a, matrix, sv.slot, sv.sloc, sv.x, a.qdata + qp, a.tdata + sv.sloc);
-			else {
-				uint32_t qw[24], sw[24];
-#pragma unroll
-				for (int k = 0; k < POST_LETTERS / 16; ++k) {
-					uint4 v, w;
-					__builtin_memcpy(&v, a.qdata + qp - POST_BEFORE + 16 * k, 16);
-					__builtin_memcpy(&w, a.tdata + sv.sloc - POST_BEFORE + 16 * k, 16);
-					qw[4 * k] = v.x; qw[4 * k + 1] = v.y; qw[4 * k + 2] = v.z; qw[4 * k + 3] = v.w;
-					sw[4 * k] = w.x; sw[4 * k + 1] = w.y; sw[4 * k + 2] = w.z; sw[4 * k + 3] = w.w;
-				}
-				score = stage2_score_regs(a, matrix, sv.slot, sv.sloc, sv.x, qw, sw);
-			}
-			if (score >= 0)
-				stage[atomicAdd(&st_n, 1u)] = SeedScored{ sv.slot, sv.x, sv.sloc, score, seed_chunk(a.params, seed_of_key(a.params, sid, sl.key)) };
-		}
+	if (CHAIN) {
+		if (ch.ctr[chain_ctr_status(ch.S)]) return;
+		n_survivors = (int64_t)*a.survivor_count;
+		if (n_survivors > a.survivor_cap) return;          // an incomplete list: the host runs the shape's pair filter again
 	}
-	__syncthreads();
-	const unsigned n = st_n;
-	if (n == 0) return;
-	if (threadIdx.x == 0) st_base = atomicAdd(a.scored_count, (unsigned long long)n);
-	__syncthreads();
-	if (threadIdx.x < n) a.scored[st_base + threadIdx.x] = stage[threadIdx.x];
+	for (int i = threadIdx.x; i < 1024; i += blockDim.x) matrix[i] = a.matrix[i];
+	for (int64_t tile = (int64_t)blockIdx.x * blockDim.x; tile < n_survivors; tile += (int64_t)gridDim.x * blockDim.x) {
+		if (threadIdx.x == 0) st_n = 0;
+		__syncthreads();
+		const int64_t i = tile + threadIdx.x;
+		// (the kernel argument is not modified: a private copy of the 3 KB struct would live in scratch memory)
+		if (i < n_survivors) {
+			const SeedSurvivor sv = a.survivors[i];
+			const SeedSlot sl = a.slot(sv.slot);
+			if (!(sl.flags & SLOT_ERASED)) {                  // (the fused stream kernel never lets a pair of a non-complex seed through)
+				const int64_t qp = a.q_begin + sv.x;
+				int score;
+				// windows wider than the staged stretch (--ungapped-window above 48; short translated frames use their whole length): from the blocks
+				if (a.params.query_translated || a.params.ungapped_window > POST_BEFORE) score = stage2_score(a, matrix, sv.slot, sv.sloc, sv.x, a.qdata + qp, a.tdata + sv.sloc);
+				else {
+					uint32_t qw[24], sw[24];
+#pragma unroll
+					for (int k = 0; k < POST_LETTERS / 16; ++k) {
+						uint4 v, w;
+						__builtin_memcpy(&v, a.qdata + qp - POST_BEFORE + 16 * k, 16);
+						__builtin_memcpy(&w, a.tdata + sv.sloc - POST_BEFORE + 16 * k, 16);
+						qw[4 * k] = v.x; qw[4 * k + 1] = v.y; qw[4 * k + 2] = v.z; qw[4 * k + 3] = v.w;
+						sw[4 * k] = w.x; sw[4 * k + 1] = w.y; sw[4 * k + 2] = w.z; sw[4 * k + 3] = w.w;
+					}
+					score = stage2_score_regs(a, matrix, sv.slot, sv.sloc, sv.x, qw, sw);
+				}
+				if (score >= 0)
+					stage[atomicAdd(&st_n, 1u)] = SeedScored{ sv.slot, sv.x, sv.sloc, score, seed_chunk(a.params, seed_of_key(a.params, sid, sl.key)) };
+			}
+		}
+		__syncthreads();
+		const unsigned n = st_n;
+		if (n != 0) {
+			if (threadIdx.x == 0) st_base = atomicAdd(a.scored_count, (unsigned long long)n);
+			__syncthreads();
+			if (threadIdx.x < n) a.scored[st_base + threadIdx.x] = stage[threadIdx.x];
+		}
+		if (!CHAIN) return;                               // (the host-sized grid covers the list)
+		__syncthreads();
+	}
 }
 
 // The left-most rule's windows with wide loads (LmBytewise's counterpart, seed_core.h). The byte-wise form walks up to 96 + 49 + 49
@@ -1727,7 +1762,7 @@ hipError_t launch_seed_mask(const SeedArgs& a, int sid, hipStream_t st, int64_t 
 {
 	if (!a.fused && n_matched >= 0 && n_matched * 4 < (int64_t)a.slot_mask) {
 		if (n_matched == 0) return hipSuccess;
-		hipLaunchKernelGGL(seed_mask_joined_kernel, dim3(blocks_for(n_matched, 256)), dim3(256), 0, st, a, sid, n_matched);
+		hipLaunchKernelGGL(seed_mask_joined_kernel<false>, dim3(blocks_for(n_matched, 256)), dim3(256), 0, st, a, sid, n_matched, SeedChain{});
 		return hipGetLastError();
 	}
 	hipLaunchKernelGGL(seed_mask_kernel, dim3(blocks_for((int64_t)a.slot_mask + 1, 256)), dim3(256), 0, st, a, sid);
@@ -1737,7 +1772,7 @@ hipError_t launch_seed_mask(const SeedArgs& a, int sid, hipStream_t st, int64_t 
 hipError_t launch_seed_pairs(const SeedArgs& a, int sid, int64_t n_matched, hipStream_t st)
 {
 	if (n_matched == 0) return hipSuccess;
-	hipLaunchKernelGGL(seed_pair_kernel, dim3(blocks_for(n_matched, 128)), dim3(128), 0, st, a, sid, n_matched);
+	hipLaunchKernelGGL(seed_pair_kernel<false>, dim3(blocks_for(n_matched, 128)), dim3(128), 0, st, a, sid, n_matched, SeedChain{});
 	return hipGetLastError();
 }
 
@@ -1762,7 +1797,7 @@ hipError_t launch_seed_post(const SeedArgs& a, int sid, int64_t n_survivors, hip
 		const hipError_t e = hipMemsetAsync(a.scored_count, 0, sizeof(unsigned long long), st);
 		if (e != hipSuccess) return e;
 	}
-	hipLaunchKernelGGL(seed_score_kernel, dim3(blocks_for(n_survivors, POST_THREADS)), dim3(POST_THREADS), 0, st, a, sid, n_survivors);
+	hipLaunchKernelGGL(seed_score_kernel<false>, dim3(blocks_for(n_survivors, POST_THREADS)), dim3(POST_THREADS), 0, st, a, sid, n_survivors, SeedChain{});
 	// 4-bit class map of the letters (as launch_seed_stream builds it); reductions with more than 15 classes keep the byte-wise windows
 	uint64_t lo = 0, hi = 0;
 	const SeedParams& c = a.params;
@@ -1894,6 +1929,147 @@ hipError_t sort_seed_hits(const dmnd_seed_hit* hits, dmnd_seed_hit* out, int64_t
 	hipLaunchKernelGGL(hit_keys_kernel, grid, block, 0, st, hits, (const uint32_t*)idx[0], n, 2, keys[0], (uint32_t*)nullptr, 0, 0);
 	if ((e = sort_pairs(keys[0], keys[1], idx[0], idx[1], n, 32, tmp, tmp_bytes, st)) != hipSuccess) return e;
 	hipLaunchKernelGGL(hit_gather_kernel, grid, block, 0, st, hits, (const uint32_t*)idx[1], n, out);
+	return hipGetLastError();
+}
+
+// ---- chain mode (seed_chain.h) -------------------------------------------------------------------------------------------
+namespace {
+
+// the gate of shape s's pair filter: a shape that reached the tiled-filter threshold is the host's
+__device__ void chain_gate(const SeedChain& ch, int s)
+{
+	const unsigned long long n = ch.ctr[s] - (s ? ch.ctr[s - 1] : 0ull);
+	if ((long long)n >= ch.tiled_from) ch.ctr[chain_ctr_status(ch.S)] |= CHAIN_TILED;
+}
+
+// One thread, between two kernels of the chain: what the host decided there when it read the counters.
+// Behind the stream kernel of shape sid: ctr[sid] is the end of the shape's range of the shared lists and the start of the next one's.
+__global__ void seed_chain_streamed_kernel(SeedChain ch, int sid)
+{
+	if (blockIdx.x != 0 || threadIdx.x != 0) return;
+	const unsigned long long end = ch.ctr[sid];
+	if ((long long)end > ch.matched_cap) ch.ctr[chain_ctr_status(ch.S)] |= CHAIN_MATCHED_OVER;
+	if (sid + 1 < ch.S) { ch.ctr[sid + 1] = end; return; }      // (the stream kernels append with atomics on ctr[sid])
+	if (!ch.ctr[chain_ctr_status(ch.S)]) chain_gate(ch, 0);
+}
+
+// Behind the left-most rule of shape sid
+__global__ void seed_chain_shape_done_kernel(SeedChain ch, int sid)
+{
+	if (blockIdx.x != 0 || threadIdx.x != 0) return;
+	unsigned long long& status = ch.ctr[chain_ctr_status(ch.S)];
+	// the left-most kernel has consumed the scored list: behind a flag the scoring of the following shapes does nothing, and their
+	// left-most kernels must not find this shape's list again
+	ch.ctr[ch.S + 4] = 0;
+	if (status) return;
+	const unsigned long long ns = ch.ctr[ch.S + 3];
+	ch.ctr[chain_ctr_survivors_of(ch.S) + sid] = ns;
+	if ((long long)ns > ch.survivor_cap) { status |= CHAIN_SURVIVORS_OVER; return; }
+	if ((long long)ch.ctr[ch.S] > ch.hit_cap) { status |= CHAIN_HITS_OVER; return; }
+	if (ch.ctr[ch.S + 1] != 0) { status |= CHAIN_DEFERRED; return; }      // (deferred pairs over their capacity: the host sees the count)
+	ch.ctr[chain_ctr_done(ch.S)] = (unsigned long long)(sid + 1);
+	if (sid + 1 < ch.S) {
+		ch.ctr[ch.S + 3] = 0; ch.ctr[ch.S + 4] = 0;        // the next shape's survivors and scored survivors
+		chain_gate(ch, sid + 1);
+	}
+}
+
+// hit_keys_kernel over a fixed capacity: entries from the hit count (device memory) on carry a key of all ones, which sorts last
+// -- behind every real key even where the fields of one are all ones, since the radix sorts are stable and the padding starts behind the hits.
+// (pass 0: scores; pass 3: query | subject | seed_offset)
+__global__ void hit_keys_chain_kernel(const dmnd_seed_hit* hits, const uint32_t* perm, int64_t cap, int pass, uint64_t* keys, uint32_t* idx_out, int subject_bits, int off_bits, SeedChain ch)
+{
+	const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= cap) return;
+	int64_t n = (int64_t)ch.ctr[ch.S];
+	if (n > cap || (ch.ctr[chain_ctr_status(ch.S)] & ~(unsigned long long)CHAIN_SORT_OVER)) n = 0;      // nothing to sort here: the host continues
+	const uint32_t src = perm ? perm[i] : (uint32_t)i;
+	uint64_t key = ~(uint64_t)0;
+	if ((int64_t)src < n) {
+		const dmnd_seed_hit h = hits[src];
+		key = pass == 0 ? (uint64_t)(uint32_t)h.score : ((((uint64_t)h.query << subject_bits) | (uint64_t)h.subject) << off_bits) | ((uint64_t)h.seed_offset & 0xffffffu);
+	}
+	keys[i] = key;
+	if (idx_out) idx_out[i] = src;
+}
+
+// the sorted hits, and the readback: the counter block, then the leading sorted hits
+__global__ void hit_gather_chain_kernel(const dmnd_seed_hit* hits, const uint32_t* perm, int64_t cap, dmnd_seed_hit* out, SeedChain ch, unsigned long long* ret, int ret_words, dmnd_seed_hit* ret_hits, int64_t n_ret_hits)
+{
+	const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	const unsigned long long status = ch.ctr[chain_ctr_status(ch.S)];
+	int64_t n = (int64_t)ch.ctr[ch.S];
+	const bool over = n > cap;
+	if (i < ret_words) ret[i] = i == chain_ctr_status(ch.S) && !status && (over || !perm) ? (unsigned long long)CHAIN_SORT_OVER : ch.ctr[i];
+	if (over || status || !perm) return;
+	if (i < n) {
+		const dmnd_seed_hit h = hits[perm[i]];
+		out[i] = h;
+		if (i < n_ret_hits) ret_hits[i] = h;
+	}
+}
+
+}  // namespace
+
+hipError_t launch_seed_chain_streamed(const SeedChain& ch, int sid, hipStream_t st)
+{
+	hipLaunchKernelGGL(seed_chain_streamed_kernel, dim3(1), dim3(64), 0, st, ch, sid);
+	return hipGetLastError();
+}
+
+// Grids of the chain's kernels: the host does not know the list sizes, every workgroup reads them and leaves, or strides over the
+// list -- eight workgroups per CU cover the 10^4 - 10^5 entries of a long-seed block pair in one pass
+enum { CHAIN_GRID = 256 * 8 };
+
+hipError_t launch_seed_chain_mask(const SeedArgs& a, const SeedChain& ch, int sid, hipStream_t st)
+{
+	hipLaunchKernelGGL(seed_mask_joined_kernel<true>, dim3(CHAIN_GRID / 2), dim3(256), 0, st, a, sid, (int64_t)0, ch);
+	return hipGetLastError();
+}
+
+hipError_t launch_seed_chain_shape(const SeedArgs& a, const SeedChain& ch, int sid, hipStream_t st)
+{
+	hipLaunchKernelGGL(seed_pair_kernel<true>, dim3(CHAIN_GRID), dim3(128), 0, st, a, sid, (int64_t)0, ch);
+	hipLaunchKernelGGL(seed_score_kernel<true>, dim3(CHAIN_GRID / 2), dim3(POST_THREADS), 0, st, a, sid, (int64_t)0, ch);
+	// (a voided shape leaves the scored count zero: the left-most kernel reads it and leaves)
+	uint64_t lo = 0, hi = 0;
+	const SeedParams& c = a.params;
+	for (int l = 0; l < 32; ++l) {
+		const uint64_t code = c.reduction[l] == L_MASK ? 15u : (uint64_t)(c.reduction[l] & 15);
+		(l < 16 ? lo : hi) |= code << ((l & 15) * 4);
+	}
+	hipLaunchKernelGGL(seed_leftmost_kernel, dim3(CHAIN_GRID / 2), dim3(256), 0, st, a, sid, lo, hi, c.reduction_size <= 15 ? 1 : 0);
+	hipLaunchKernelGGL(seed_chain_shape_done_kernel, dim3(1), dim3(64), 0, st, ch, sid);
+	return hipGetLastError();
+}
+
+hipError_t launch_seed_chain_sort(const SeedChain& ch, bool sorted, const dmnd_seed_hit* hits, dmnd_seed_hit* out, int64_t sort_cap, uint64_t* keys[2], uint32_t* idx[2],
+	void** tmp, size_t* tmp_bytes, hipStream_t st, int query_bits, int subject_bits, int off_bits, bool equal_scores, char* ret, int64_t ret_hits)
+{
+	const dim3 grid(blocks_for(std::max<int64_t>(sort_cap, chain_ctr_words(ch.S)), 256)), block(256);
+	unsigned long long* ret_ctr = reinterpret_cast<unsigned long long*>(ret);
+	dmnd_seed_hit* ret_h = reinterpret_cast<dmnd_seed_hit*>(ret + chain_ret_header_bytes(ch.S));
+	if (!sorted || !sort_seed_hits_one_key(query_bits, subject_bits, off_bits)) {
+		hipLaunchKernelGGL(hit_gather_chain_kernel, dim3(1), block, 0, st, hits, (const uint32_t*)nullptr, sort_cap, out, ch, ret_ctr, chain_ctr_words(ch.S), ret_h, ret_hits);
+		return hipGetLastError();
+	}
+	hipError_t e;
+	const int bits = query_bits + subject_bits + off_bits;
+	const uint32_t* perm;
+	if (equal_scores) {
+		hipLaunchKernelGGL(hit_keys_chain_kernel, grid, block, 0, st, hits, (const uint32_t*)nullptr, sort_cap, 3, keys[0], idx[1], subject_bits, off_bits, ch);
+		if ((e = sort_pairs(keys[0], keys[1], idx[1], idx[0], sort_cap, bits, tmp, tmp_bytes, st)) != hipSuccess) return e;
+		perm = idx[0];
+	}
+	else {
+		// least significant criterion first; every pass is stable
+		hipLaunchKernelGGL(hit_keys_chain_kernel, grid, block, 0, st, hits, (const uint32_t*)nullptr, sort_cap, 0, keys[0], idx[0], 0, 0, ch);
+		if ((e = sort_pairs(keys[0], keys[1], idx[0], idx[1], sort_cap, 32, tmp, tmp_bytes, st)) != hipSuccess) return e;
+		hipLaunchKernelGGL(hit_keys_chain_kernel, grid, block, 0, st, hits, (const uint32_t*)idx[1], sort_cap, 3, keys[0], (uint32_t*)nullptr, subject_bits, off_bits, ch);
+		if ((e = sort_pairs(keys[0], keys[1], idx[1], idx[0], sort_cap, bits, tmp, tmp_bytes, st)) != hipSuccess) return e;
+		perm = idx[0];
+	}
+	hipLaunchKernelGGL(hit_gather_chain_kernel, grid, block, 0, st, hits, perm, sort_cap, out, ch, ret_ctr, chain_ctr_words(ch.S), ret_h, ret_hits);
 	return hipGetLastError();
 }
 

@@ -29,6 +29,10 @@ struct Tuning {
 	bool no_stream_priority = false;   // DMND_NO_STREAM_PRIORITY: every stream at the default priority
 	// ---- seed stage geometry (seed_api.hip seed_sizes; 0 = the size-dependent default chosen there)
 	int seed_slots_x8 = 0;             // DMND_SEED_SLOTS_X8: table slots per query position x 8 (8 .. 64; default 32 fused / 16)
+	// ---- chain mode of the long-seed search (seed_chain.h)
+	// (values only: the environment variables of these two are the tests' per-call hooks, read in ONE place, seed_api.hip chain_sort_cap / chain_readback_bytes)
+	int seed_readback_bytes = 1 << 20; // DMND_SEED_READBACK_BYTES: most bytes of sorted hits that come back with the chain's one copy
+	int seed_sort_cap = 1 << 16;       // DMND_SEED_SORT_CAP: entries of the padded sort whose size only the device knows (C2: 2e4 hits per step)
 };
 
 inline const Tuning& tuning()

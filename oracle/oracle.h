@@ -64,7 +64,13 @@ int oracle_gapped_filter_target(const int8_t* matrix8, const int8_t* query, int 
 void oracle_cutoff_table2d(const oracle_evaluer* e, double evalue, int32_t* table);
 
 /* tantan repeat masking (tantan.c) */
+/* "oracle-sources-digest:" + the SHA-1 of the sources the library was compiled from (sources_digest.c) */
+const char* oracle_sources_digest(void);
+
 int oracle_tantan_mask(int8_t* seq, int len, const float* lr, float p_repeat, float p_repeat_end, float repeat_growth, float p_mask);
+/* the same with one deliberately wrong rounding (variant 1 - 3, see tantan.c; 0 = oracle_tantan_mask; pf_out, optional: the repeat probability per position): for finding and checking
+ * the threshold cases of tests/golden/tantan_threshold.txt only */
+int oracle_tantan_mask_wrong(int8_t* seq, int len, const float* lr, float p_repeat, float p_repeat_end, float repeat_growth, float p_mask, int variant, float* pf_out);
 double oracle_tantan_lambda(const int8_t* matrix8);
 void oracle_tantan_matrix(const int8_t* matrix8, float* lr);
 

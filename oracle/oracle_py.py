@@ -32,12 +32,31 @@ class Evaluer(ctypes.Structure):
 _lib = None
 
 
+def _sources_digest():
+    """SHA-1 of oracle/*.c and oracle/*.h in name order, as oracle/Makefile compiles it into the library"""
+    import hashlib
+    h = hashlib.sha1()
+    for f in sorted(f for f in os.listdir(_HERE) if f.endswith((".c", ".h"))):
+        with open(os.path.join(_HERE, f), "rb") as src:
+            h.update(src.read())
+    return h.hexdigest()
+
+
+def _built_from_these_sources():
+    if not os.path.exists(_SO):
+        return False
+    with open(_SO, "rb") as f:
+        return b"oracle-sources-digest:" + _sources_digest().encode() in f.read()
+
+
 def lib():
     global _lib
     if _lib is None:
-        srcs = [os.path.join(_HERE, f) for f in os.listdir(_HERE) if f.endswith((".c", ".h"))]
-        if not os.path.exists(_SO) or any(os.path.getmtime(s) > os.path.getmtime(_SO) for s in srcs):
-            subprocess.check_call(["make", "-s", "-C", _HERE, "restatement"])
+        # by content, not by time stamp: a library carried over from another checkout is newer than the sources it does not match
+        if not _built_from_these_sources():
+            subprocess.check_call(["make", "-s", "-B", "-C", _HERE, "restatement"])
+            if not _built_from_these_sources():
+                raise RuntimeError("oracle/_ref/libswipe_oracle.so is not built from the sources in oracle/")
         _lib = ctypes.CDLL(_SO)
         _lib.oracle_evalue.restype = ctypes.c_double
         _lib.oracle_bitscore.restype = ctypes.c_double
@@ -232,6 +251,19 @@ def tantan_mask(seq, lr, p_repeat=0.005, p_repeat_end=0.05, repeat_growth=1.0 / 
     f = ctypes.c_float
     n = lib().oracle_tantan_mask(s.ctypes.data_as(ctypes.c_void_p), len(s), m.ctypes.data_as(ctypes.c_void_p),
                                  f(p_repeat), f(p_repeat_end), f(repeat_growth), f(p_mask))
+    return s, n
+
+
+def tantan_mask_wrong(seq, lr, variant, p_repeat=0.005, p_repeat_end=0.05, repeat_growth=1.0 / 0.9, p_mask=0.9, probabilities=None):
+    """tantan_mask with one deliberately wrong rounding (oracle/tantan.c: 1 = forward sum, 2 = backward sum take offsets 48 and 49
+    first, 3 = fused multiply-add in the forward cell; 0 = the reference's arithmetic). probabilities: a float32 array of the
+    sequence's length that receives the repeat probability of every position."""
+    s = np.ascontiguousarray(seq, np.int8).copy()
+    m = np.ascontiguousarray(lr, np.float32)
+    f = ctypes.c_float
+    n = lib().oracle_tantan_mask_wrong(s.ctypes.data_as(ctypes.c_void_p), len(s), m.ctypes.data_as(ctypes.c_void_p),
+                                       f(p_repeat), f(p_repeat_end), f(repeat_growth), f(p_mask), int(variant),
+                                       probabilities.ctypes.data_as(ctypes.c_void_p) if probabilities is not None else None)
     return s, n
 
 

@@ -36,8 +36,14 @@ static float sum50(const float* x)            /* SIMD::sum(f, 50) */
 }
 
 /* lr: 32x32 floats, lr[a*32+b] = likelihood ratio of letters a, b. Returns the number of masked letters; seq is hard-masked
- * in place (letter 23) where the repeat probability >= p_mask (mask_mode 1 of the reference). */
-int oracle_tantan_mask(int8_t* seq, int len, const float* lr, float p_repeat, float p_repeat_end, float repeat_growth, float p_mask)
+ * in place (letter 23) where the repeat probability >= p_mask (mask_mode 1 of the reference).
+ * variant 0 is the reference's arithmetic. The others are deliberately WRONG in one rounding each, the mistakes a kernel can make
+ * without changing the mathematics: 1 = the forward sum takes offsets 48 and 49 before the six groups, 2 = the backward sum does,
+ * 3 = the forward cell's f * f2f + b * d is one fused multiply-add. They exist so that tests/golden/tantan_threshold.txt can hold
+ * sequences on which each of them changes a mask (tests/golden/make_tantan_threshold.py finds them, tests/test_tantan_corpus.py
+ * asserts that they still do): a repeat probability within an ulp or two of p_mask is what makes a test of masks notice them.
+ * pf_out (optional): the repeat probability of every position. */
+static int tantan_mask_variant(int8_t* seq, int len, const float* lr, float p_repeat, float p_repeat_end, float repeat_growth, float p_mask, int variant, float* pf_out)
 {
 	if (len <= 0) return 0;
 	float f[WINDOW], d[WINDOW];
@@ -55,12 +61,18 @@ int oracle_tantan_mask(int8_t* seq, int len, const float* lr, float p_repeat, fl
 		for (int off = 0; off < WINDOW; ++off) e[off] = i - 1 - off >= 0 ? lr[ltr * 32 + (seq[i - 1 - off] & 31)] : 0.0f;
 		const float b_old = b;
 		float f_sum_new = 0.0f;
+		if (variant == 1)
+			for (int off = 48; off < 50; ++off) {
+				const float t1 = f[off] * f2f, t2 = b_old * d[off];
+				const float tmp = t1 + t2;
+				f_sum_new += tmp * e[off];
+			}
 		for (int g = 0; g < 6; ++g) {
 			float v[8];
 			for (int l = 0; l < 8; ++l) {
 				const int off = 8 * g + l;
 				const float t1 = f[off] * f2f, t2 = b_old * d[off];
-				const float tmp = t1 + t2;
+				const float tmp = variant == 3 ? fmaf(f[off], f2f, t2) : t1 + t2;
 				v[l] = tmp * e[off];
 				f[off] = v[l];
 			}
@@ -68,10 +80,10 @@ int oracle_tantan_mask(int8_t* seq, int len, const float* lr, float p_repeat, fl
 		}
 		for (int off = 48; off < 50; ++off) {
 			const float t1 = f[off] * f2f, t2 = b_old * d[off];
-			float vf = t1 + t2;
+			float vf = variant == 3 ? fmaf(f[off], f2f, t2) : t1 + t2;
 			vf = vf * e[off];
 			f[off] = vf;
-			f_sum_new += vf;
+			if (variant != 1) f_sum_new += vf;
 		}
 		{ const float t1 = b_old * b2b, t2 = f_sum * p_repeat_end; b = t1 + t2; }
 		f_sum = f_sum_new;
@@ -104,6 +116,8 @@ int oracle_tantan_mask(int8_t* seq, int len, const float* lr, float p_repeat, fl
 		for (int off = 0; off < WINDOW; ++off) e[off] = i - 1 - off >= 0 ? lr[ltr * 32 + (orig[i - 1 - off] & 31)] : 0.0f;
 		const float C = p_repeat_end * b;
 		float tsum = 0.0f;
+		if (variant == 2)
+			for (int off = 48; off < 50; ++off) { const float vf = f[off] * e[off]; const float t = vf * d[off]; tsum += t; }
 		for (int g = 0; g < 6; ++g) {
 			float vt[8];
 			for (int l = 0; l < 8; ++l) {
@@ -117,18 +131,31 @@ int oracle_tantan_mask(int8_t* seq, int len, const float* lr, float p_repeat, fl
 		}
 		for (int off = 48; off < 50; ++off) {
 			float vf = f[off] * e[off];
-			{ const float t = vf * d[off]; tsum += t; }
+			if (variant != 2) { const float t = vf * d[off]; tsum += t; }
 			{ const float t1 = vf * f2f, t2 = p_repeat_end * b; f[off] = t1 + t2; }
 		}
 		{ const float t1 = b2b * b; b = t1 + tsum; }
+		if (pf_out) pf_out[i] = pf;
 		if (pf >= p_mask) { seq[i] = 23; ++n_masked; }
 	}
 	free(pb); free(scale); free(orig);
 	return n_masked;
 }
 
+int oracle_tantan_mask(int8_t* seq, int len, const float* lr, float p_repeat, float p_repeat_end, float repeat_growth, float p_mask)
+{
+	return tantan_mask_variant(seq, len, lr, p_repeat, p_repeat_end, repeat_growth, p_mask, 0, NULL);
+}
+
+int oracle_tantan_mask_wrong(int8_t* seq, int len, const float* lr, float p_repeat, float p_repeat_end, float repeat_growth, float p_mask, int variant, float* pf_out)
+{
+	return tantan_mask_variant(seq, len, lr, p_repeat, p_repeat_end, repeat_growth, p_mask, variant, pf_out);
+}
+
 /* ---- likelihood-ratio matrix: lambda solves sum(inverse(exp(lambda * S))) = 1 over the 20 standard amino acids ---- */
-static int inv_sum(const int* S, int n, double lambda, double* f)
+/* f(lambda) = sum(inverse(exp(lambda * S))) - 1; valid (optional): every row and column sum of the inverse -- the letter
+ * probabilities the matrix implies -- lies in [0, 1] (LambdaCalculator::check_lambda) */
+static int inv_sum(const int* S, int n, double lambda, double* f, int* valid)
 {
 	double A[20][40];
 	for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) { A[i][j] = exp(lambda * S[i * n + j]); A[i][n + j] = i == j ? 1.0 : 0.0; }
@@ -144,23 +171,72 @@ static int inv_sum(const int* S, int n, double lambda, double* f)
 	long double acc = 0;
 	for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) acc += A[i][n + j];
 	*f = (double)(acc - 1.0L);
+	if (valid) {
+		*valid = 1;
+		for (int i = 0; i < n; ++i) {
+			double row = 0, col = 0;
+			for (int j = 0; j < n; ++j) { row += A[i][n + j]; col += A[j][n + i]; }
+			if (!(row >= 0.0 && row <= 1.0) || !(col >= 0.0 && col <= 1.0)) *valid = 0;
+		}
+	}
 	return 1;
 }
 
+/* The scale of the matrix as the reference's masking derives it (Masking::Masking, masking.cpp:132-143, LambdaCalculator): the
+ * lambda in (ub * 1e-6, ub] with f(lambda) = 0 whose implied letter probabilities are valid, ub from the smallest row / column
+ * maximum (LambdaCalculator::find_ub). The reference brackets the root with random pairs, so its last bits are not defined; this
+ * restatement takes the brackets from 4096 equal cells of the interval in ascending order, bisects the first cell with a sign change
+ * down to two neighbouring doubles and takes the one closer to the root (LambdaCalculator::binary_search). f is noisy in its last
+ * bits (a 20 x 20 inversion), so the bracket decides which of several neighbouring sign changes is found: csrc/mask_api.hip
+ * documents the same brackets, and tests/test_tantan_corpus.py asserts that both arrive at the same double. No valid root: -1,
+ * the reference's fallback (PAM250 is the one standard matrix where that happens). */
 double oracle_tantan_lambda(const int8_t* matrix8)
 {
-	int S[400];
-	for (int i = 0; i < 20; ++i) for (int j = 0; j < 20; ++j) S[i * 20 + j] = matrix8[i * 32 + j];
-	double lo = 1e-3, hi = 1.0, flo, fhi;
-	if (!inv_sum(S, 20, lo, &flo) || !inv_sum(S, 20, hi, &fhi) || flo * fhi > 0) return -1.0;
-	for (int it = 0; it < 200; ++it) {
-		const double mid = 0.5 * (lo + hi);
-		double fm;
-		if (!inv_sum(S, 20, mid, &fm)) return -1.0;
-		if ((fm < 0) == (flo < 0)) { lo = mid; flo = fm; } else { hi = mid; fhi = fm; }
-		if (hi - lo < 1e-15) break;
+	enum { N = 20, GRID = 4096 };
+	int S[N * N];
+	for (int i = 0; i < N; ++i) for (int j = 0; j < N; ++j) S[i * N + j] = matrix8[i * 32 + j];
+	double r_max_min = 1e300, c_max_min = 1e300;
+	int zero_rows = 0, zero_cols = 0;
+	for (int i = 0; i < N; ++i) {
+		int rmax = -128, rmin = 127, cmax = -128, cmin = 127;
+		for (int j = 0; j < N; ++j) {
+			if (S[i * N + j] > rmax) rmax = S[i * N + j];
+			if (S[i * N + j] < rmin) rmin = S[i * N + j];
+			if (S[j * N + i] > cmax) cmax = S[j * N + i];
+			if (S[j * N + i] < cmin) cmin = S[j * N + i];
+		}
+		if (rmax == 0 && rmin == 0) ++zero_rows; else if (rmax <= 0 || rmin >= 0) return -1.0; else if (rmax < r_max_min) r_max_min = rmax;
+		if (cmax == 0 && cmin == 0) ++zero_cols; else if (cmax <= 0 || cmin >= 0) return -1.0; else if (cmax < c_max_min) c_max_min = cmax;
 	}
-	return 0.5 * (lo + hi);
+	if (zero_rows == N) return -1.0;
+	const double ub = r_max_min > c_max_min ? 1.1 * log(1.0 * (N - zero_rows)) / r_max_min : 1.1 * log(1.0 * (N - zero_cols)) / c_max_min;
+	const double lb = ub * 1e-6;
+	double x0 = lb, f0 = 0;
+	int have0 = inv_sum(S, N, x0, &f0, NULL);
+	for (int g = 1; g <= GRID; ++g) {
+		const double x1 = lb + (ub - lb) * g / GRID;
+		double f1 = 0;
+		const int have1 = inv_sum(S, N, x1, &f1, NULL);
+		if (have0 && have1 && (f0 < 0) != (f1 < 0)) {
+			double lo = x0, hi = x1, flo = f0, fhi = f1;
+			int ok = 1;
+			for (int it = 0; it < 200 && ok; ++it) {
+				const double mid = 0.5 * (lo + hi);
+				double fm;
+				if (mid == lo || mid == hi) break;
+				ok = inv_sum(S, N, mid, &fm, NULL);
+				if (ok) { if ((fm < 0) == (flo < 0)) { lo = mid; flo = fm; } else { hi = mid; fhi = fm; } }
+			}
+			if (ok) {
+				const double lambda = fabs(flo) < fabs(fhi) ? lo : hi;
+				double fl;
+				int valid = 0;
+				if (inv_sum(S, N, lambda, &fl, &valid) && valid && fabs(fl) < 1e-3) return lambda;
+			}
+		}
+		x0 = x1; f0 = f1; have0 = have1;
+	}
+	return -1.0;
 }
 
 /* Masking::Masking: lr[i][j] = (float)exp(lambda * score(i, j)) for the 26 alphabet letters, 0 elsewhere */

@@ -219,3 +219,20 @@ def hauser_bias(seq, matrix8, bg, window=40):
     lib().emu_hauser_bias(s.ctypes.data_as(ctypes.c_void_p), len(s), m.ctypes.data_as(ctypes.c_void_p), b.ctypes.data_as(ctypes.c_void_p),
                           int(window), out.ctypes.data_as(ctypes.c_void_p))
     return out
+
+
+def xdrop_segments(matrix8, qblock, cbs, tblock, qa, sa, xdrop):
+    """Both walks of xdrop_walk_core (xdrop_core.h, host instantiation) for seed hits at block offsets qa / sa, as xdrop_seg_kernel
+    calls them. Returns an (n, 3) int32 array: left reach, right reach, score."""
+    m = np.ascontiguousarray(matrix8, dtype=np.int8)
+    q = np.ascontiguousarray(qblock, dtype=np.int8)
+    t = np.ascontiguousarray(tblock, dtype=np.int8)
+    c = np.ascontiguousarray(cbs, dtype=np.int8) if cbs is not None else None
+    qa = np.ascontiguousarray(qa, dtype=np.int64)
+    sa = np.ascontiguousarray(sa, dtype=np.int64)
+    out = np.zeros((len(qa), 3), np.int32)
+    v = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    f = lib().emu_xdrop_segments
+    f.restype = None
+    f(v(m), v(q), v(c) if c is not None else None, v(t), v(qa), v(sa), ctypes.c_int64(len(qa)), int(xdrop), v(out))
+    return out

@@ -10,27 +10,10 @@ import pytest
 
 from tapfile import read_ext_tap
 from diamond_amd import hip
+from xdrop_cases import _reference_xdrop
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(300)]
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-
-
-def _reference_xdrop(M, q, cbs, t, qa, sa, xdrop):
-    score = st = 0
-    n, delta, length = 1, 0, 0
-    i, j = qa - 1, sa - 1
-    while score - st < xdrop and (q[i] & 31) != 31 and (t[j] & 31) != 31:
-        st += int(M[q[i] & 31, t[j] & 31]) + (int(cbs[i]) if cbs is not None else 0)
-        if st > score:
-            score, delta = st, n
-        i -= 1; j -= 1; n += 1
-    i, j, st, n = qa, sa, score, 1
-    while score - st < xdrop and (q[i] & 31) != 31 and (t[j] & 31) != 31:
-        st += int(M[q[i] & 31, t[j] & 31]) + (int(cbs[i]) if cbs is not None else 0)
-        if st > score:
-            score, length = st, n
-        i += 1; j += 1; n += 1
-    return delta, length + delta, score
 
 
 @pytest.mark.parametrize("tap", ["ext_fast_synth.tap", "ext_default.tap"])

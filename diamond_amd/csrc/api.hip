@@ -356,7 +356,7 @@ extern "C" void dmnd_destroy(dmnd_ctx* c)
 	for (DevBuf& kb : c->keep_trace) kb.release();
 	c->stage_h.release(); c->ends_h.release(); c->stage_d.release();
 	c->xd_hits.release(); c->xd_out.release(); c->xd_host.release();
-	c->plan_dev.release(); c->plan_host.release();
+	c->plan_dev.release(); c->plan_host.release(); c->rank_dev.release();
 	c->ext_dev.release(); c->ext_trace.release(); c->ext_host.release(); c->ext_ev.release();
 	for (DevBuf& b : c->ext_trace_more) b.release();
 	c->ext_tr.release(); c->ext_tr_raw.release(); c->ext_tr_store.release(); c->ext_tr_out.release(); c->ext_source_lens.release();

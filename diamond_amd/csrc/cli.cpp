@@ -694,6 +694,8 @@ int run_blastp(const Options& o)
 	const bool tantan = o.masking.empty() || o.masking == "1" || o.masking == "tantan";
 	const bool seg = o.masking == "seg";
 	const bool seg_host = seg && std::getenv("DMND_SEG_HOST") && std::getenv("DMND_SEG_HOST")[0] == '1';
+	// DMND_RANK_HOST=1 (read per run): --global-ranking ranks every block pair's targets on host threads (dmnd_rank_targets) instead of in HBM
+	const bool rank_host = std::getenv("DMND_RANK_HOST") && std::getenv("DMND_RANK_HOST")[0] == '1';
 	const bool seg_dev = seg && !seg_host;
 	if (!tantan && !seg && o.masking != "0" && o.masking != "none")
 		throw std::runtime_error("Invalid value for --masking: " + o.masking + " (none / 0, seg, tantan / 1)");
@@ -894,6 +896,7 @@ int run_blastp(const Options& o)
 		chk(dmnd_set_approx_id(c, std::max(0.0, o.approx_id)));      // (the reference reads a value <= 0 as off)
 		chk(dmnd_set_comp_based_stats(c, o.cbs));
 		chk(dmnd_set_query_contexts(c, blastx ? 6 : 1));
+		if (o.global_ranking > 0 && !rank_host) chk(dmnd_set_seed_hits_resident(c, 1));      // the device form ranks the hits in HBM: the seed search brings none back
 		chk(dmnd_set_frameshift(c, o.frameshift, o.range_culling ? 1 : 0, o.range_cover, 16));
 		chk(dmnd_set_sensitivity(c, sens));
 		// global ranking extends its targets over the full matrix (search/setup.cpp:377-389)
@@ -1154,8 +1157,11 @@ int run_blastp(const Options& o)
 			int64_t n_hits = 0;
 			chk(dmnd_seed_search(ctx, &sp, &n_hits));
 			g_timeline.mark("dmnd_seed_search returned");
-			std::vector<dmnd_seed_hit> hits((size_t)n_hits);
-			chk(dmnd_seed_hits(ctx, hits.data(), n_hits));
+			// (--global-ranking in its device form ranks the hits where the seed stage left them: dmnd_seed_hits is not called, and the
+			// contexts were told to keep the hits out of the seed search's own readback, dmnd_set_seed_hits_resident above)
+			const bool rank_device = o.global_ranking > 0 && !rank_host;
+			std::vector<dmnd_seed_hit> hits(rank_device ? 0 : (size_t)n_hits);
+			if (!rank_device) chk(dmnd_seed_hits(ctx, hits.data(), n_hits));
 			const double sd = ms_since(t0);
 			if (g_timeline.on) {
 				double ms[5] = { 0, 0, 0, 0, 0 };
@@ -1167,13 +1173,20 @@ int run_blastp(const Options& o)
 			if (o.global_ranking > 0) {
 				// no extension here: the block pair's seed hits only update the ranking table (search/stage2.h:138, table.cpp:153-190);
 				// the targets are neither masked lazily (extend.cpp:202) nor extended before the last block
-				std::vector<dmnd_ranked_target> recs((size_t)std::max<int64_t>(n_hits, 1));
+				// The device form (the default; DMND_RANK_HOST=1: the host form) ranks in HBM and brings back per query the first N records of
+				// this block -- all the table can take from it (csrc/rank_kernels.h) --, targets already database ordinals.
+				std::vector<dmnd_ranked_target> recs((size_t)std::max<int64_t>(rank_device ? std::min<int64_t>(n_hits, (int64_t)(qr.end - qr.begin) * o.global_ranking) : n_hits, 1));
 				int64_t n_recs = 0;
-				chk(dmnd_rank_targets(ctx, q.data.data(), t.data.data(), hits.data(), n_hits, threads, recs.data(), (int64_t)recs.size(), &n_recs));
-				for (int64_t k = 0; k < n_recs; ++k) recs[(size_t)k].target += (uint32_t)tr.begin;
+				if (rank_device) chk(dmnd_rank_targets_device(ctx, nullptr, n_hits, o.global_ranking, (uint32_t)tr.begin, recs.data(), (int64_t)recs.size(), &n_recs));
+				else {
+					chk(dmnd_rank_targets(ctx, q.data.data(), t.data.data(), hits.data(), n_hits, threads, recs.data(), (int64_t)recs.size(), &n_recs));
+					for (int64_t k = 0; k < n_recs; ++k) recs[(size_t)k].target += (uint32_t)tr.begin;
+				}
+				g_timeline.mark("targets of block " + std::to_string(bi) + " ranked (" + (rank_device ? "on the device" : "on the host") + ")");
 				std::lock_guard<std::mutex> lock(merge_mutex);
 				chk(dmnd_rank_update(rank_table.data(), (int64_t)(qr.end - qr.begin), o.global_ranking, recs.data(), n_recs));
-				for (const dmnd_seed_hit& h : hits) seeded[h.query / C] = 1;
+				// (a query with a seed hit keeps at least one record, in either form)
+				for (int64_t k = 0; k < n_recs; ++k) seeded[recs[(size_t)k].query] = 1;
 				ms_upload += up; ms_mask += mk; ms_seed += sd;
 				total_hits += n_hits;
 				if (&qr == &q_blocks.front()) { mt_total += mt; motif_letters += ml; }

@@ -107,6 +107,8 @@ struct dmnd_ctx {
 	dmnd::DevBuf plan_dev;                    // device planner of dmnd_extend (plan_kernels.hip): its work arrays ...
 	dmnd::PinBuf plan_host;                   // ... and the group / query / band lists it hands to the host
 	void* plan_tmp = nullptr; size_t plan_tmp_bytes = 0;      // rocPRIM scan scratch of the planner
+	dmnd::DevBuf rank_dev;                    // device form of the global ranking step (rank_api.hip): its work arrays and records; grows on demand
+	double rank_stats[4] = { 0, 0, 0, 0 };     // of the last dmnd_rank_targets_device: groups, hits whose walk counted, records returned, 1 = hits taken from HBM
 	dmnd::DevBuf ext_dev, ext_trace;          // device half of dmnd_extend behind the planner (extend_kernels.hip): work arrays, kept traces
 	std::vector<dmnd::DevBuf> ext_trace_more; // ... the kept traces of the ranking chunks behind the first
 	dmnd::DevBuf ext_tr, ext_tr_raw, ext_tr_store, ext_tr_out;      // ... with a transcript arena: the transcript arrays (extend_core.h tr_layout), the raw slots of one walked piece, the store of the kept transcripts, the gathered output
@@ -159,6 +161,7 @@ struct dmnd_ctx {
 	size_t seed_ret_bytes_header = 0;
 	double seed_chain_wait_us = 0.0;
 	int seed_chain_rest = 0;                   // searches that leave the chain out by default (seed_api.hip chain_by_default)
+	bool seed_hits_stay = false;               // dmnd_set_seed_hits_resident: the chain's readback carries the counter block only, the sorted hits stay in HBM
 	int64_t seed_last_hits = -1;               // hits of the context's last complete seed search (-1: none yet): sizes the chain's readback
 	// gapped filter (gapped_api.hip)
 	dmnd::DevBuf gf_tables, gf_hits, gf_flags, gf_scores, gf_units;

@@ -58,6 +58,7 @@
 #include "match_order.h"
 #include "extend_device.h"
 #include "top_core.h"
+#include "rank_core.h"
 #include <unordered_map>
 
 namespace dmnd {
@@ -117,7 +118,7 @@ void make_cfg(const dmnd_ctx* c, HostCfg& h)
 {
 	for (int i = 0; i < 32 * 32; ++i) { h.S.m[i] = c->params.matrix8[i]; if ((i & 31) < 24) h.rows[i >> 5][i & 31] = (i & 31) < 20 ? c->params.matrix8[i] : 0; }
 	h.S.gap_open = c->params.gap_open; h.S.gap_extend = c->params.gap_extend;
-	h.xdrop = (int)std::ceil((12.3 * 0.69314718055994530941723212145818 + std::log(c->params.K)) / c->params.lambda);
+	h.xdrop = rank_xdrop(c->params.K, c->params.lambda);                      // config.raw_ungapped_xdrop (rank_core.h: one statement for both forms of the global ranking)
 	for (int i = 0; i < 20; ++i) {                     // ScoreMatrix::init_background_scores, score_matrix.cpp:241-248
 		h.background_scores[i] = 0;
 		for (int j = 0; j < 20; ++j) h.background_scores[i] += BLOSUM62_BG[j] * h.S.at(i, j);
@@ -1762,7 +1763,7 @@ extern "C" int dmnd_rank_targets(dmnd_ctx* c, const int8_t* qdata, const int8_t*
 			Seg d = walk(sh[g.begin]);
 			int score = d.score, context = sh[g.begin].frame;
 			for (size_t x = g.begin + 1; x < g.end; ++x) {
-				if (d.diag() == sh[x].i - sh[x].j && d.j_end() >= sh[x].j) continue;
+				if (rank_skips(d.diag(), d.j_end(), sh[x].i - sh[x].j, sh[x].j)) continue;      // (rank_core.h: the rule both forms share)
 				d = walk(sh[x]);
 				if (d.score > score) { score = d.score; context = sh[x].frame; }
 			}

@@ -76,5 +76,7 @@ struct PlanArgs {
 };
 
 hipError_t launch_plan(const PlanArgs& a, hipStream_t st);
+// its grouping half alone (groups / pairs / queries of the hits; plan_kernels.hip): what the device form of the global ranking needs
+hipError_t launch_plan_groups(const PlanArgs& a, hipStream_t st, size_t extra_tmp);
 
 }  // namespace dmnd

@@ -426,18 +426,19 @@ void plan_kernel_table(const void** out, int* n)
 	for (int i = 0; i < *n; ++i) out[i] = k[i];
 }
 
-hipError_t launch_plan(const PlanArgs& a, hipStream_t st)
+// The grouping half of the planner alone: counters cleared, (six contexts: key, stable radix sort, permute, pair scan | one: mark), head
+// scan, fill -- groups, pairs and queries of the call's hits and nothing else. launch_plan runs it first; the device form of the global
+// ranking (rank_kernels.hip) runs only this. extra_tmp: scratch bytes the caller needs from *a.scan_tmp behind this launch (grown once).
+hipError_t launch_plan_groups(const PlanArgs& a, hipStream_t st, size_t extra_tmp)
 {
 	if (a.n_hits <= 0) return hipSuccess;
 	const size_t n = (size_t)a.n_hits;
 	hipError_t e = hipMemsetAsync(a.counters, 0, sizeof(PlanCounters), st);
 	if (e != hipSuccess) return e;
-	const unsigned b256 = (unsigned)((n + 255) / 256), b64 = (unsigned)((n + 63) / 64), b256g = (unsigned)((n + 1 + 255) / 256);
+	const unsigned b256 = (unsigned)((n + 255) / 256);
 	const bool translated = a.contexts > 1;
-	size_t need = 0, need2 = 0, need3 = 0, need4 = 0;
+	size_t need = 0, need3 = 0, need4 = 0;
 	e = rocprim::inclusive_scan(nullptr, need, a.heads, a.head_scan, n, rocprim::plus<uint64_t>(), st);
-	if (e != hipSuccess) return e;
-	e = rocprim::exclusive_scan(nullptr, need2, a.band_count, a.band_off, 0u, n + 1, rocprim::plus<uint32_t>(), st);
 	if (e != hipSuccess) return e;
 	if (translated) {
 		e = rocprim::radix_sort_pairs(nullptr, need3, a.keys, a.keys_sorted, a.perm_in, a.perm, n, 0, a.key_bits, st);
@@ -445,7 +446,7 @@ hipError_t launch_plan(const PlanArgs& a, hipStream_t st)
 		e = rocprim::inclusive_scan(nullptr, need4, a.pheads, a.phead_scan, n, rocprim::plus<uint32_t>(), st);
 		if (e != hipSuccess) return e;
 	}
-	size_t need_all = need > need2 ? need : need2;
+	size_t need_all = need > extra_tmp ? need : extra_tmp;
 	if (need3 > need_all) need_all = need3;
 	if (need4 > need_all) need_all = need4;
 	e = ensure_tmp(a.scan_tmp, a.scan_tmp_bytes, need_all);
@@ -462,6 +463,20 @@ hipError_t launch_plan(const PlanArgs& a, hipStream_t st)
 	e = rocprim::inclusive_scan(*a.scan_tmp, need, a.heads, a.head_scan, n, rocprim::plus<uint64_t>(), st);
 	if (e != hipSuccess) return e;
 	hipLaunchKernelGGL(plan_fill_kernel, dim3(b256), dim3(256), 0, st, a);
+	return hipGetLastError();
+}
+
+hipError_t launch_plan(const PlanArgs& a, hipStream_t st)
+{
+	if (a.n_hits <= 0) return hipSuccess;
+	const size_t n = (size_t)a.n_hits;
+	const unsigned b256 = (unsigned)((n + 255) / 256), b64 = (unsigned)((n + 63) / 64), b256g = (unsigned)((n + 1 + 255) / 256);
+	const bool translated = a.contexts > 1;
+	size_t need2 = 0;
+	hipError_t e = rocprim::exclusive_scan(nullptr, need2, a.band_count, a.band_off, 0u, n + 1, rocprim::plus<uint32_t>(), st);
+	if (e != hipSuccess) return e;
+	e = launch_plan_groups(a, st, need2);
+	if (e != hipSuccess) return e;
 	// groups <= hits: the per-group kernels are launched over the hit count and return beyond the group count (read on the device)
 	hipLaunchKernelGGL(plan_segments_kernel, dim3(b64), dim3(64), 0, st, a);
 	// (the chaining kernels are launched over the upper bound of one group per two hits -- a group that needs chaining has at least

@@ -851,7 +851,8 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 		}
 		// the copy is on the call's serial path: of the hits that the budget allows it carries as many as the context's last search
 		// found plus a quarter (more hits than that: dmnd_seed_hits copies, and the next search's readback is sized for them)
-		const int64_t copy_hits = c->seed_last_hits < 0 ? ret_hits : std::min<int64_t>(ret_hits, c->seed_last_hits + c->seed_last_hits / 4 + 1024);
+		// (dmnd_set_seed_hits_resident: none of them -- the caller reads the hits where they lie in HBM)
+		const int64_t copy_hits = c->seed_hits_stay ? 0 : c->seed_last_hits < 0 ? ret_hits : std::min<int64_t>(ret_hits, c->seed_last_hits + c->seed_last_hits / 4 + 1024);
 		HIP_TRY(hipMemcpyAsync(c->seed_ret_h.p, c->seed_ret.p, chain_ret_header_bytes(S) + (size_t)copy_hits * sizeof(dmnd_seed_hit), hipMemcpyDeviceToHost, st));
 		lap("chain enqueued");
 		{
@@ -1098,6 +1099,15 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 	}
 	*n_hits = c->n_seed_hits;
 	c->seed_last_hits = c->n_seed_hits;
+	return DMND_OK;
+}
+
+extern "C" int64_t dmnd_seed_hit_count(const dmnd_ctx* c) { return c ? c->n_seed_hits : -1; }
+
+extern "C" int dmnd_set_seed_hits_resident(dmnd_ctx* c, int on)
+{
+	if (!c) return fail(DMND_E_ARG, "dmnd_set_seed_hits_resident: ctx is NULL");
+	c->seed_hits_stay = on != 0;
 	return DMND_OK;
 }
 

@@ -84,7 +84,7 @@ EXPORTS = ["dmnd_abi_version", "dmnd_last_error", "dmnd_default_params", "dmnd_c
            "dmnd_seed_params_set_index_chunks", "dmnd_join_blocks", "dmnd_set_sensitivity", "dmnd_touch_streams",
            "dmnd_seed_params_set_query_indexed", "dmnd_auto_query_indexed", "dmnd_set_motif_table", "dmnd_motif_table_size",
            "dmnd_soft_mask_block", "dmnd_download_block", "dmnd_seg_mask_block_device", "dmnd_seg_mask_sequences_device", "dmnd_seg_ranges_device", "dmnd_seg_device_stats", "dmnd_output_fields", "dmnd_format_fields", "dmnd_format_pairwise_intro", "dmnd_format_pairwise",
-           "dmnd_format_paf", "dmnd_device_count", "dmnd_set_top_percent", "dmnd_join_blocks_top", "dmnd_set_filters", "dmnd_format_sam", "dmnd_set_query_source_lengths", "dmnd_format_fields_unaligned", "dmnd_format_fields_header", "dmnd_set_query_index_reuse", "dmnd_set_no_self_hits", "dmnd_matrix_params", "dmnd_masking_lambda", "dmnd_translate_opts", "dmnd_set_extension_mode", "dmnd_format_xml_header", "dmnd_format_xml_query_intro", "dmnd_format_xml", "dmnd_format_xml_query_epilog", "dmnd_format_daa_header", "dmnd_format_daa_query", "dmnd_format_daa_match", "dmnd_seg_ranges", "dmnd_seg_mask_block", "dmnd_seg_lnfact", "dmnd_daa_match_read", "dmnd_hsp_from_transcript", "dmnd_hsp_from_transcript_frames", "dmnd_set_format_flags", "dmnd_host_alloc", "dmnd_host_free", "dmnd_share_block", "dmnd_copy_block", "dmnd_init", "dmnd_seed_reserve", "dmnd_mask_sequences", "dmnd_set_max_hsps", "dmnd_rank_targets", "dmnd_rank_update", "dmnd_set_global_ranking",
+           "dmnd_format_paf", "dmnd_device_count", "dmnd_set_top_percent", "dmnd_join_blocks_top", "dmnd_set_filters", "dmnd_format_sam", "dmnd_set_query_source_lengths", "dmnd_format_fields_unaligned", "dmnd_format_fields_header", "dmnd_set_query_index_reuse", "dmnd_set_no_self_hits", "dmnd_matrix_params", "dmnd_masking_lambda", "dmnd_translate_opts", "dmnd_set_extension_mode", "dmnd_format_xml_header", "dmnd_format_xml_query_intro", "dmnd_format_xml", "dmnd_format_xml_query_epilog", "dmnd_format_daa_header", "dmnd_format_daa_query", "dmnd_format_daa_match", "dmnd_seg_ranges", "dmnd_seg_mask_block", "dmnd_seg_lnfact", "dmnd_daa_match_read", "dmnd_hsp_from_transcript", "dmnd_hsp_from_transcript_frames", "dmnd_set_format_flags", "dmnd_host_alloc", "dmnd_host_free", "dmnd_share_block", "dmnd_copy_block", "dmnd_init", "dmnd_seed_reserve", "dmnd_mask_sequences", "dmnd_set_max_hsps", "dmnd_rank_targets", "dmnd_rank_update", "dmnd_set_global_ranking", "dmnd_rank_targets_device", "dmnd_rank_device_stats", "dmnd_seed_hit_count", "dmnd_set_seed_hits_resident",
            "dmnd_upload_matrices", "dmnd_frameshift_swipe", "dmnd_set_frameshift", "dmnd_set_context_motif_table", "dmnd_cbs_composition", "dmnd_cbs_rule", "dmnd_cbs_target_matrix", "dmnd_cbs_ideal_lambda", "dmnd_join_blocks_range", "dmnd_join_blocks_device", "dmnd_join_blocks_device_host", "dmnd_join_ranks", "dmnd_join_ranks_plan", "dmnd_xdrop_ungapped"]
 
 
@@ -790,12 +790,29 @@ class Context:
                                                     tr.size if tr is not None else 0, ctypes.byref(used)))
         return out, (tr[:used.value] if tr is not None else None)
 
-    def seed_search(self, seed_params):
-        """Search::search_shape for all shapes/chunks on the uploaded blocks. Returns hits sorted by (query, subject, seed_offset)."""
+    def seed_search(self, seed_params, fetch=True):
+        """Search::search_shape for all shapes/chunks on the uploaded blocks. Returns hits sorted by (query, subject, seed_offset); fetch=False: only their count, the hits stay in HBM."""
         n = ctypes.c_int64(0)
         self._check(self.lib.dmnd_seed_search(self.h, ctypes.byref(seed_params), ctypes.byref(n)))
-        hits = np.empty(n.value, dtype=SEED_HIT_DTYPE)
-        self._check(self.lib.dmnd_seed_hits(self.h, hits.ctypes.data if n.value else None, n.value))
+        return self.seed_hits(n.value) if fetch else n.value
+
+    def seed_hit_count(self):
+        """Hits of the context's last seed search (dmnd_seed_hit_count: the library's own count)."""
+        self.lib.dmnd_seed_hit_count.argtypes, self.lib.dmnd_seed_hit_count.restype = [ctypes.c_void_p], ctypes.c_int64
+        return int(self.lib.dmnd_seed_hit_count(self.h))
+
+    def set_seed_hits_resident(self, on=True):
+        """dmnd_set_seed_hits_resident: the following searches leave their hits in HBM (rank_targets_device(None) reads them there);
+        a search that runs as one device chain brings back its counters only."""
+        self.lib.dmnd_set_seed_hits_resident.argtypes = [ctypes.c_void_p, ctypes.c_int]      # (without them the handle would travel as a C int)
+        self._check(self.lib.dmnd_set_seed_hits_resident(self.h, 1 if on else 0))
+
+    def seed_hits(self, n=None):
+        """The hits of the context's last seed_search (dmnd_seed_hits), sorted by (query, subject, seed_offset). n: their count where
+        the caller knows it (default: the library's, seed_hit_count)."""
+        n = self.seed_hit_count() if n is None else int(n)
+        hits = np.empty(n, dtype=SEED_HIT_DTYPE)
+        self._check(self.lib.dmnd_seed_hits(self.h, hits.ctypes.data if n else None, n))
         return hits
 
     def mask_block(self, which, host_data=None):
@@ -988,6 +1005,30 @@ class Context:
         self._check(self.lib.dmnd_rank_targets(self.h, qd.ctypes.data, td.ctypes.data, hits.ctypes.data, ctypes.c_int64(hits.size), int(threads),
                                                out.ctypes.data, ctypes.c_int64(out.size), ctypes.byref(n)))
         return out[:n.value]
+
+    def rank_targets_device(self, hits=None, n_keep=0, target_offset=0):
+        """dmnd_rank_targets_device: the records of rank_targets, made in HBM over the resident blocks. hits=None: the hits of the
+        context's last seed_search where they lie in HBM. n_keep > 0: per query the first n_keep records by (score descending, target
+        ascending); target_offset is added to every target."""
+        v = ctypes.c_void_p
+        self.lib.dmnd_rank_targets_device.argtypes = [v, v, ctypes.c_int64, ctypes.c_int, ctypes.c_uint32, v, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]
+        n = ctypes.c_int64(0)
+        if hits is None:
+            n_hits, ptr = self.seed_hit_count(), None
+        else:
+            hits = np.ascontiguousarray(hits, dtype=SEED_HIT_DTYPE)
+            n_hits, ptr = hits.size, hits.ctypes.data          # (an empty list is still a list of the caller's: not NULL)
+        out = np.zeros(max(1, n_hits), RANKED_DTYPE)
+        self._check(self.lib.dmnd_rank_targets_device(self.h, ptr, ctypes.c_int64(n_hits), int(n_keep), ctypes.c_uint32(int(target_offset)),
+                                                      out.ctypes.data, ctypes.c_int64(out.size), ctypes.byref(n)))
+        return out[:n.value]
+
+    def rank_device_stats(self):
+        """Of the last rank_targets_device: groups, hits whose walk counted (not skipped), records returned, 1 = hits taken from HBM."""
+        st = (ctypes.c_double * 4)()
+        self.lib.dmnd_rank_device_stats.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        self._check(self.lib.dmnd_rank_device_stats(self.h, st))
+        return [float(x) for x in st]
 
     def set_global_ranking(self, n):
         self._check(self.lib.dmnd_set_global_ranking(self.h, int(n)))

@@ -295,6 +295,12 @@ int dmnd_set_query_index_reuse(dmnd_ctx* ctx, int on);
 /* Copies the hits of the last dmnd_seed_search to the caller, sorted by (query, subject, seed_offset)
  * (the reference sorts by query before extension, align/align.cpp:233). cap < n -> DMND_E_CAP. */
 int dmnd_seed_hits(dmnd_ctx* ctx, dmnd_seed_hit* out, int64_t cap);
+/* Hits of the context's last dmnd_seed_search (0 before the first; -1: ctx is NULL). */
+int64_t dmnd_seed_hit_count(const dmnd_ctx* ctx);
+/* on != 0: the caller reads the hits of the following searches where they lie in HBM (dmnd_rank_targets_device with hits == NULL):
+ * a search that runs as one device chain then brings back its counter block only, not the sorted hits beside it. dmnd_seed_hits
+ * still works (it downloads them). Off by default. */
+int dmnd_set_seed_hits_resident(dmnd_ctx* ctx, int on);
 /* device milliseconds of the last dmnd_seed_search: [0] index queries [1] stream reference [2] mask [3] pair filter [4] total */
 int dmnd_seed_kernel_ms(const dmnd_ctx* ctx, double ms[5]);
 
@@ -553,7 +559,11 @@ int dmnd_xdrop_ungapped(dmnd_ctx* ctx, const dmnd_seed_hit* hits, int64_t n_hits
  * the full matrix, after the last block. Three calls:
  *  - dmnd_rank_targets after dmnd_seed_search / dmnd_seed_hits of a block pair (get_query_hits_reextend, table.cpp:108-121): one
  *    record per (query, target) of the hits = the best x-drop ungapped score over the target's seed hits (no composition bias) and
- *    the query context it was found in (target_score, table.cpp:88-106); target = block sequence id. Host code, as in the reference.
+ *    the query context it was found in (target_score, table.cpp:88-106); target = block sequence id. Two forms give the same records:
+ *    dmnd_rank_targets is host code over host copies of the blocks, as in the reference; dmnd_rank_targets_device (below) does the
+ *    step in HBM on the resident blocks, by default on the seed hits where the seed search left them, and brings back only records.
+ *    Hits of one target with equal (diagonal, column) in different frames: the host's order of them is whatever its unstable sort
+ *    leaves, the device takes them frame ascending (csrc/rank_core.h); everywhere else the two agree record for record.
  *  - dmnd_rank_update (merge_hits, table.cpp:135-151): merges such records (target already turned into a database ordinal by the
  *    caller, records grouped by query) into a table of n entries per query, zero-initialised by the caller: per target its best
  *    score, rows ordered by (score descending, target ascending); an entry with score 0 is empty.
@@ -565,6 +575,17 @@ typedef struct { uint32_t query, target; uint16_t score; uint8_t context, pad; }
 int dmnd_rank_targets(dmnd_ctx* ctx, const int8_t* qdata, const int8_t* tdata, const dmnd_seed_hit* hits, int64_t n_hits, int threads,
 	dmnd_ranked_target* out, int64_t cap, int64_t* n_out);
 int dmnd_rank_update(dmnd_ranked_target* table, int64_t n_queries, int n, const dmnd_ranked_target* records, int64_t n_records);
+/* dmnd_rank_targets on the device: same records. hits == NULL: the hits of the context's last dmnd_seed_search where
+ * they lie in HBM (n_hits must equal its count). hits != NULL: uploaded first; must be in the order dmnd_seed_hits
+ * returns (else DMND_E_ARG). n_keep == 0: every record, ordered by (query, target) like dmnd_rank_targets;
+ * n_keep > 0: per query the first n_keep by (score descending, target ascending), in that order.
+ * target_offset is added to every target (block id -> database ordinal). *n_out is set also on DMND_E_CAP.
+ * Both blocks must be uploaded with limits; dmnd_set_query_contexts is honoured (a record per read and target). The cut loses
+ * nothing for dmnd_rank_update with n <= n_keep (csrc/rank_kernels.h has the argument). */
+int dmnd_rank_targets_device(dmnd_ctx* ctx, const dmnd_seed_hit* hits, int64_t n_hits, int n_keep, uint32_t target_offset,
+	dmnd_ranked_target* out, int64_t cap, int64_t* n_out);
+/* Of the last call: [0] groups, [1] hits whose walk counted (not skipped), [2] records returned, [3] 1 = hits taken from HBM. */
+int dmnd_rank_device_stats(const dmnd_ctx* ctx, double out[4]);
 int dmnd_set_global_ranking(dmnd_ctx* ctx, int n);
 /* Multi-block databases (-b / --block-size): the records of one query block against several reference
  * blocks (dmnd_match::target already offset to database ordinals by the caller, blocks in any order) are merged per query

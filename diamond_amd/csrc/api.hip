@@ -495,7 +495,7 @@ extern "C" int dmnd_share_block(dmnd_ctx* c, int which, const dmnd_ctx* src)
 	c->limits[which] = src->limits[which];
 	c->coarse[which] = src->coarse[which];
 	c->soft_valid[which] = false;
-	if (which == DMND_QUERY) { c->source_lens = src->source_lens; c->source_lens_generation = ~(uint64_t)0; ++c->query_generation; }
+	if (which == DMND_QUERY) { c->source_lens = src->source_lens; c->source_lens_generation = ~(uint64_t)0; ++c->query_generation; ++c->query_limits_version; }
 	return DMND_OK;
 }
 
@@ -546,7 +546,7 @@ extern "C" int dmnd_upload_block(dmnd_ctx* c, int which, const int8_t* data, int
 	HIP_TRY(sync_stream(lane ? c->t_stream : c->stream));
 	c->block_len[which] = data_len;
 	c->soft_valid[which] = false;
-	if (which == DMND_QUERY) { c->source_lens.clear(); c->source_lens_generation = ~(uint64_t)0; ++c->query_generation; }
+	if (which == DMND_QUERY) { c->source_lens.clear(); c->source_lens_generation = ~(uint64_t)0; ++c->query_generation; ++c->query_limits_version; }
 	c->limits[which].clear();
 	c->coarse[which].clear();
 	if (limits) {
@@ -559,6 +559,8 @@ extern "C" int dmnd_upload_block(dmnd_ctx* c, int which, const int8_t* data, int
 			while (sidx + 1 <= n_seqs && limits[sidx + 1] <= pos) ++sidx;
 			co[b] = (uint32_t)std::min<int64_t>(sidx, n_seqs - 1);
 		}
+		// the seed stage's query ids: once per uploaded block, not once per search of it (one query block meets many reference blocks and shapes)
+		if (which == DMND_QUERY) return dmnd_seed_query_ids(c);
 	}
 	return DMND_OK;
 }

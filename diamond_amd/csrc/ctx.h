@@ -162,7 +162,11 @@ struct dmnd_ctx {
 	double seed_chain_wait_us = 0.0;
 	int seed_chain_rest = 0;                   // searches that leave the chain out by default (seed_api.hip chain_by_default)
 	bool seed_hits_stay = false;               // dmnd_set_seed_hits_resident: the chain's readback carries the counter block only, the sorted hits stay in HBM
-	int64_t seed_last_hits = -1;               // hits of the context's last complete seed search (-1: none yet): sizes the chain's readback
+	int64_t seed_last_hits = -1;               // hits of the context's last complete seed search (-1: none yet): sizes the chain's readback and its padded sort
+	// qid_of (query position -> query id) depends on the query block's limits alone: filled when they arrive (dmnd_upload_block), or by
+	// the first search that finds it out of date (a shared block, a buffer that has grown since)
+	uint64_t query_limits_version = 0;         // bumped whenever limits[DMND_QUERY] change
+	uint64_t qid_of_version = ~(uint64_t)0;    // query_limits_version that qid_of holds; ~0: none
 	// gapped filter (gapped_api.hip)
 	dmnd::DevBuf gf_tables, gf_hits, gf_flags, gf_scores, gf_units;
 	double gapped_filter_evalue = 0.0, gf_ms = 0.0;
@@ -250,5 +254,7 @@ int dmnd_extend_frameshift(dmnd_ctx* c, const int8_t* qdata, const int8_t* tdata
 	std::vector<dmnd_match>& out, uint8_t* transcript, int64_t transcript_cap, int64_t* transcript_used);
 // the first n_keep adjusted matrices of c stay, n more are appended (dmnd_upload_matrices = the same with n_keep = 0)
 int dmnd_append_matrices(dmnd_ctx* c, int64_t n_keep, const int8_t* matrices, int64_t n);
+// seed_api.hip: fills c->qid_of for the query block's limits on the context's stream, unless it holds them already
+int dmnd_seed_query_ids(dmnd_ctx* c);
 // k-th of `split` auxiliary contexts of c (created on first use; owned and destroyed by c)
 dmnd_ctx* aux_context(dmnd_ctx* c, int k, int split);

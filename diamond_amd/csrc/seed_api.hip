@@ -380,7 +380,11 @@ static SeedSizes seed_sizes(const dmnd_ctx* c, const SeedParams& sp, int64_t nq_
 static int seed_reserve(dmnd_ctx* c, const SeedParams& sp, const SeedSizes& z, int64_t nq_pos, int64_t q_end, int64_t q_block_len, bool generous)
 {
 	if (int rc = c->seed_bitmap.ensure(z.bm_total)) return rc;
-	if (int rc = c->qid_of.ensure((size_t)q_end * sizeof(uint32_t))) return rc;
+	{
+		const size_t held = c->qid_of.cap;
+		if (int rc = c->qid_of.ensure((size_t)q_end * sizeof(uint32_t))) return rc;
+		if (c->qid_of.cap != held) c->qid_of_version = ~(uint64_t)0;    // grown: the ids went with the old buffer (the new one may have its address)
+	}
 	if (int rc = c->mask_time.ensure((size_t)q_block_len + 256)) return rc;
 	if (int rc = c->seed_keys.ensure((size_t)z.SB * (z.slots << z.slot_shift))) return rc;
 	if (int rc = c->seed_need.ensure((size_t)(z.slots / 32 + SEED_NEED_FOLD_WORDS) * sizeof(uint32_t))) return rc;      // the map and, behind it, its folded copy (launch_seed_collect)
@@ -403,6 +407,18 @@ static int seed_reserve(dmnd_ctx* c, const SeedParams& sp, const SeedSizes& z, i
 		if (int rc = c->seed_survivors.ensure(((size_t)1 << 20) * sizeof(SeedSurvivor))) return rc;
 		if (int rc = c->seed_scored.ensure(((size_t)1 << 20) * sizeof(SeedScored))) return rc;
 	}
+	return DMND_OK;
+}
+
+int dmnd_seed_query_ids(dmnd_ctx* c)
+{
+	const std::vector<int64_t>& ql = c->limits[DMND_QUERY];
+	if (ql.size() < 2) return DMND_OK;
+	const size_t bytes = (size_t)ql.back() * sizeof(uint32_t);
+	if (c->qid_of_version == c->query_limits_version && c->qid_of.cap >= bytes) return DMND_OK;
+	if (int rc = c->qid_of.ensure(bytes)) return rc;
+	HIP_TRY(launch_seed_qid(c->d_limits[DMND_QUERY].as<int64_t>(), (int64_t)ql.size() - 1, c->qid_of.as<uint32_t>(), c->stream));
+	c->qid_of_version = c->query_limits_version;
 	return DMND_OK;
 }
 
@@ -449,6 +465,7 @@ static int seed_deferred_pass(dmnd_ctx* c, SeedArgs a, int sid, int64_t n_matche
 //  * a context whose last chain met something no buffer growth removes (deferred pairs, the tiled filter, more hits than the padded
 //    sort holds: chain_rests_after) leaves the chain out for the next SEED_CHAIN_REST searches: there the chain only adds its
 //    readback and an unused sort (C4, deferred pairs in every search: 9.2 ms per step this way, 9.55 with the chain tried every time).
+//    (More hits than a pad below the sort's ceiling is not such a case: the next search's pad is sized for them.)
 enum { SEED_CHAIN_REST = 15 };
 static bool chain_by_default(dmnd_ctx* c, bool classes_long)
 {
@@ -456,15 +473,25 @@ static bool chain_by_default(dmnd_ctx* c, bool classes_long)
 	if (c->seed_chain_rest > 0) { --c->seed_chain_rest; return false; }
 	return true;
 }
-static bool chain_rests_after(const ChainPlan& plan, unsigned long long status)
+static bool chain_rests_after(const ChainPlan& plan, unsigned long long status, bool pad_grows)
 {
-	return plan.point == CHAIN_FROM_DEFERRED || plan.point == CHAIN_FROM_SORT || (status & CHAIN_TILED) != 0;
+	return plan.point == CHAIN_FROM_DEFERRED || (plan.point == CHAIN_FROM_SORT && !pad_grows) || (status & CHAIN_TILED) != 0;
 }
 
 // The chain's two sizes: the tuning values (csrc/tuning.h), or per call what the tests' hooks of the same names say
 static int64_t chain_sort_cap()
 {
 	return std::min<int64_t>(seed_cap("DMND_SEED_SORT_CAP", tuning().seed_sort_cap), (int64_t)1 << 24);
+}
+// The padded sort runs over its whole pad whatever the hit count: the pad is sized like the readback, by the context's last hit count
+// plus a quarter, here rounded up to a power of two (the sort merges in doubling runs) -- under the ceiling above, which also serves
+// a context's first search. More hits than that: the host's launches sort them, and the next search's pad is sized for them.
+static int64_t chain_sort_pad(int64_t ceiling, int64_t last_hits)
+{
+	if (last_hits < 0) return ceiling;
+	int64_t pad = 1024;
+	while (pad < ceiling && pad < last_hits + last_hits / 4) pad <<= 1;
+	return std::min(pad, ceiling);
 }
 static int64_t chain_readback_bytes()
 {
@@ -570,7 +597,7 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 		HIP_TRY(launch_seed_clear(z, st));
 	}
 	bool pristine = true;                                // the counters and the need map are as the clear above left them
-	HIP_TRY(launch_seed_qid(c->d_limits[DMND_QUERY].as<int64_t>(), (int64_t)ql.size() - 1, c->qid_of.as<uint32_t>(), st));
+	if (int rc = dmnd_seed_query_ids(c)) return rc;      // (filled at the upload: nothing to do here but for a shared block or a grown buffer)
 
 	// fused pipeline: 4-bit copies of the query and the reference block for the Hamming pre-filter
 	if (fused) {
@@ -796,7 +823,7 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 		const int64_t def_cap = seed_cap("DMND_SEED_DEFERRED_CAP", std::max<int64_t>((int64_t)1 << 18, (int64_t)(c->seed_deferred.cap / sizeof(SeedDeferred))));
 		int64_t tiled_from = (int64_t)1 << 22;
 		if (const char* e = getenv("DMND_SEED_TILED")) tiled_from = atoi(e) != 0 ? 0 : INT64_MAX;
-		const int64_t sort_cap = chain_sort_cap();
+		const int64_t sort_ceiling = chain_sort_cap(), sort_cap = chain_sort_pad(sort_ceiling, c->seed_last_hits);
 		const int64_t ret_hits = chain_ret_hits(chain_readback_bytes(), (int64_t)sizeof(dmnd_seed_hit), sort_cap);
 		const size_t ret_bytes = chain_ret_header_bytes(S) + (size_t)ret_hits * sizeof(dmnd_seed_hit);
 		if (int rc = c->matched_slot.ensure((size_t)cap_total * sizeof(uint32_t))) return rc;
@@ -805,10 +832,10 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 		if (int rc = c->seed_scored.ensure((size_t)surv_cap * sizeof(SeedScored))) return rc;
 		if (int rc = c->seed_hits.ensure((size_t)hit_cap * sizeof(dmnd_seed_hit))) return rc;
 		if (int rc = c->seed_deferred.ensure((size_t)def_cap * sizeof(SeedDeferred))) return rc;
-		if (int rc = c->seed_hits_sorted.ensure((size_t)sort_cap * sizeof(dmnd_seed_hit))) return rc;
+		if (int rc = c->seed_hits_sorted.ensure((size_t)sort_ceiling * sizeof(dmnd_seed_hit))) return rc;
 		for (int k = 0; k < 2; ++k) {
-			if (int rc = c->sort_keys[k].ensure((size_t)sort_cap * sizeof(uint64_t))) return rc;
-			if (int rc = c->sort_idx[k].ensure((size_t)sort_cap * sizeof(uint32_t))) return rc;
+			if (int rc = c->sort_keys[k].ensure((size_t)sort_ceiling * sizeof(uint64_t))) return rc;
+			if (int rc = c->sort_idx[k].ensure((size_t)sort_ceiling * sizeof(uint32_t))) return rc;
 		}
 		if (int rc = c->seed_ret.ensure(ret_bytes)) return rc;
 		if (int rc = c->seed_ret_h.ensure(ret_bytes)) return rc;
@@ -877,7 +904,7 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 		for (int sid = 0; sid < S && (unsigned long long)sid < done + ((status & (CHAIN_SURVIVORS_OVER | CHAIN_HITS_OVER | CHAIN_DEFERRED)) ? 1 : 0); ++sid) c->seed_trace[sid] = r[chain_ctr_survivors_of(S) + sid];
 		phase1_done = plan.point != CHAIN_FROM_PHASE1;
 		kept_hit_cap = hit_cap; kept_def_cap = def_cap;
-		if (chain_env < 0 && chain_rests_after(plan, status)) c->seed_chain_rest = SEED_CHAIN_REST;
+		if (chain_env < 0 && chain_rests_after(plan, status, sort_seed_hits_one_key(query_bits, subject_bits, off_bits) && (int64_t)r[S] <= sort_ceiling)) c->seed_chain_rest = SEED_CHAIN_REST;
 		switch (plan.point) {
 		case CHAIN_COMPLETE:
 			hits_done = true;

@@ -359,6 +359,17 @@ DMND_HD bool left_most_pair(const SeedParams& c, const int8_t* q, const uint8_t*
 	return left_most_pair_t(LmBytewise(), c, q, qmt, s, seed_offset, sid, chunk, query_len);
 }
 
+// 4-bit class maps of the 32 letter codes (letters 0-15, 16-31): 15 = invalid (X, '*'), else the reduced class. What the reference
+// stream, the query keys and the left-most rule decode letters with; needs reduction_size <= 15.
+DMND_HD void seed_class_maps(const SeedParams& c, uint64_t& lo, uint64_t& hi)
+{
+	lo = 0; hi = 0;
+	for (int l = 0; l < 32; ++l) {
+		const uint64_t code = c.reduction[l] == L_MASK ? 15u : (uint64_t)(c.reduction[l] & 15);
+		(l < 16 ? lo : hi) |= code << ((l & 15) * 4);
+	}
+}
+
 // Stage-2 ungapped window score: best running local score over `window` aligned letters
 // (window_ungapped_best / ungapped_window, src/dp/ungapped_simd.cpp:32-87, dp/ungapped_align.cpp:244-258).
 DMND_HD int ungapped_window_score(const int8_t* M, const int8_t* q, const int8_t* s, int window)

@@ -2,7 +2,7 @@
 // Search::search_shape (/root/reference/src/search/stage0.cpp:101-217) and its SIMD stage-1/2 filters.
 //
 // Data flow (per-thread arithmetic in seed_core.h):
-//   seed_qid_kernel     query position -> query id (for Hit::query_ and the seed offset)
+//   seed_qid_kernel     query position -> query id (for Hit::query_ and the seed offset); once per uploaded query block
 //   launch_seed_build   the query side from ONE sort: every query position's seed in registers -> its sort key (top bits of
 //                       its hash); a stable radix sort; then the open-addressing table in HBM, the per-seed lists of query
 //                       positions and both filters of the stream are written in sorted order with plain stores
@@ -110,6 +110,74 @@ __global__ void seed_order_kernel(SeedArgs a, int sid, uint32_t* __restrict__ sk
 	skey[i] = k;
 }
 
+__device__ __forceinline__ uint32_t reduce4(uint32_t letter, uint64_t map_lo, uint64_t map_hi)
+{
+	const uint64_t m = (letter & 16) ? map_hi : map_lo;
+	return (uint32_t)(m >> ((letter & 15) * 4)) & 15u;
+}
+
+// seed_order_kernel for shapes of up to 16 letters over at most 15 classes, 16 positions per thread: the letters decoded the way the
+// plain branch of seed_stream_fast_kernel decodes the reference (two 16-byte loads, class nibbles, delimiter and bad-letter maps), a
+// window's key one funnel shift and the care mask. One thread per position spent ~12 byte loads and as many table look-ups in the
+// kernel arguments on it (62-117 us for the 3e6 positions of C2). The workgroup's 4096 (sort key, table key) pairs go through LDS,
+// 17 entries per thread's 16 against bank conflicts, so that the stores are coalesced. HASHED: seed_key_hashed keeps the windows
+// that hold a mask or stop letter; a low-complexity seed is masked here, as in seed_order_kernel.
+template<bool HASHED>
+__global__ __launch_bounds__(256) void seed_order16_kernel(SeedArgs a, int sid, uint64_t map_lo, uint64_t map_hi, int64_t base, uint64_t care64,
+	uint32_t* __restrict__ skey, uint64_t* __restrict__ keys, uint32_t* __restrict__ ctr)
+{
+	__shared__ uint32_t s_top[256 * 17];
+	__shared__ uint64_t s_key[256 * 17];
+	if (blockIdx.x == 0 && threadIdx.x < 4) ctr[threadIdx.x] = 0;
+	const int64_t wg_base = base + (int64_t)blockIdx.x * 4096;
+	const int64_t p0 = wg_base + (int64_t)threadIdx.x * 16;
+	const uint32_t none = 1u << a.slot_bits;
+	if (p0 < a.q_end) {
+		typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+		const u32x4 v0 = *reinterpret_cast<const u32x4*>(a.qseed + p0), v1 = *reinterpret_cast<const u32x4*>(a.qseed + p0 + 16);
+		const uint32_t w[8] = { v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w };
+		uint64_t codes[2] = { 0, 0 };
+		uint32_t delim = 0, bad = 0;
+#pragma unroll
+		for (int j = 0; j < 32; ++j) {
+			const uint32_t l = (w[j >> 2] >> ((j & 3) * 8)) & LETTER_MASK;
+			const uint32_t c = reduce4(l, map_lo, map_hi);
+			codes[j >> 4] |= (uint64_t)(HASHED && c == 15u ? 0u : c) << ((j & 15) * 4);
+			delim |= (l == L_DELIM ? 1u : 0u) << j;
+			bad |= (c == 15u ? 1u : 0u) << j;
+		}
+		const uint32_t care = a.params.shape_mask[sid], span = (1u << a.params.shape_len[sid]) - 1;      // length <= 16
+		const int64_t first = a.q_begin - p0, last = a.q_end - p0;                                       // window starts of the block: first <= i < last
+#pragma unroll
+		for (int i = 0; i < 16; ++i) {
+			const int sh = i * 4;
+			uint64_t seed = (sh == 0 ? codes[0] : (codes[0] >> sh) | (codes[1] << (64 - sh))) & care64;
+			const bool inside = i >= first && i < last && ((delim >> i) & span) == 0;
+			// spaced seeds: no mask / stop letter at a care position; hashed seeds: none anywhere in the window, or seed_key_hashed decides
+			bool ok = inside && ((bad >> i) & (HASHED ? span : care)) == 0;
+			if (HASHED && inside && !ok) ok = seed_key_hashed(a.params, sid, a.qseed + p0 + i, seed);
+			uint32_t k = none;
+			if (ok) {
+				if (HASHED && !seed_is_complex(a.params, sid, a.qseed + p0 + i)) {
+					const uint8_t t = (uint8_t)(sid * a.params.index_chunks);
+					if (t < a.mask_time[p0 + i]) a.mask_time[p0 + i] = t;
+				}
+				else k = a.order(seed_hash_a(seed), seed) >> (32 - a.slot_bits);
+			}
+			s_top[threadIdx.x * 17 + i] = k;
+			s_key[threadIdx.x * 17 + i] = seed;
+		}
+	}
+	__syncthreads();
+#pragma unroll 4
+	for (int r = 0; r < 16; ++r) {
+		const int e = r * 256 + threadIdx.x;                             // the workgroup's e-th position
+		const int64_t p = wg_base + e;
+		if (p < a.q_begin || p >= a.q_end) continue;
+		skey[p - a.q_begin] = s_top[e + (e >> 4)];
+		keys[p - a.q_begin] = s_key[e + (e >> 4)];
+	}
+}
 
 // After the stable sort by t (positions ascending within a run of equal t): a run holds the positions of every key whose t it is,
 // interleaved. Its first thread regroups them in place into one position-ascending list per key, the keys in the order of their
@@ -409,11 +477,6 @@ __device__ __forceinline__ int window_identity(const uint32_t* a, const uint32_t
 // per-position byte loads, no polynomial. A 2^k-bit Bloom-style bitmap of the query seeds (built by seed_index_kernel, resident
 // in every XCD's L2) rejects most reference seeds before the open-addressing table in HBM/Infinity Cache is touched.
 // Preconditions (checked by the host): shape length <= 16, reduction size <= 15.
-__device__ __forceinline__ uint32_t reduce4(uint32_t letter, uint64_t map_lo, uint64_t map_hi)
-{
-	const uint64_t m = (letter & 16) ? map_hi : map_lo;
-	return (uint32_t)(m >> ((letter & 15) * 4)) & 15u;
-}
 // LEVEL2: consult the level-2 bitmap before the table. It pays when most level-1 positives are false (long seeds: --fast,
 // default); with short seeds (weight <= 9: a third of the reference positions really join) it is a wasted random access.
 // HASHED: seeds of the query-indexed algorithm (seed_key_hashed, seed_core.h). A window made of amino acids only has the same
@@ -1646,7 +1709,16 @@ hipError_t launch_seed_build(const SeedArgs& a, int sid, uint32_t* qlist, uint32
 	uint32_t* ctr = work + 2 * n;
 	uint32_t* wrap = work + 2 * n + 64;
 	uint64_t* keys = reinterpret_cast<uint64_t*>(work + ((3 * n + 65) & ~(int64_t)1));
-	hipLaunchKernelGGL(seed_order_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, st, a, sid, skey, keys, ctr);
+	if (seed_nibble_mode(a.params, sid)) {
+		uint64_t lo, hi, care64 = 0;
+		seed_class_maps(a.params, lo, hi);
+		for (int k = 0; k < a.params.shape_weight[sid]; ++k) care64 |= (uint64_t)15 << (4 * a.params.shape_pos[sid][k]);
+		const int64_t base = a.q_begin & ~(int64_t)15;
+		const dim3 grid(blocks_for(a.q_end - base, 4096));
+		if (a.params.seed_encoding == SEED_HASHED) hipLaunchKernelGGL(seed_order16_kernel<true>, grid, dim3(256), 0, st, a, sid, lo, hi, base, care64, skey, keys, ctr);
+		else hipLaunchKernelGGL(seed_order16_kernel<false>, grid, dim3(256), 0, st, a, sid, lo, hi, base, care64, skey, keys, ctr);
+	}
+	else hipLaunchKernelGGL(seed_order_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, st, a, sid, skey, keys, ctr);
 	// the sentinel 1 << slot_bits must sort last: slot_bits + 1 key bits (C2: 24 = three radix passes)
 	const unsigned end_bit = (unsigned)(a.slot_bits + 1);
 	rocprim::counting_iterator<uint32_t> iota(0);
@@ -1790,6 +1862,14 @@ hipError_t launch_seed_count_pairs(const SeedArgs& a, int64_t n_matched, unsigne
 	return hipGetLastError();
 }
 
+// the left-most kernel with the 4-bit class maps of the letters; reductions with more than 15 classes keep the byte-wise windows
+static void launch_leftmost(const SeedArgs& a, int sid, dim3 grid, hipStream_t st)
+{
+	uint64_t lo, hi;
+	seed_class_maps(a.params, lo, hi);
+	hipLaunchKernelGGL(seed_leftmost_kernel, grid, dim3(256), 0, st, a, sid, lo, hi, a.params.reduction_size <= 15 ? 1 : 0);
+}
+
 hipError_t launch_seed_post(const SeedArgs& a, int sid, int64_t n_survivors, hipStream_t st, bool clear_scored)
 {
 	if (n_survivors == 0) return hipSuccess;
@@ -1798,14 +1878,7 @@ hipError_t launch_seed_post(const SeedArgs& a, int sid, int64_t n_survivors, hip
 		if (e != hipSuccess) return e;
 	}
 	hipLaunchKernelGGL(seed_score_kernel<false>, dim3(blocks_for(n_survivors, POST_THREADS)), dim3(POST_THREADS), 0, st, a, sid, n_survivors, SeedChain{});
-	// 4-bit class map of the letters (as launch_seed_stream builds it); reductions with more than 15 classes keep the byte-wise windows
-	uint64_t lo = 0, hi = 0;
-	const SeedParams& c = a.params;
-	for (int l = 0; l < 32; ++l) {
-		const uint64_t code = c.reduction[l] == L_MASK ? 15u : (uint64_t)(c.reduction[l] & 15);
-		(l < 16 ? lo : hi) |= code << ((l & 15) * 4);
-	}
-	hipLaunchKernelGGL(seed_leftmost_kernel, dim3(std::min<unsigned>(blocks_for(n_survivors, 256), 256 * 16)), dim3(256), 0, st, a, sid, lo, hi, c.reduction_size <= 15 ? 1 : 0);
+	launch_leftmost(a, sid, dim3(std::min<unsigned>(blocks_for(n_survivors, 256), 256 * 16)), st);
 	return hipGetLastError();
 }
 
@@ -2032,13 +2105,7 @@ hipError_t launch_seed_chain_shape(const SeedArgs& a, const SeedChain& ch, int s
 	hipLaunchKernelGGL(seed_pair_kernel<true>, dim3(CHAIN_GRID), dim3(128), 0, st, a, sid, (int64_t)0, ch);
 	hipLaunchKernelGGL(seed_score_kernel<true>, dim3(CHAIN_GRID / 2), dim3(POST_THREADS), 0, st, a, sid, (int64_t)0, ch);
 	// (a voided shape leaves the scored count zero: the left-most kernel reads it and leaves)
-	uint64_t lo = 0, hi = 0;
-	const SeedParams& c = a.params;
-	for (int l = 0; l < 32; ++l) {
-		const uint64_t code = c.reduction[l] == L_MASK ? 15u : (uint64_t)(c.reduction[l] & 15);
-		(l < 16 ? lo : hi) |= code << ((l & 15) * 4);
-	}
-	hipLaunchKernelGGL(seed_leftmost_kernel, dim3(CHAIN_GRID / 2), dim3(256), 0, st, a, sid, lo, hi, c.reduction_size <= 15 ? 1 : 0);
+	launch_leftmost(a, sid, dim3(CHAIN_GRID / 2), st);
 	hipLaunchKernelGGL(seed_chain_shape_done_kernel, dim3(1), dim3(64), 0, st, ch, sid);
 	return hipGetLastError();
 }

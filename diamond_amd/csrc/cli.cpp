@@ -1296,6 +1296,10 @@ int run_blastp(const Options& o)
 						h.query = (uint32_t)(qi * C + e.context); h.seed_offset = 0; h.subject = rb.limits[local]; h.score = e.score;
 						hits.push_back(h);
 					}
+				// The table holds a query's entries in rank order; the device planner takes a call's hits in (block sequence, location)
+				// order, as the seed stage leaves them (a read's six contexts one after the other). load_hits sorts a query's hits by
+				// location anyway and the one ranking chunk of this pass holds them all: the order changes nothing that is printed.
+				std::stable_sort(hits.begin(), hits.end(), [](const dmnd_seed_hit& a, const dmnd_seed_hit& b) { return a.query < b.query || (a.query == b.query && a.subject < b.subject); });
 				const int64_t n_hits = (int64_t)hits.size();
 				if (o.no_self_hits) {
 					if (blastx) throw std::runtime_error("--no-self-hits is not supported for blastx");

@@ -22,6 +22,8 @@ struct DeviceCfg {
 	FilterCfg filters;                   // --id, --approx-id, --query-cover, --subject-cover (filter_core.h)
 	double top = -1.0;                   // --top: >= 0 = the targets within this percentage of the best bit score, -k plays no part
 	int contexts = 1;                    // 6: translated queries -- the planner groups per read, the records carry the winning frame
+	bool ext_full = false;               // Extension::Mode::FULL: one full-matrix DpTarget per (context, target) unit with a hit (plan_full_kernel); max_swipe_dp is held against query length x target length
+	int global_ranking = 0;              // > 0: the final pass of --global-ranking -- one hit per ranked target, at most this many per query, ONE ranking chunk of that size (extend.cpp:80)
 };
 
 // What the device planner hands over (page-locked host copies of its lists; valid until the context's next dmnd_extend)
@@ -37,8 +39,8 @@ struct DevPlan {
 	PlanArgs dev;                             // the same lists (and the planner's inputs) where they lie in HBM
 };
 
-// Runs the planner over the call's hits (in c->xd_hits, with their x-drop extensions in c->xd_out and -- gf_on -- their gapped
-// filter flags in c->gf_flags), waits for it and leaves its lists in HBM. planned = false: the hits are not in
+// Runs the planner over the call's hits (in c->xd_hits, with their x-drop extensions in c->xd_out -- not read in Mode::FULL -- and
+// -- gf_on -- their gapped filter flags in c->gf_flags), waits for it and leaves its lists in HBM. planned = false: the hits are not in
 // (query, location, seed offset) order, the host has to plan.
 int plan_on_device(dmnd_ctx* c, const DeviceCfg& h, int64_t n_hits, bool gf_on, DevPlan& plan, bool& planned);
 // The planner's lists on the host (page-locked copies, valid until the context's next dmnd_extend): only the host path reads them

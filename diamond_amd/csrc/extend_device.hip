@@ -137,7 +137,8 @@ int dmnd::plan_on_device(dmnd_ctx* c, const DeviceCfg& h, int64_t n_hits, bool g
 	a.matrix = c->matrix.as<int8_t>();
 	a.hits = c->xd_hits.as<dmnd_seed_hit>(); a.n_hits = n_hits;
 	a.gf_flags = gf_on ? c->gf_flags.as<uint8_t>() : nullptr;
-	a.xd = c->xd_out.as<XdropSeg>();
+	a.xd = h.ext_full ? nullptr : c->xd_out.as<XdropSeg>();      // (Mode::FULL has no x-drop stage: plan_full_kernel)
+	a.ext_full = h.ext_full ? 1 : 0;
 	a.gap_open = h.gap_open; a.gap_extend = h.gap_extend; a.band_fast = h.band_mode_fast;
 	a.small_segs = n_hits >= plan_small_hits() ? 4 : 0;
 	a.tgt = reinterpret_cast<uint32_t*>(d + o_tgt); a.heads = reinterpret_cast<uint64_t*>(d + o_heads); a.head_scan = reinterpret_cast<uint64_t*>(d + o_scan);
@@ -285,6 +286,7 @@ int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan,
 	a.hits = plan.dev.hits; a.qlimits = plan.dev.qlimits; a.tlimits = plan.dev.tlimits;
 	a.contexts = h.contexts; a.band_query = plan.dev.band_query; a.ungapped0 = plan.dev.ungapped0;
 	a.source_lens = read_lens ? c->ext_source_lens.as<int32_t>() : nullptr;
+	a.ext_full = h.ext_full ? 1 : 0;
 	a.use_cbs = h.use_cbs ? 1 : 0; a.row_min_items = (uint32_t)std::min<int64_t>(sweep_rows_min_items(), 0xffffffffll); a.chunk_size = (uint32_t)chunk; a.k = h.max_target_seqs; a.max_swipe_dp = h.max_swipe_dp;
 	const Evaluer& E = c->evaluer;
 	a.min_bit_score = h.min_bit_score; a.filt = h.filters; a.filt_on = filt ? 1 : 0;

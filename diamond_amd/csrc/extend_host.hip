@@ -1,10 +1,11 @@
 // extend_host.hip -- the extension stage above the GPU Smith-Waterman: what Extension::extend does per query
 // (/root/reference/src/align/extend.cpp:226-420), re-organised for the GPU as block-wide batches.
-// Since round 6 dmnd_extend has TWO halves behind one entry. The default protein search (one query context, one HSP per target,
-// -k culling by e-value or --top, Hauser bias or none, banded extension, with or without a transcript arena) is planned (plan_kernels.hip) and extended
+// Since round 6 dmnd_extend has TWO halves behind one entry. A search with one HSP per target (one query context or six,
+// -k culling by e-value or --top, Hauser bias or none, banded extension or full matrices -- --ext full, the final pass of
+// --global-ranking --, with or without HSP filters and a transcript arena) is planned (plan_kernels.hip) and extended
 // (extend_kernels.hip; extend_device.hip drives it) entirely in HBM: the host reads a few counters per ranking iteration, writes
 // its own e-value and bit score into the records and leaves them on the device for the join (with a transcript arena: copies the
-// gathered transcripts into its front instead; the host path fills the rest). Every other mode, and the queries the
+// gathered transcripts into its front instead; the host path fills the rest). Every other mode (-F, --max-hsps != 1, matrix adjustment), and the queries the
 // device half hands back, take the HOST PATH described next (extend_range) -- same records either way; the two outputs are merged by query.
 // The host path: the queries with seed hits go through
 //   prelude     :  Hauser bias of the whole query block                              (GPU, bias_kernels.hip; once per call)
@@ -172,6 +173,10 @@ DeviceCfg device_cfg(const HostCfg& h)      // what the device half reads of the
 	d.max_swipe_dp = h.max_swipe_dp; d.use_cbs = h.use_cbs; d.max_evalue = h.max_evalue; d.min_bit_score = h.min_bit_score;
 	d.filters.min_id = h.min_id; d.filters.approx_id = h.approx_id; d.filters.query_cover = h.query_cover; d.filters.subject_cover = h.subject_cover;
 	d.contexts = h.contexts;
+	d.ext_full = h.ext_full; d.global_ranking = h.global_ranking;
+	// the final pass of the global ranking: one chunk holds all ranked targets of a query (extend.cpp:80; rank_groups below) -- the
+	// table is cut at global_ranking entries per query, so a chunk of that size holds every query's groups
+	if (h.global_ranking > 0) d.ranking_chunk = h.global_ranking;
 	return d;
 }
 
@@ -1298,8 +1303,9 @@ struct ExtendFront {
 };
 // plan_translated: a call of six query contexts is planned on the device too (per read, plan_kernels.hip) -- asked for where the
 // device half will extend it (device_takes below) and by dmnd_extend_plan_device; otherwise the host plans it as ever.
+// plan_full: the same for a call in Mode::FULL.
 template<typename Lap>
-int extend_front(dmnd_ctx* c, const HostCfg& h, const dmnd_seed_hit* hits, int64_t n_hits, size_t n_queries, Lap lap, TraceLaps& trp, ExtendFront& f, bool plan_translated)
+int extend_front(dmnd_ctx* c, const HostCfg& h, const dmnd_seed_hit* hits, int64_t n_hits, size_t n_queries, Lap lap, TraceLaps& trp, ExtendFront& f, bool plan_translated, bool plan_full)
 {
 	const std::vector<int64_t>& ql = c->limits[DMND_QUERY];
 	f.cbs = nullptr;
@@ -1310,7 +1316,8 @@ int extend_front(dmnd_ctx* c, const HostCfg& h, const dmnd_seed_hit* hits, int64
 	}
 	else {
 		HIP_TRY(hipSetDevice(c->device));
-		const bool host_walks = !(xdrop_gpu && !h.ext_full && n_hits > 0);
+		// (Mode::FULL walks no letters on the host at all: no copy)
+		const bool host_walks = !h.ext_full && !(xdrop_gpu && n_hits > 0);
 		if (c->cbs.cap < (size_t)ql.back() + 256) c->cbs_generation = ~(uint64_t)0;      // (the buffer is about to be replaced)
 		if (int rc = c->cbs.ensure((size_t)ql.back() + 256)) return rc;
 		if (host_walks && c->pinned_cbs_cap < (size_t)ql.back() + 64) {
@@ -1358,9 +1365,17 @@ int extend_front(dmnd_ctx* c, const HostCfg& h, const dmnd_seed_hit* hits, int64
 		f.xd = reinterpret_cast<const XdropSeg*>(1);          // (set below, once it is known whether the host needs the copy)
 	}
 	lap(4, 1);
-	// The groups, segments, chains and bands of every (query, target) pair on the device (plan_kernels.hip; banded extension; six
+	// The groups, segments, chains and bands of every (query, target) pair on the device (plan_kernels.hip; banded extension, or one full-matrix band per group in Mode::FULL; six
 	// query contexts: per (read, target) pair). DMND_EXTEND_PLAN_GPU=0: the host plans, as up to round 5.
-	f.try_plan = env_plan_gpu() && f.xd && (h.contexts == 1 || plan_translated) && n_hits < ((int64_t)1 << 31);
+	// Mode::FULL (--ext full, the final pass of --global-ranking) has no x-drop stage: the planner (plan_full_kernel) reads the hits
+	// alone, which go to HBM here -- only for a call the device half will extend (plan_full), the host plans such a call without them.
+	f.try_plan = env_plan_gpu() && (f.xd || (h.ext_full && plan_full && n_hits > 0)) && (h.contexts == 1 || plan_translated) && n_hits < ((int64_t)1 << 31);
+	if (f.try_plan && !f.xd) {
+		HIP_TRY(hipSetDevice(c->device));
+		if (int rc = c->xd_hits.ensure((size_t)n_hits * sizeof(dmnd_seed_hit))) return rc;
+		HIP_TRY(hipMemcpyAsync(c->xd_hits.p, hits, (size_t)n_hits * sizeof(dmnd_seed_hit), hipMemcpyHostToDevice, c->stream));
+		f.bias_pending = true;
+	}
 	// 1b. gapped filter of every seed hit in one launch (only --sensitive and above; extend.cpp:205-213)
 	f.gf.clear();
 	c->gf_ms = 0;
@@ -1445,15 +1460,16 @@ extern "C" int dmnd_extend(dmnd_ctx* c, const int8_t* qdata, const int8_t* tdata
 	// DMND_EXTEND_DEVICE=0: all queries on the host path, as up to round 5. Read per call, like the hooks of extend_device.hip
 	// (DESIGN.md 9): a test compares the two paths in one process.
 	const bool ext_gpu = [] { const char* e = std::getenv("DMND_EXTEND_DEVICE"); return !e || e[0] != '0'; }();
-	// what the device half extends: one HSP per target, Hauser bias or none, banded extension, -k or --top, one query context or six
-	// (blastx). With six contexts and the HSP filters the query cover is measured on the DNA read: such a call is taken when the context
+	// what the device half extends: one HSP per target, Hauser bias or none, banded or full-matrix extension (--ext full; the final pass
+	// of --global-ranking, whose one ranking chunk per query extend_on_device accepts up to EXT_MAX_CHUNK), -k or --top, one query context
+	// or six (blastx). With six contexts and the HSP filters the query cover is measured on the DNA read: such a call is taken when the context
 	// holds the block's read lengths (dmnd_set_query_source_lengths; the device half copies them to HBM), and stays on the host path as a
 	// whole without them -- there every cover is measured against 1 (--query-cover itself is refused by extend_cfg)
 	const bool have_read_lens = c->source_lens.size() == (ql.size() - 1) / (size_t)h.contexts;
-	const bool device_takes = ext_gpu && h.max_hsps == 1 && !cbs_matrix_adjust(h.cbs_mode) && !h.ext_full
-		&& h.global_ranking == 0 && !c->same_title && h.max_target_seqs > 0 && (h.contexts == 1 || !h.have_filters() || have_read_lens);
+	const bool device_takes = ext_gpu && h.max_hsps == 1 && !cbs_matrix_adjust(h.cbs_mode)
+		&& !c->same_title && h.max_target_seqs > 0 && (h.contexts == 1 || !h.have_filters() || have_read_lens);
 	ExtendFront f;
-	if (int rc = extend_front(c, h, hits, n_hits, qr.size(), lap, trp, f, device_takes)) return rc;
+	if (int rc = extend_front(c, h, hits, n_hits, qr.size(), lap, trp, f, device_takes, device_takes)) return rc;
 	const int8_t* const cbs = f.cbs;
 	bool bias_pending = f.bias_pending;
 	const XdropSeg* xd = f.xd;
@@ -1473,8 +1489,8 @@ extern "C" int dmnd_extend(dmnd_ctx* c, const int8_t* qdata, const int8_t* tdata
 	// The queries are extended in HBM from here on (extend_kernels.hip), ranking chunk by ranking chunk: the default search of a
 	// protein or translated query block -- one HSP per target, -k culling by e-value or --top culling by score, Hauser bias or none,
 	// with or without the HSP filters (translated: with the block's read lengths), with or without a transcript arena (its transcripts
-	// come first in the arena). The queries the device half hands back, and every query of any other mode (-F, --max-hsps != 1,
-	// --ext full, --global-ranking, matrix adjustment), take the host path below.
+	// come first in the arena), banded or -- --ext full, the final pass of --global-ranking -- over the whole matrix. The queries the
+	// device half hands back, and every query of any other mode (-F, --max-hsps != 1, matrix adjustment), take the host path below.
 	c->ext_records_dev = nullptr; c->ext_records_n = -1;
 	std::vector<dmnd_match> dev_records;
 	std::vector<Range> qr_host;
@@ -1499,15 +1515,18 @@ extern "C" int dmnd_extend(dmnd_ctx* c, const int8_t* qdata, const int8_t* tdata
 	const std::vector<Range>& qr_run = on_device ? qr_host : qr_all;
 	if (planned && !tr_planned && !qr_run.empty()) { if (int rc = plan_fetch_lists(c, plan)) return rc; bias_pending = false; }
 	if (tr_planned && !qr_run.empty()) {
-		if (int rc = c->xd_host.ensure((size_t)n_hits * sizeof(XdropSeg))) return rc;
-		HIP_TRY(hipMemcpyAsync(c->xd_host.p, c->xd_out.p, (size_t)n_hits * sizeof(XdropSeg), hipMemcpyDeviceToHost, c->stream));
+		// (Mode::FULL: there are no x-drop results, and the host's plan of such a read reads none)
+		if (f.xd) {
+			if (int rc = c->xd_host.ensure((size_t)n_hits * sizeof(XdropSeg))) return rc;
+			HIP_TRY(hipMemcpyAsync(c->xd_host.p, c->xd_out.p, (size_t)n_hits * sizeof(XdropSeg), hipMemcpyDeviceToHost, c->stream));
+		}
 		if (f.gf_on) {
 			f.gf.resize((size_t)n_hits);
 			HIP_TRY(hipMemcpyAsync(f.gf.data(), c->gf_flags.p, (size_t)n_hits, hipMemcpyDeviceToHost, c->stream));
 		}
 		HIP_TRY(sync_stream(c->stream));
 		bias_pending = false;
-		xd = c->xd_host.as<XdropSeg>();                      // (taken once the buffer exists: ensure() may have allocated or replaced it)
+		if (f.xd) xd = c->xd_host.as<XdropSeg>();            // (taken once the buffer exists: ensure() may have allocated or replaced it)
 	}
 	const uint32_t* pq_index = on_device ? pq_host.data() : nullptr;
 	double dev_stats[12];
@@ -1940,9 +1959,9 @@ extern "C" int dmnd_extend_plan_device(dmnd_ctx* c, const dmnd_seed_hit* hits, i
 	TraceLaps trp("dmnd_extend_plan_device");
 	const std::vector<Range> qr = split_by_query(hits, n_hits, h.contexts);
 	ExtendFront f;
-	if (int rc = extend_front(c, h, hits, n_hits, qr.size(), [](int, int = -1) {}, trp, f, true)) return rc;
+	if (int rc = extend_front(c, h, hits, n_hits, qr.size(), [](int, int = -1) {}, trp, f, true, true)) return rc;
 	if (f.bias_pending) HIP_TRY(sync_stream(c->stream));
-	if (n_hits > 0 && !f.try_plan) return fail(DMND_E_ARG, "dmnd_extend_plan_device: this configuration is planned by the host (--ext full, DMND_EXTEND_PLAN_GPU=0 or DMND_EXTEND_XDROP_GPU=0)");
+	if (n_hits > 0 && !f.try_plan) return fail(DMND_E_ARG, "dmnd_extend_plan_device: this configuration is planned by the host (DMND_EXTEND_PLAN_GPU=0 or DMND_EXTEND_XDROP_GPU=0)");
 	info->unsorted = f.plan.unsorted ? 1 : 0;
 	if (!f.planned) return DMND_OK;
 	DevPlan& plan = f.plan;

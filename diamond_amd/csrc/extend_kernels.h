@@ -15,6 +15,9 @@
 // target exactly; next to the underflow two tiny values are always flagged). The records leave with the device value; the host overwrites
 // it with its own (and the bit score) and checks the order. Queries with a group the planner left to the host, with an item the
 // traceback path cannot take or with more than EXT_MAX_GROUPS groups stay on the host path (extend_host.hip extend_range).
+// The bands are the planner's: chained and merged ones of a banded search, or -- Extension::Mode::FULL: --ext full, the final pass of
+// --global-ranking -- one band over the whole matrix per target and context with a seed hit; there an item is held against max_swipe_dp
+// with query length x target length (ExtArgs::ext_full), everything behind ext_mark_kernel is the same.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -50,6 +53,7 @@ struct ExtArgs {
 	uint32_t chunk_size;           // ranking_chunk_size
 	int k;                         // max_target_seqs
 	int64_t max_swipe_dp;
+	int ext_full;                  // Extension::Mode::FULL: max_swipe_dp is held against query length x target length (plan_core.h full_matrix_dp_size)
 	ExtEvalue ev;
 	double min_bit_score;          // --min-score: != 0 replaces the e-value cutoff (ScoreMatrix::report_cutoff)
 	FilterCfg filt; int filt_on;   // the HSP filters (filter_core.h); filt_on: the filter arrays exist (without top_on: the call runs the filtered ranking loop, the f-kernels)

@@ -72,6 +72,14 @@ __device__ inline int64_t ext_cells(const dmnd_dp_target& d)       // DpTarget::
 	return (int64_t)(j1 - pos) * (int64_t)(d.d_end - d.d_begin);
 }
 
+// What config.max_swipe_dp is held against: the band's columns x width, or -- Mode::FULL, DP::Flags::FULL_MATRIX -- the whole matrix
+// (dp/dp.h:121-124; extend_host.hip dp_size). The counters (cells1, cells2, the roofline statistics) count ext_cells in both modes, as
+// the host path's do: the cells the band sweeps compute, corners outside the matrix included.
+__device__ inline int64_t ext_dp_size(const ExtArgs& a, const dmnd_dp_target& d)
+{
+	return a.ext_full ? full_matrix_dp_size(d.query_len, d.target_len) : ext_cells(d);
+}
+
 // bit score of a raw score (Evaluer::bitscore, evalue.h): plain double arithmetic, no library function -- the host's value bit for bit
 __device__ inline double ext_bitscore(const ExtEvalue& p, int raw_score) { return (p.lambda * (double)raw_score - p.ln_k) / 0.69314718055994530941723212145818; }
 
@@ -112,7 +120,7 @@ __global__ __launch_bounds__(64) void ext_mark_kernel(ExtArgs a)
 				int qlen = qlen1;
 				if (a.band_query) { const uint32_t bq = a.band_query[grp.band_begin + k]; qlen = (int)(a.qlimits[bq + 1] - a.qlimits[bq] - 1); }
 				const dmnd_dp_target d{ 0, 0, 0, qlen, tlen, b.d_begin, b.d_end };
-				if (qlen <= 0 || band <= 0 || band_class(band) > 32 || ext_cells(d) > a.max_swipe_dp) bad = true;
+				if (qlen <= 0 || band <= 0 || band_class(band) > 32 || ext_dp_size(a, d) > a.max_swipe_dp) bad = true;
 			}
 		}
 	const bool ok = __ballot(bad) == 0;

@@ -4,7 +4,9 @@
 // align/gapped_score.cpp:107-180), done for ALL seed hits of a block pair in a handful of launches: the hits are grouped by
 // (query, target), every group's hits become diagonal segments (from the x-drop kernel's results), the segments are chained
 // (chain_graph.h, the same source the host compiles) and the chains' bands merged into the DpTargets of round 1.
-// The host keeps the ranking logic (which groups of a query are extended when) and only looks bands up.
+// Extension::Mode::FULL (--ext full, the final pass of --global-ranking; PlanArgs::ext_full): behind the grouping every group gets one
+// band over its whole matrix (plan_full_kernel; align/ungapped.cpp:70-75, gapped_score.cpp:123-130) -- no x-drop results, segments or chains.
+// The host path, for the queries that take it, keeps the ranking logic (which groups of a query are extended when) and only looks bands up.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -44,6 +46,7 @@ struct PlanArgs {
 	const XdropSeg* xd;            // x-drop extension of every hit (xdrop_seg_kernel)
 	int gap_open, gap_extend, band_fast;
 	int small_segs;                // groups with at most this many segments are chained with the small workspace (0: none; plan_kernels.hip)
+	int ext_full;                  // Extension::Mode::FULL: every group gets one band, the whole matrix (plan_full_kernel); xd is not read
 	// work and output arrays, all in HBM, sized for n_hits entries (+ 1 where a sentinel follows)
 	uint32_t* tgt;                 // target of every hit
 	uint64_t* heads;               // group head flag | query head flag << 32, then their inclusive scan

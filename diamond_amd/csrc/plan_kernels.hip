@@ -17,6 +17,9 @@
 //   plan_segments_kernel per group: score, filter flag, sorted segments; single-segment groups are finished here
 //   plan_chain_list_kernel, plan_chain_kernel<small> / <large>    per multi-segment group: chaining + band merge
 //   rocPRIM exclusive scan of the band counts, plan_gather_kernel: dense band list
+// Extension::Mode::FULL (PlanArgs::ext_full: --ext full, the final pass of --global-ranking) stops behind plan_fill_kernel and runs
+//   plan_full_kernel     per group: score, filter flag, ONE band over the whole matrix at the group's own place in the dense list
+// (six contexts: plan_pairs_kernel behind it, as below); no x-drop results are read.
 // Translated queries (PlanArgs::contexts = 6) arrive context after context and are grouped per READ (load_hits.h:44-127 over the six
 // frames). In front of the kernels above: plan_key_kernel (target, order check, sort key of every hit), a stable rocPRIM radix sort by
 // (read, target), plan_permute_kernel (hits, x-drop results and filter flags in the new order; unit / pair / read head flags). Groups
@@ -77,7 +80,7 @@ __global__ __launch_bounds__(256) void plan_permute_kernel(PlanArgs a)
 	const dmnd_seed_hit h = a.hits_in[src];
 	const uint64_t key = a.keys_sorted[k];
 	a.hits_sorted[k] = h;
-	a.xd_sorted[k] = a.xd_in[src];
+	if (a.xd_in) a.xd_sorted[k] = a.xd_in[src];              // (NULL in Mode::FULL: no x-drop stage)
 	if (a.gf_in) a.gf_sorted[k] = a.gf_in[src];
 	a.tgt[k] = plan_key_target(key, a.target_bits);
 	uint64_t gh = 1, qh = 1, ph = 1;
@@ -388,21 +391,51 @@ __global__ __launch_bounds__(256) void plan_pairs_kernel(PlanArgs a)
 	pr.n_hits = a.pairs[p + 1].hit_begin - pr.hit_begin;
 	pr.band_begin = first.band_begin;
 	pr.pass = first.pass;
-	uint32_t n_bands = 0;
-	int score = 0, ungapped0 = 0;
-	bool on_host = false;
+	PairSum s = pair_sum_begin();                                    // (plan_core.h)
 	for (uint32_t u = u0; u < u1; ++u) {
 		const PlanGroup g = a.groups[u];
-		score = chain_max(score, (int)g.score);
-		if (a.hits[g.hit_begin].query % (uint32_t)a.contexts == 0) ungapped0 = g.score;
-		if (g.n_bands == PLAN_ON_HOST) on_host = true; else n_bands += g.n_bands;
+		pair_sum_add(s, (int)g.score, a.hits[g.hit_begin].query % (uint32_t)a.contexts, g.n_bands, g.n_bands == PLAN_ON_HOST);
 	}
-	if (n_bands >= PLAN_NEED_CHAIN) on_host = true;
-	pr.score = (uint16_t)score;
-	pr.n_bands = on_host ? (uint8_t)PLAN_ON_HOST : (uint8_t)n_bands;
+	pair_sum_end(s, PLAN_NEED_CHAIN);
+	pr.score = (uint16_t)s.score;
+	pr.n_bands = s.on_host ? (uint8_t)PLAN_ON_HOST : (uint8_t)s.n_bands;
 	a.pairs[p] = pr;
-	a.ungapped0[p] = (uint16_t)ungapped0;
-	if (on_host) atomicAdd(&a.counters->n_pairs_on_host, 1u);
+	a.ungapped0[p] = (uint16_t)s.ungapped0;
+	if (s.on_host) atomicAdd(&a.counters->n_pairs_on_host, 1u);
+}
+
+// Extension::Mode::FULL (PlanArgs::ext_full; --ext full and the final pass of --global-ranking): no segments, no chaining, no band
+// merge. One thread per group -- with six contexts per (context, target) unit, and only the frames of a pair that have a hit are units
+// at all -- writes the group's record and its ONE band, the whole matrix (plan_core.h full_matrix_band), straight into the dense band
+// list at the group's own index: band_begin = group number, no count, no scan, no gather. The pass flag is what the gapped filter left
+// (of the pair for six contexts, as in plan_segments_kernel; the final pass of the global ranking runs without the filter). No group
+// is left to the host. plan_pairs_kernel behind it sums a pair's units up as for banded targets.
+__global__ __launch_bounds__(256) void plan_full_kernel(PlanArgs a)
+{
+	const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+	const uint32_t G = a.counters->n_groups;
+	if (g >= G) return;
+	if (g == 0) a.counters->n_bands = G;
+	PlanGroup grp = a.groups[g];
+	const uint32_t b = grp.hit_begin, e = a.groups[g + 1].hit_begin;
+	int score = 0;
+	bool pass = a.gf_flags == nullptr;
+	for (uint32_t k = b; k < e; ++k) {
+		score = chain_max(score, (int)(uint16_t)a.hits[k].score);
+		if (a.gf_flags) pass |= a.gf_flags[k] != 0;
+	}
+	if (a.contexts > 1 && a.gf_flags) {
+		const uint32_t p = a.unit_pair[g], pb = a.pairs[p].hit_begin, pe = a.pairs[p + 1].hit_begin;
+		for (uint32_t k = pb; k < pe && !pass; ++k) pass = a.gf_flags[k] != 0;
+	}
+	const uint32_t query = a.hits[b].query;
+	const int qlen = (int)(a.qlimits[query + 1] - a.qlimits[query] - 1);
+	const int tlen = (int)(a.tlimits[grp.target + 1] - a.tlimits[grp.target] - 1);
+	const FullBand fb = full_matrix_band(qlen, tlen);
+	a.bands[g] = PlanBand{ fb.d_begin, fb.d_end };
+	if (a.band_query) a.band_query[g] = query;
+	grp.n_hits = e - b; grp.score = (uint16_t)score; grp.pass = pass ? 1 : 0; grp.band_begin = g; grp.n_bands = 1;
+	a.groups[g] = grp;
 }
 
 hipError_t ensure_tmp(void** tmp, size_t* have, size_t need)
@@ -421,7 +454,7 @@ void plan_kernel_table(const void** out, int* n)
 {
 	const void* k[] = { (const void*)plan_mark_kernel, (const void*)plan_fill_kernel, (const void*)plan_segments_kernel, (const void*)plan_chain_list_kernel,
 		(const void*)plan_chain_kernel<PLAN_SMALL_SEGS, 16, 4, true>, (const void*)plan_chain_kernel<PLAN_MAX_SEGS, 96, 16, false>, (const void*)plan_count_kernel, (const void*)plan_gather_kernel,
-		(const void*)plan_key_kernel, (const void*)plan_permute_kernel, (const void*)plan_pairs_kernel };
+		(const void*)plan_key_kernel, (const void*)plan_permute_kernel, (const void*)plan_pairs_kernel, (const void*)plan_full_kernel };
 	*n = (int)(sizeof(k) / sizeof(k[0]));
 	for (int i = 0; i < *n; ++i) out[i] = k[i];
 }
@@ -475,8 +508,14 @@ hipError_t launch_plan(const PlanArgs& a, hipStream_t st)
 	size_t need2 = 0;
 	hipError_t e = rocprim::exclusive_scan(nullptr, need2, a.band_count, a.band_off, 0u, n + 1, rocprim::plus<uint32_t>(), st);
 	if (e != hipSuccess) return e;
-	e = launch_plan_groups(a, st, need2);
+	e = launch_plan_groups(a, st, a.ext_full ? 0 : need2);
 	if (e != hipSuccess) return e;
+	if (a.ext_full) {
+		// Mode::FULL: one band per group, written where the group lies (plan_full_kernel)
+		hipLaunchKernelGGL(plan_full_kernel, dim3(b256), dim3(256), 0, st, a);
+		if (translated) hipLaunchKernelGGL(plan_pairs_kernel, dim3(b256), dim3(256), 0, st, a);
+		return hipGetLastError();
+	}
 	// groups <= hits: the per-group kernels are launched over the hit count and return beyond the group count (read on the device)
 	hipLaunchKernelGGL(plan_segments_kernel, dim3(b64), dim3(64), 0, st, a);
 	// (the chaining kernels are launched over the upper bound of one group per two hits -- a group that needs chaining has at least

@@ -13,6 +13,7 @@ LIB_PATH = os.path.join(_HERE, "libdiamond_hip.so")
 
 SWIPE_SCORE, SWIPE_COORDS, SWIPE_TRACEBACK, SWIPE_STATS = 0, 1, 2, 3
 QUERY, TARGET = 0, 1
+EXT_DEFAULT, EXT_BANDED_FAST, EXT_BANDED_SLOW, EXT_FULL = -1, 0, 1, 2      # dmnd_set_extension_mode (--ext): DMND_EXT_* of diamond_hip.h
 
 
 class DiamondHipError(RuntimeError):
@@ -1030,7 +1031,15 @@ class Context:
         self._check(self.lib.dmnd_rank_device_stats(self.h, st))
         return [float(x) for x in st]
 
+    def set_extension_mode(self, mode):
+        """--ext: EXT_BANDED_FAST, EXT_BANDED_SLOW or EXT_FULL (one DpTarget over the whole matrix per target and context with a seed
+        hit, no chaining); EXT_DEFAULT: the band mode of the context's sensitivity. The final pass of a --global-ranking search
+        (set_global_ranking) needs EXT_FULL."""
+        self.lib.dmnd_set_extension_mode.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        self._check(self.lib.dmnd_set_extension_mode(self.h, int(mode)))
+
     def set_global_ranking(self, n):
+        self.lib.dmnd_set_global_ranking.argtypes = [ctypes.c_void_p, ctypes.c_int]
         self._check(self.lib.dmnd_set_global_ranking(self.h, int(n)))
 
     def set_max_hsps(self, n):

@@ -7,6 +7,8 @@ warm-up steps, `--repeats` times; beside them the device half's counters and the
   python tools/top_step.py --blastx --top -1 [--id 50 --query-cover 50]
                                                          the C4 workload instead (bench.py's: the first 5 000 queries back-translated into
                                                          DNA reads, six contexts, default sensitivity, read lengths set), with HSP filters
+  python tools/top_step.py --ext full -k 25          the same step over the whole matrix of every target with a seed hit (--ext full;
+  python tools/top_step.py --ext full --top 10        -k N implies --top -1), for DESIGN.md 5.0-full
 The seed stage runs once, outside the timed region: every step extends the same seed hits."""
 import argparse
 import hashlib
@@ -34,7 +36,11 @@ def main():
     ap.add_argument("--blastx", action="store_true")
     ap.add_argument("--id", type=float, default=0.0)
     ap.add_argument("--query-cover", type=float, default=0.0)
+    ap.add_argument("--ext", choices=["banded-fast", "banded-slow", "full"], default=None)
+    ap.add_argument("-k", "--max-target-seqs", type=int, default=None)
     args = ap.parse_args()
+    if args.max_target_seqs is not None:
+        args.top = -1.0
     if args.lib:
         hip.LIB_PATH = os.path.abspath(args.lib)
     db, doff, q, qoff = synth.generate(args.families, members=10, queries=args.queries, seed=20260923)
@@ -61,6 +67,10 @@ def main():
         ctx.set_gapped_filter(gf)
         ctx.set_filters(min_id=args.id, query_cover=args.query_cover)
         ctx.set_top_percent(args.top if args.top >= 0 else None)
+        if args.max_target_seqs is not None:
+            ctx.set_max_target_seqs(args.max_target_seqs)
+        if args.ext:
+            ctx.set_extension_mode({"banded-fast": hip.EXT_BANDED_FAST, "banded-slow": hip.EXT_BANDED_SLOW, "full": hip.EXT_FULL}[args.ext])
         hits = ctx.seed_search(sp)
         reps, md5, n_records = [], None, 0
         for r in range(args.repeats):
@@ -74,13 +84,16 @@ def main():
                     cpu.append((c1 - c0) * 1e3)
             reps.append(dict(wall_ms_median=float(np.median(wall)), wall_ms_mean=float(np.mean(wall)), cpu_ms_mean=float(np.mean(cpu))))
             md5, n_records = hashlib.md5(m.tobytes()).hexdigest(), len(m)
-        dv = ctx.extend_device_stats()
+        dv, st = ctx.extend_device_stats(), ctx.extend_stats()
         w = [x["wall_ms_median"] for x in reps]
-        print(json.dumps(dict(top=args.top, blastx=args.blastx, id=args.id, query_cover=args.query_cover, lib=args.lib or "this build", seed_hits=int(len(hits)), records=n_records, records_md5=md5,
+        print(json.dumps(dict(top=args.top, ext=args.ext or "default", k=args.max_target_seqs, blastx=args.blastx, id=args.id, query_cover=args.query_cover, lib=args.lib or "this build", seed_hits=int(len(hits)), records=n_records, records_md5=md5,
                               wall_ms_median_of_repeats=float(np.median(w)), wall_ms_spread=float(max(w) - min(w)),
                               cpu_ms_median_of_repeats=float(np.median([x["cpu_ms_mean"] for x in reps])), repeats=reps,
                               device=dict(queries=dv["queries"], back_to_host=dv["queries_back_to_host"], capped=dv["queries_capped"],
-                                          records=dv["records"], records_filtered=dv["records_filtered"], on_filter_threshold=dv["queries_on_filter_threshold"]))))
+                                          records=dv["records"], items=dv["items"],
+                                          lane_use=dv["band_diagonal_steps"] / dv["wavefront_diagonal_steps"] if dv["wavefront_diagonal_steps"] else None,
+                                          round1_sweep_ms=st["round1_swipe_kernel_ms"], round2_sweep_ms=st["round2_swipe_kernel_ms"], walk_ms=st["traceback_kernel_ms"],
+                                          records_filtered=dv["records_filtered"], on_filter_threshold=dv["queries_on_filter_threshold"]))))
     finally:
         ctx.close()
 

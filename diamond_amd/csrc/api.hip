@@ -375,6 +375,7 @@ extern "C" void dmnd_destroy(dmnd_ctx* c)
 		&c->d_limits[0], &c->d_limits[1], &c->qid_of, &c->mask_time, &c->seed_keys, &c->seed_next, &c->seed_qlist, &c->seed_qkeys, &c->seed_slot2, &c->seed_loc2, &c->seed_survivors, &c->seed_scored, &c->seed_need, &c->seed_qfold, &c->seed_tfold, &c->seed_tcodes, &c->seed_tflags, &c->seed_tplanes, &c->seed_tclass,
 		&c->matched_slot, &c->matched_loc, &c->counters, &c->seed_hits, &c->seed_bitmap, &c->seed_deferred, &c->seed_eslot, &c->seed_eloc, &c->seed_hits_sorted, &c->seed_ret, &c->sort_keys[0], &c->sort_keys[1], &c->sort_idx[0], &c->sort_idx[1], &c->gf_tables, &c->gf_hits, &c->gf_flags, &c->gf_scores, &c->gf_units, &c->alt_targets, &c->mask_lr, &c->mask_pb, &c->mask_scale, &c->mask_pos, &c->mask_ids, &c->mask_soff, &c->mask_long_ids, &c->mask_long_soff, &c->mask_long_pb, &c->mask_long_scale, &c->soft[0], &c->soft[1], &c->motif_hit, &c->motif_table, &c->seg_tables, &c->seg_cls, &c->seg_work, &c->seg_handed, &c->seg_ranges, &c->adj_matrices, &c->join_keep, &c->join_pos, &c->join_in, &c->join_out, &c->join_recv })
 		b->release();
+	c->release_seed_ref();
 	if (c->ev0) (void)hipEventDestroy(c->ev0);
 	if (c->ev1) (void)hipEventDestroy(c->ev1);
 	if (c->ev2) (void)hipEventDestroy(c->ev2);
@@ -496,6 +497,8 @@ extern "C" int dmnd_share_block(dmnd_ctx* c, int which, const dmnd_ctx* src)
 	c->coarse[which] = src->coarse[which];
 	c->soft_valid[which] = false;
 	if (which == DMND_QUERY) { c->source_lens = src->source_lens; c->source_lens_generation = ~(uint64_t)0; ++c->query_generation; ++c->query_limits_version; }
+	else { ++c->target_generation; c->release_seed_ref(); }
+	c->seed_last_joined = -1;
 	return DMND_OK;
 }
 
@@ -510,7 +513,7 @@ extern "C" int dmnd_copy_block(dmnd_ctx* c, int which, const dmnd_ctx* src)
 	HIP_TRY(sync_stream(src->stream));                 // whatever wrote the source block has finished
 	HIP_TRY(hipMemcpyAsync(c->block[which].p, src->block[which].p, (size_t)c->block_len[which], hipMemcpyDeviceToDevice, c->stream));
 	c->soft_valid[which] = false;
-	if (which == DMND_QUERY) ++c->query_generation;
+	if (which == DMND_QUERY) ++c->query_generation; else ++c->target_generation;
 	return DMND_OK;
 }
 
@@ -547,6 +550,8 @@ extern "C" int dmnd_upload_block(dmnd_ctx* c, int which, const int8_t* data, int
 	c->block_len[which] = data_len;
 	c->soft_valid[which] = false;
 	if (which == DMND_QUERY) { c->source_lens.clear(); c->source_lens_generation = ~(uint64_t)0; ++c->query_generation; ++c->query_limits_version; }
+	else { ++c->target_generation; c->release_seed_ref(); }
+	c->seed_last_joined = -1;
 	c->limits[which].clear();
 	c->coarse[which].clear();
 	if (limits) {

@@ -214,7 +214,7 @@ extern "C" int dmnd_soft_mask_block(dmnd_ctx* c, int which, int64_t* n_covered)
 	if (!c->block[which].p || c->limits[which].size() < 2) return fail(DMND_E_ARG, "dmnd_soft_mask_block: block must be uploaded with limits");
 	if (n_covered) *n_covered = 0;
 	c->soft_valid[which] = false;
-	if (which == DMND_QUERY) ++c->query_generation;
+	if (which == DMND_QUERY) ++c->query_generation; else ++c->target_generation;
 	// the table of this call: the context's own, or a snapshot of the process-wide one
 	std::vector<uint64_t> snapshot;
 	if (!c->own_motifs) { std::lock_guard<std::mutex> lock(g_motifs_mutex); snapshot = g_motifs; }
@@ -241,6 +241,7 @@ extern "C" int dmnd_soft_mask_block(dmnd_ctx* c, int which, int64_t* n_covered)
 	HIP_TRY(copy_now(st, &n, c->counters.p, sizeof(n), hipMemcpyDeviceToHost));
 	if (n_covered) *n_covered = (int64_t)n;
 	c->soft_valid[which] = true;
+	if (which == DMND_TARGET) ++c->target_generation;      // the seed stage reads another view of the reference block from here on
 	return DMND_OK;
 }
 
@@ -263,7 +264,7 @@ static int mask_impl(dmnd_ctx* c, int which, int8_t* host_data, const int32_t* i
 {
 	if (!c || (which != DMND_QUERY && which != DMND_TARGET)) return fail(DMND_E_ARG, "dmnd_mask_block: bad argument");
 	c->soft_valid[which] = false;
-	if (which == DMND_QUERY) ++c->query_generation;
+	if (which == DMND_QUERY) ++c->query_generation; else ++c->target_generation;
 	if (!c->block[which].p || c->limits[which].size() < 2) return fail(DMND_E_ARG, "dmnd_mask_block: block must be uploaded with limits");
 	if (!c->block[which].own) return fail(DMND_E_ARG, "dmnd_mask_block: the block is shared from another context (dmnd_share_block); mask it there");
 	HIP_TRY(hipSetDevice(c->device));
@@ -470,7 +471,7 @@ int seg_device_impl(dmnd_ctx* c, int which, int8_t* host_data, const int32_t* id
 	if (!c || (which != DMND_QUERY && which != DMND_TARGET)) return fail(DMND_E_ARG, std::string(call) + ": bad argument");
 	if (n_masked) *n_masked = 0;
 	c->soft_valid[which] = false;
-	if (which == DMND_QUERY) ++c->query_generation;
+	if (which == DMND_QUERY) ++c->query_generation; else ++c->target_generation;
 	c->seg_last.clear(); c->seg_last_sorted = true;
 	for (double& x : c->seg_stats) x = 0;
 	if (!c->block[which].p || c->limits[which].size() < 2) return fail(DMND_E_ARG, std::string(call) + ": block must be uploaded with limits");

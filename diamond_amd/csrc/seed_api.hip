@@ -663,6 +663,70 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 	Timer tm(st);
 	for (int i = 0; i < 5; ++i) c->seed_ms[i] = 0;
 	lap("clears and query ids enqueued");
+	// ---- Sliced long-seed stream (seed_slices_core.h): long spaced seeds on the plain path (not fused, no key classes,
+	// nibble shapes) probe the level-1 filter from LDS slices, over a routing of the reference windows that is kept per uploaded block.
+	// Hashed (query-indexed) seeds stay on the plain kernel: their windows with a mask / stop letter are keyed from the raw letters.
+	// The first search of a block generation takes the plain kernel and builds nothing (a block searched once pays nothing), the second
+	// one with the same key builds, later ones keep. DMND_SEED_SLICES=0/1 forces never / always (always: built by the first search),
+	// DMND_SEED_SLICES_BUDGET_MB and DMND_SEED_SLICES_MIN_LETTERS stand in for the tuning values -- all read per call (the tests switch them).
+	SeedRefUse ref_use = SEED_REF_NONE;
+	int slice_bits = -1;
+	const int64_t ref_windows = seed_ref_windows(t_begin, t_end);
+	{
+		const int force = [] { const char* e = getenv("DMND_SEED_SLICES"); return e ? (atoi(e) != 0 ? 1 : 0) : -1; }();
+		const uint64_t budget = [] { const char* e = getenv("DMND_SEED_SLICES_BUDGET_MB"); return (uint64_t)std::max<long long>(0, e ? atoll(e) : tuning().seed_slices_budget_mb); }() << 20;
+		const int64_t min_letters = [] { const char* e = getenv("DMND_SEED_SLICES_MIN_LETTERS"); return e ? atoll(e) : tuning().seed_slices_min_letters; }();
+		const uint32_t max_words = [] { const char* e = getenv("DMND_SEED_SLICE_WORDS"); return (uint32_t)std::min<long long>(SEED_SLICE_MAX_WORDS, std::max<long long>(64, e ? atoll(e) : SEED_SLICE_MAX_WORDS)); }();      // (tests: many slices of a small filter)
+		slice_bits = seed_slice_bits(bm1_words, slot_bits, max_words);
+		// The default rule takes the sliced stream where it was measured to win: a sparse level-1 filter -- at least four bits per query
+		// position, C2's 3 % positives: what the slices save is the probe that ends at level 1; C4's filter (1e7
+		// query seeds, a third of the probes positive) took 4.29 ms by slices against 3.52 -- and few joins in the context's last search
+		// (the sliced stream lists the joins slice by slice, not in block order: C2skew).
+		const bool sparse_filter = (uint64_t)nq_pos * 4 <= bm1_words * 32;      // (at least four filter bits per query position: seed_sizes' own bound for the third bit)
+		const bool eligible = !fused && !classes && nibble_shapes && sp.seed_encoding == SEED_SPACED && slice_bits >= 0 && ref_windows < ((int64_t)1 << 31)
+			&& (force == 1 || (t_end - t_begin >= min_letters && sparse_filter && c->seed_last_joined <= tuning().seed_slices_max_joined));
+		const int8_t* tseed = c->soft_valid[DMND_TARGET] ? c->soft[DMND_TARGET].as<int8_t>() : c->block[DMND_TARGET].as<int8_t>();
+		bool drop = false;
+		ref_use = seed_ref_decide(c->seed_ref, seed_ref_key_of(c->target_generation, tseed, t_begin, t_end, sp, slice_bits), force, eligible, seed_ref_cache_bytes(t_begin, t_end, S), budget, &drop);
+		if (drop) c->release_seed_ref_buffers();            // (nothing on the stream reads them: the last search has been waited for; the state is seed_ref_decide's)
+		if (ref_use == SEED_REF_BUILT) {
+			// class nibbles (kept), flags and routing bytes (scratch of the build), then per shape one radix pass into its lists.
+			// An allocation that fails leaves the search on the plain kernel.
+			const int64_t n_groups = seed_code_groups(t_begin, t_end);
+			DevBuf route[2];
+			// (the kept buffers at their exact size, not with the slack DevBuf::ensure adds for buffers that grow: the budget counts these bytes)
+			auto exact = [](DevBuf& b, size_t bytes) {
+				if (b.cap == bytes && b.own) return true;
+				b.release();
+				if (hipMalloc(&b.p, bytes) != hipSuccess) { b.p = nullptr; (void)hipGetLastError(); return false; }
+				b.cap = bytes;
+				return true;
+			};
+			bool ok = exact(c->seed_ref_codes, (size_t)n_groups * sizeof(uint64_t)) && c->seed_tflags.ensure((size_t)n_groups * sizeof(uint32_t)) == DMND_OK
+				&& exact(c->seed_ref_lists, (size_t)S * (size_t)ref_windows * sizeof(uint32_t)) && exact(c->seed_ref_counts, (size_t)S * 64 * sizeof(uint32_t))
+				&& exact(route[0], (size_t)ref_windows) && exact(route[1], (size_t)ref_windows);
+			if (ok) {
+				tm.start();
+				hipError_t e = launch_seed_codes(sp, tseed, t_begin, t_end, c->seed_ref_codes.as<uint64_t>(), c->seed_tflags.as<uint32_t>(), nullptr, st);
+				for (int sid = 0; sid < S && e == hipSuccess; ++sid)
+					e = launch_seed_route(sp, sid, c->seed_ref_codes.as<uint64_t>(), c->seed_tflags.as<uint32_t>(), t_begin, t_end, slice_bits, route[0].as<uint8_t>(), route[1].as<uint8_t>(),
+						c->seed_ref_lists.as<uint32_t>() + (size_t)sid * (size_t)ref_windows, c->seed_ref_counts.as<uint32_t>() + (size_t)sid * 64, &c->sort_tmp, &c->sort_tmp_bytes, st);
+				tm.stop(c->seed_ms[0]);
+				if (e == hipSuccess) e = sync_stream(st);          // the scratch goes away below
+				if (e != hipSuccess) { route[0].release(); route[1].release(); c->release_seed_ref(); HIP_TRY(e); }
+			}
+			route[0].release(); route[1].release();
+			seed_ref_built(c->seed_ref, ok);
+			if (!ok) { c->release_seed_ref(); ref_use = SEED_REF_NONE; }
+			lap("reference cache built");
+		}
+	}
+	// the stream of one shape: the sliced kernel over the cache, or the plain one
+	auto stream_shape = [&](const SeedArgs& a, int sid) -> hipError_t {
+		if (ref_use == SEED_REF_NONE) return launch_seed_stream(a, sid, st);
+		return launch_seed_stream_slices(a, sid, c->seed_ref_codes.as<uint64_t>(), c->seed_ref_lists.as<uint32_t>() + (size_t)sid * (size_t)ref_windows,
+			c->seed_ref_counts.as<uint32_t>() + (size_t)sid * 64, slice_bits, st);
+	};
 	// the query side of one shape: built (table, position lists, bitmaps), or -- kept from an earlier call -- its marks reset
 	auto query_side = [&](const SeedArgs& a, int sid, bool build) -> int {
 		if (build) {
@@ -856,7 +920,7 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 			if (int rc = query_side(a, sid, !index_ready)) return rc;
 			tm.stop(c->seed_ms[0]);
 			tm.start();
-			HIP_TRY(launch_seed_stream(a, sid, st));
+			HIP_TRY(stream_shape(a, sid));
 			tm.stop(c->seed_ms[1]);
 			HIP_TRY(launch_seed_chain_streamed(ch, sid, st));
 		}
@@ -954,7 +1018,7 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 			if (int rc = query_side(a, sid, !index_ready || attempt > 0 || dirty)) return rc;
 			tm.stop(c->seed_ms[0]);
 			tm.start();
-			HIP_TRY(launch_seed_stream(a, sid, st));
+			HIP_TRY(stream_shape(a, sid));
 			tm.stop(c->seed_ms[1]);
 			HIP_TRY(copy_now(c->stream, &counts[sid], a.matched_count, sizeof(unsigned long long), hipMemcpyDeviceToHost));
 			if ((int64_t)counts[sid] > cap_total - off) { overflow = true; off += (int64_t)counts[sid]; continue; }
@@ -1123,9 +1187,15 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 		std::fprintf(stderr, " | deferred:");
 		for (int sid = 0; sid < S && (size_t)(S + sid) < c->seed_trace.size(); ++sid) std::fprintf(stderr, " %llu", c->seed_trace[S + sid]);
 		std::fprintf(stderr, " | hits %lld | ms index %.2f stream %.2f mask %.2f pairs %.2f | path: %s\n", (long long)c->n_seed_hits, c->seed_ms[0], c->seed_ms[1], c->seed_ms[2], c->seed_ms[3], path);
+		// which stream ran, and what this call did about the reference cache (its own line: the one above ends with the path)
+		const size_t held = c->seed_ref_codes.cap + c->seed_ref_lists.cap + c->seed_ref_counts.cap;
+		if (ref_use == SEED_REF_NONE) std::fprintf(stderr, "dmnd_seed_search: stream: plain, reference cache: none, %zu bytes held\n", held);
+		else std::fprintf(stderr, "dmnd_seed_search: stream: slices (%d x %g KB), reference cache: %s, %zu bytes held\n", 1 << slice_bits, (double)(bm1_words >> slice_bits) * 4 / 1024, ref_use == SEED_REF_BUILT ? "built" : "kept", held);
 	}
 	*n_hits = c->n_seed_hits;
 	c->seed_last_hits = c->n_seed_hits;
+	c->seed_last_joined = 0;
+	for (int sid = 0; sid < S; ++sid) c->seed_last_joined += (int64_t)counts[sid];
 	return DMND_OK;
 }
 

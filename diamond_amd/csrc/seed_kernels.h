@@ -5,6 +5,7 @@
 #include "../../include/diamond_hip.h"
 #include "seed_core.h"
 #include "seed_chain.h"
+#include "seed_slices_core.h"
 
 namespace dmnd {
 
@@ -128,6 +129,13 @@ inline int64_t seed_code_groups(int64_t t_begin, int64_t t_end) { return (t_end 
 hipError_t launch_seed_codes(const SeedParams& c, const int8_t* tseed, int64_t t_begin, int64_t t_end, uint64_t* codes, uint32_t* flags, uint64_t* planes, hipStream_t st);
 hipError_t launch_seed_stream(const SeedArgs& a, int sid, hipStream_t st, bool fused = false);
 bool seed_stream_can_fuse(const SeedParams& c);
+// Sliced long-seed stream (seed_slices_core.h). The routing of shape sid over the class nibbles / flags of launch_seed_codes: list
+// receives the seed_ref_windows window offsets (from t_begin rounded down to 16) slice by slice, ascending in each, counts (64 words)
+// the windows per slice; route / route_sorted: one byte per window each, scratch. Spaced nibble-mode shapes, fewer than 2^31 windows.
+hipError_t launch_seed_route(const SeedParams& c, int sid, const uint64_t* codes, const uint32_t* flags, int64_t t_begin, int64_t t_end, int slice_bits,
+	uint8_t* route, uint8_t* route_sorted, uint32_t* list, uint32_t* counts, void** tmp, size_t* tmp_bytes, hipStream_t st);
+// launch_seed_stream's work for a search without key classes, from that routing: the same joined positions, in another order
+hipError_t launch_seed_stream_slices(const SeedArgs& a, int sid, const uint64_t* codes, const uint32_t* list, const uint32_t* counts, int slice_bits, hipStream_t st);
 // n_matched >= 0: the number of joined positions in a.matched_* (few of them: the kernel walks that list instead of the table)
 hipError_t launch_seed_mask(const SeedArgs& a, int sid, hipStream_t st, int64_t n_matched = -1);
 hipError_t launch_seed_pairs(const SeedArgs& a, int sid, int64_t n_matched, hipStream_t st);

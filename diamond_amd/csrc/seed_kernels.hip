@@ -847,6 +847,176 @@ __global__ __launch_bounds__(256) void seed_stream_fast_kernel(SeedArgs a, int s
 	}
 }
 
+// ---- sliced long-seed reference stream (seed_slices_core.h) -------------------------------------------------------
+// The plain stream sends one 4-byte level-1 probe per window to L2, each lane's its own request, and runs at the rate the L2s accept
+// requests. Here a workgroup loads ONE slice of the filter into LDS and walks the list of the windows whose keys fall into that
+// slice (the routing, built once per uploaded reference block: seed_route_kernel + one stable radix pass): the probe is an LDS read,
+// and what goes to L2 is coalesced -- the list (4 bytes per window, consecutive) and the class nibbles of windows that lie some 2^b
+// letters apart (16 bytes per window out of neighbouring lines).
+// Workgroup w serves slice w mod 2^b and the (w >> b)-th share of its list; no workgroup waits for another. The shares of all slices
+// cover the same stretch of the block at the same time, so a line of nibbles is pulled into an XCD's L2 once for its slices.
+// One workgroup of 16 wavefronts fits a CU beside the slice, so nothing in the loop may make a wavefront wait for the others: behind
+// the slice load there is no workgroup barrier (a barrier also drains the loads a wavefront has requested ahead). Every wavefront
+// keeps its own queue of level-1 positives and its own staging area in LDS, addressed with ballots instead of atomics:
+//  * list entries are requested two rounds ahead and nibbles one round ahead of the round whose keys are hashed and probed;
+//  * level-1 positives (3.1 % of the windows with C2's 3 MB filter and three bits per seed, 9.7 % with 2 MB and two: seed_sizes) are queued, and 64 of them at a time take the plain kernel's path -- level-2 bitmap,
+//    table, SLOT_JOINED -- with all lanes busy, instead of a chain of dependent reads in the few lanes that found one;
+//  * joins are staged and go out with one matched_count atomic per flush; direct append when the staging area is full.
+// Spaced seeds only (hashed seeds stay on the plain kernel: their windows with a mask / stop letter are keyed from the raw letters).
+enum { SEED_SLICE_THREADS = 1024, SEED_SLICE_BATCH = 4, SEED_SLICE_QUEUE = 128, SEED_SLICE_STAGE = 32 };
+__global__ __launch_bounds__(SEED_SLICE_THREADS) void seed_stream_slices_kernel(SeedArgs a, int64_t base, uint64_t care64, const uint64_t* __restrict__ codes,
+	const uint32_t* __restrict__ list, const uint32_t* __restrict__ counts, int slice_bits, uint32_t slice_words)
+{
+	constexpr int B = SEED_SLICE_BATCH;                       // windows of a thread per round
+	constexpr unsigned WAVES = SEED_SLICE_THREADS / 64, QW = SEED_SLICE_QUEUE, ST = SEED_SLICE_STAGE;
+	static_assert(QW >= 128, "a wavefront queues up to 63 + 64 positives before it probes 64");
+	__shared__ uint32_t slice[SEED_SLICE_MAX_WORDS];
+	__shared__ uint64_t q_key[WAVES][QW];
+	__shared__ uint32_t q_off[WAVES][QW];
+	__shared__ uint32_t st_slot[WAVES][ST], st_off[WAVES][ST];
+	const unsigned s = blockIdx.x & ((1u << slice_bits) - 1), share = blockIdx.x >> slice_bits, shares = gridDim.x >> slice_bits;
+	uint64_t begin = 0;
+	for (unsigned i = 0; i < s; ++i) begin += counts[i];
+	const uint64_t count = counts[s];
+	const uint64_t lo = begin + count * share / shares, hi = begin + count * (share + 1) / shares;
+	const uint32_t word0 = s * slice_words;
+	for (uint32_t i = threadIdx.x; i < slice_words; i += blockDim.x) slice[i] = a.bitmap1[word0 + i];
+	__syncthreads();
+	const unsigned wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+	unsigned qn = 0, sn = 0;                                  // queued positives, staged joins of this wavefront (wavefront-uniform)
+	auto rank_in = [&](unsigned long long ballot) { return (unsigned)__builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u)); };
+	// LDS written by some lanes of the wavefront and read by others: the hardware runs a wavefront's LDS operations in order
+	auto wave_sync = [&]() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); };
+	auto flush = [&]() {
+		const unsigned n = sn < ST ? sn : ST;
+		unsigned long long at = 0;
+		if (lane == 0) at = atomicAdd(a.matched_count, (unsigned long long)n);
+		at = ((unsigned long long)(uint32_t)__shfl((int)(at >> 32), 0) << 32) | (uint32_t)__shfl((int)(uint32_t)at, 0);
+		wave_sync();
+		if (lane < n && at + lane < (unsigned long long)a.matched_cap) { a.matched_slot[at + lane] = st_slot[wave][lane]; a.matched_loc[at + lane] = base + st_off[wave][lane]; }
+		wave_sync();
+		sn = 0;
+	};
+	// level-2 bitmap -> table for one queued window per lane, the joins staged. This is probe_table / table_chain of
+	// seed_stream_fast_kernel (same level-2 test, chain walk, SLOT_JOINED store and direct append) with the staging slot taken by ballot
+	// instead of an LDS atomic and LEVEL2 read from the arguments: a change to either has to be made in both.
+	auto probe = [&](bool active, uint64_t seed, uint32_t off) {
+		bool found = false;
+		uint64_t slot = 0;
+		if (active) {
+			const uint64_t hh = seed_hash(seed);
+			if (!a.level2 || ((a.bitmap[a.bm2_index((uint32_t)hh, seed)] >> (uint32_t)(hh >> 59)) & 1u)) {
+				slot = a.home(hh, seed);
+				SeedSlot sl = a.slot(slot);
+				uint32_t fl = 0;
+				for (;;) {
+					if (sl.key == SEED_EMPTY) break;
+					if (sl.key == seed) { found = true; fl = sl.flags; break; }
+					slot = (slot + 1) & a.slot_mask;
+					sl = a.slot(slot);
+				}
+				if (found && !(fl & SLOT_JOINED)) a.slot(slot).flags = fl | SLOT_JOINED;
+			}
+		}
+		const unsigned long long jb = __ballot(found);
+		if (jb == 0) return;
+		const unsigned k = sn + rank_in(jb);
+		if (found) {
+			if (k < ST) { st_slot[wave][k] = (uint32_t)slot; st_off[wave][k] = off; }
+			else {                                                // staging area full (dense matches): direct append
+				const unsigned long long idx = atomicAdd(a.matched_count, 1ull);
+				if (idx < (unsigned long long)a.matched_cap) { a.matched_slot[idx] = (uint32_t)slot; a.matched_loc[idx] = base + off; }
+			}
+		}
+		sn += (unsigned)__builtin_popcountll(jb);
+		if (sn >= ST / 2) flush();
+	};
+	const uint64_t stride = (uint64_t)B * blockDim.x;
+	auto entries = [&](uint64_t k0, uint32_t* o) {
+#pragma unroll
+		for (int j = 0; j < B; ++j) {
+			const uint64_t k = k0 + (uint64_t)j * blockDim.x + threadIdx.x;
+			o[j] = k < hi ? list[k] : 0xffffffffu;
+		}
+	};
+	auto nibbles = [&](const uint32_t* o, uint64_t* c0, uint64_t* c1) {
+#pragma unroll
+		for (int j = 0; j < B; ++j) {
+			const uint32_t g = o[j] == 0xffffffffu ? 0u : o[j] >> 4;
+			c0[j] = codes[g]; c1[j] = codes[g + 1];
+		}
+	};
+	uint32_t off[B], off1[B], off2[B];
+	uint64_t c0[B], c1[B], n0[B], n1[B];
+	entries(lo, off);
+	entries(lo + stride, off1);
+	nibbles(off, c0, c1);
+	for (uint64_t k0 = lo; k0 < hi; k0 += stride) {
+		entries(k0 + 2 * stride, off2);
+		nibbles(off1, n0, n1);
+#pragma unroll
+		for (int j = 0; j < B; ++j) {
+			const int sh = (int)(off[j] & 15u) * 4;
+			const uint64_t key = (sh == 0 ? c0[j] : (c0[j] >> sh) | (c1[j] << (64 - sh))) & care64;
+			const uint32_t h = seed_hash_a(key);
+			// inside the slice by the slice identity (seed_slices_core.h; the launch checks its conditions). The clamp below is for the
+			// padding entries behind the end of the list (0xffffffff: their key is of group 0 and may fall into any slice), which `pass` drops
+			const uint32_t lw = a.bm1_index(h, key) - word0;
+			const uint32_t bw = slice[lw < slice_words ? lw : 0u], need = bm1_bits(h, a.bitmap1_k3);
+			const bool pass = off[j] != 0xffffffffu && (bw & need) == need;
+			const unsigned long long pb = __ballot(pass);
+			if (pb) {
+				if (pass) { const unsigned k = qn + rank_in(pb); q_key[wave][k] = key; q_off[wave][k] = off[j]; }
+				qn += (unsigned)__builtin_popcountll(pb);
+				if (qn >= 64) {                                      // (wavefront-uniform)
+					wave_sync();
+					qn -= 64;
+					const uint64_t seed = q_key[wave][qn + lane];
+					const uint32_t o = q_off[wave][qn + lane];
+					wave_sync();
+					probe(true, seed, o);
+				}
+			}
+		}
+#pragma unroll
+		for (int j = 0; j < B; ++j) { off[j] = off1[j]; off1[j] = off2[j]; c0[j] = n0[j]; c1[j] = n1[j]; }
+	}
+	wave_sync();
+	{
+		const bool active = lane < qn;
+		const uint64_t seed = active ? q_key[wave][lane] : 0;
+		const uint32_t o = active ? q_off[wave][lane] : 0;
+		probe(active, seed, o);
+	}
+	if (sn) flush();
+}
+
+// routing bytes of every window (seed_route_group) and the number of windows per slice
+__global__ __launch_bounds__(256) void seed_route_kernel(const uint64_t* __restrict__ codes, const uint32_t* __restrict__ flags, int64_t base, int64_t n_groups, int64_t t_begin, int64_t t_end,
+	int len, uint32_t care, uint64_t care64, int slice_bits, uint8_t* __restrict__ route, uint32_t* __restrict__ counts)
+{
+	__shared__ uint32_t hist[1 << SEED_SLICE_MAX_BITS];
+	if (threadIdx.x < (1u << SEED_SLICE_MAX_BITS)) hist[threadIdx.x] = 0;
+	__syncthreads();
+	const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (g < n_groups) {
+		const int64_t p0 = base + 16 * g;
+		uint8_t out[16];
+		seed_route_group(codes[g], codes[g + 1], flags[g], flags[g + 1], t_begin - p0, t_end - p0, len, care, care64, slice_bits, out);
+		uint32_t w[4] = { 0, 0, 0, 0 };
+#pragma unroll
+		for (int j = 0; j < 16; ++j) {
+			w[j >> 2] |= (uint32_t)out[j] << ((j & 3) * 8);
+			if (out[j] != SEED_ROUTE_NONE) atomicAdd(&hist[out[j]], 1u);
+		}
+		typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+		u32x4 v; v.x = w[0]; v.y = w[1]; v.z = w[2]; v.w = w[3];
+		*reinterpret_cast<u32x4*>(route + 16 * g) = v;
+	}
+	__syncthreads();
+	if (threadIdx.x < (1u << slice_bits) && hist[threadIdx.x]) atomicAdd(&counts[threadIdx.x], hist[threadIdx.x]);
+}
+
 __global__ void seed_mask_kernel(SeedArgs a, int sid)
 {
 	const uint64_t slot = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1580,7 +1750,7 @@ __global__ void seed_codes_kernel(const int8_t* __restrict__ tseed, int64_t base
 	}
 	codes[g] = code;
 	flags[g] = delim | (bad << 16);
-	planes[g] = (uint64_t)p01 | ((uint64_t)p23 << 32);
+	if (planes) planes[g] = (uint64_t)p01 | ((uint64_t)p23 << 32);      // (NULL: the sliced stream's cache wants the nibbles only)
 }
 
 hipError_t launch_seed_codes(const SeedParams& c, const int8_t* tseed, int64_t t_begin, int64_t t_end, uint64_t* codes, uint32_t* flags, uint64_t* planes, hipStream_t st)
@@ -1827,6 +1997,59 @@ hipError_t launch_seed_stream(const SeedArgs& a, int sid, hipStream_t st, bool f
 		return hipGetLastError();
 	}
 	hipLaunchKernelGGL(seed_stream_kernel, dim3(blocks_for(a.t_end - a.t_begin, 256)), dim3(256), 0, st, a, sid);
+	return hipGetLastError();
+}
+
+static uint64_t care64_of(const SeedParams& c, int sid)
+{
+	uint64_t care64 = 0;
+	for (int k = 0; k < c.shape_weight[sid]; ++k) care64 |= (uint64_t)15 << (4 * c.shape_pos[sid][k]);
+	return care64;
+}
+
+hipError_t launch_seed_route(const SeedParams& c, int sid, const uint64_t* codes, const uint32_t* flags, int64_t t_begin, int64_t t_end, int slice_bits,
+	uint8_t* route, uint8_t* route_sorted, uint32_t* list, uint32_t* counts, void** tmp, size_t* tmp_bytes, hipStream_t st)
+{
+	if (!seed_nibble_mode(c, sid) || c.seed_encoding != SEED_SPACED || slice_bits < 0 || slice_bits > SEED_SLICE_MAX_BITS) return hipErrorInvalidValue;
+	const int64_t base = t_begin & ~(int64_t)15, n = seed_ref_windows(t_begin, t_end);
+	if (n <= 0 || n >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
+	hipError_t e = hipMemsetAsync(counts, 0, ((size_t)1 << SEED_SLICE_MAX_BITS) * sizeof(uint32_t), st);
+	if (e != hipSuccess) return e;
+	hipLaunchKernelGGL(seed_route_kernel, dim3(blocks_for(n / 16, 256)), dim3(256), 0, st, codes, flags, base, n / 16, t_begin, t_end, (int)c.shape_len[sid], c.shape_mask[sid], care64_of(c, sid),
+		slice_bits, route, counts);
+	// one stable radix pass over the routing bytes' low b + 1 bits lists the windows slice by slice, ascending in each; the windows that
+	// are no seeds (all ones) come last
+	rocprim::counting_iterator<uint32_t> iota(0);
+	size_t need = 0;
+	e = rocprim::radix_sort_pairs(nullptr, need, route, route_sorted, iota, list, (size_t)n, 0, (unsigned)slice_bits + 1, st);
+	if (e != hipSuccess) return e;
+	if (need > *tmp_bytes) {
+		if (*tmp) (void)hipFree(*tmp);
+		*tmp = nullptr; *tmp_bytes = 0;
+		e = hipMalloc(tmp, need);
+		if (e != hipSuccess) return e;
+		*tmp_bytes = need;
+	}
+	e = rocprim::radix_sort_pairs(*tmp, need, route, route_sorted, iota, list, (size_t)n, 0, (unsigned)slice_bits + 1, st);
+	if (e != hipSuccess) return e;
+	return hipGetLastError();
+}
+
+hipError_t launch_seed_stream_slices(const SeedArgs& a, int sid, const uint64_t* codes, const uint32_t* list, const uint32_t* counts, int slice_bits, hipStream_t st)
+{
+	const SeedParams& c = a.params;
+	if (a.classes || a.fused || !seed_nibble_mode(c, sid) || c.seed_encoding != SEED_SPACED || slice_bits < 0 || slice_bits > SEED_SLICE_MAX_BITS) return hipErrorInvalidValue;
+	if (a.bitmap1_words % (1u << slice_bits) != 0 || (a.bitmap1_words >> slice_bits) > (uint32_t)SEED_SLICE_MAX_WORDS || slice_bits > a.slot_bits) return hipErrorInvalidValue;
+	// a workgroup per CU (the slice takes most of a CU's LDS), a whole number of shares per slice
+	int dev = 0, n_cus = 0;
+	hipError_t e = hipGetDevice(&dev);
+	if (e != hipSuccess) return e;
+	e = hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, dev);
+	if (e != hipSuccess) return e;
+	n_cus = std::max(n_cus, 1);
+	const unsigned slices = 1u << slice_bits, shares = std::max(1u, (unsigned)n_cus / slices);
+	hipLaunchKernelGGL(seed_stream_slices_kernel, dim3(slices * shares), dim3(SEED_SLICE_THREADS), 0, st, a, a.t_begin & ~(int64_t)15, care64_of(c, sid), codes, list, counts, slice_bits,
+		a.bitmap1_words >> slice_bits);
 	return hipGetLastError();
 }
 

@@ -4,7 +4,7 @@
 # and the test-only helpers: oracle/_ref/* (CPU restatement + reference build), tests/emu/libswipe_emu.so
 HIPCC   ?= /opt/rocm/bin/hipcc
 CSRC    := diamond_amd/csrc
-HIPSRC  := $(CSRC)/api.hip $(CSRC)/swipe_kernels.hip $(CSRC)/swipe16_kernels.hip $(CSRC)/seed_api.hip $(CSRC)/seed_kernels.hip $(CSRC)/extend_host.hip $(CSRC)/gapped_api.hip $(CSRC)/gapped_kernels.hip $(CSRC)/mask_api.hip $(CSRC)/mask_kernels.hip $(CSRC)/seg_kernels.hip $(CSRC)/bias_kernels.hip $(CSRC)/format_api.hip $(CSRC)/frameshift_api.hip $(CSRC)/frameshift_kernels.hip $(CSRC)/frameshift_host.hip $(CSRC)/join_device.hip $(CSRC)/rank_join.hip $(CSRC)/plan_kernels.hip $(CSRC)/extend_kernels.hip $(CSRC)/extend_device.hip $(CSRC)/join_blocks.hip $(CSRC)/format_tab.hip $(CSRC)/translate.hip $(CSRC)/rank_kernels.hip $(CSRC)/rank_api.hip
+HIPSRC  := $(CSRC)/api.hip $(CSRC)/swipe_kernels.hip $(CSRC)/swipe16_kernels.hip $(CSRC)/seed_api.hip $(CSRC)/seed_kernels.hip $(CSRC)/extend_host.hip $(CSRC)/gapped_api.hip $(CSRC)/gapped_kernels.hip $(CSRC)/mask_api.hip $(CSRC)/mask_kernels.hip $(CSRC)/seg_kernels.hip $(CSRC)/bias_kernels.hip $(CSRC)/format_api.hip $(CSRC)/frameshift_api.hip $(CSRC)/frameshift_kernels.hip $(CSRC)/frameshift_host.hip $(CSRC)/join_device.hip $(CSRC)/rank_join.hip $(CSRC)/plan_kernels.hip $(CSRC)/extend_kernels.hip $(CSRC)/extend_device.hip $(CSRC)/join_blocks.hip $(CSRC)/format_tab.hip $(CSRC)/translate.hip $(CSRC)/rank_kernels.hip $(CSRC)/rank_api.hip $(CSRC)/cbs_kernels.hip
 HIPHDR  := $(wildcard $(CSRC)/*.h) include/diamond_hip.h
 HIPFLAGS := --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function
 
@@ -26,6 +26,8 @@ build/%.o: $(CSRC)/%.hip $(HIPHDR)
 
 # the device planner truncates double expressions to int exactly as the host's chaining does: no contraction into fused multiply-adds
 build/plan_kernels.o build/extend_kernels.o build/seg_kernels.o: HIPFLAGS += -ffp-contract=off
+# the matrix adjustment on the device keeps the host form's operation order (cbs_core.h): likewise
+build/cbs_kernels.o: HIPFLAGS += -ffp-contract=off
 
 # host-only double-precision code whose results must be bit-identical to the reference's (composition-based matrix adjustment):
 # plain g++, no contraction of a * b + c into fused multiply-adds
@@ -48,7 +50,7 @@ oracle:
 	$(MAKE) -C oracle all
 
 emu: tests/emu/libswipe_emu.so
-tests/emu/libswipe_emu.so: $(wildcard tests/emu/*.cpp) $(wildcard $(CSRC)/*_core.h) $(CSRC)/seg_mask.h
+tests/emu/libswipe_emu.so: $(wildcard tests/emu/*.cpp) $(wildcard $(CSRC)/*_core.h) $(CSRC)/seg_mask.h $(CSRC)/cbs_adjust.cpp $(CSRC)/cbs_adjust.h $(CSRC)/cbs_model.h $(CSRC)/cbs_tables.h $(CSRC)/score_matrices.h
 	g++ -O2 -std=c++17 -ffp-contract=off -fPIC -shared -w -o $@ $(wildcard tests/emu/*.cpp)
 
 clean:

@@ -357,6 +357,7 @@ extern "C" void dmnd_destroy(dmnd_ctx* c)
 	c->stage_h.release(); c->ends_h.release(); c->stage_d.release();
 	c->xd_hits.release(); c->xd_out.release(); c->xd_host.release();
 	c->plan_dev.release(); c->plan_host.release(); c->rank_dev.release();
+	c->cbs_dev.release(); c->cbs_host.release();
 	c->ext_dev.release(); c->ext_trace.release(); c->ext_host.release(); c->ext_ev.release();
 	for (DevBuf& b : c->ext_trace_more) b.release();
 	c->ext_tr.release(); c->ext_tr_raw.release(); c->ext_tr_store.release(); c->ext_tr_out.release(); c->ext_source_lens.release();
@@ -1344,10 +1345,9 @@ dmnd_ctx* aux_context(dmnd_ctx* c, int k, int split)
 }
 
 // Replaces (n_keep == 0) or extends the context's adjusted matrices: the first n_keep stay, `n` are appended behind them.
-int dmnd_append_matrices(dmnd_ctx* c, int64_t n_keep, const int8_t* matrices, int64_t n)
+// matrices == NULL: the new slots are reserved, not written
+static int append_matrices(dmnd_ctx* c, int64_t n_keep, const int8_t* matrices, int64_t n)
 {
-	if (n == 0 && n_keep == 0 && c) { c->n_adj_matrices = 0; return DMND_OK; }
-	if (!c || n_keep < 0 || n < 0 || n_keep > c->n_adj_matrices || (n > 0 && !matrices)) return fail(DMND_E_ARG, "dmnd_upload_matrices: bad argument");
 	HIP_TRY(hipSetDevice(c->device));
 	const size_t M = 32 * 32, need = (size_t)(n_keep + n) * M;
 	if (need > c->adj_matrices.cap) {                     // grow: the kept matrices move to the new buffer on the device
@@ -1358,9 +1358,22 @@ int dmnd_append_matrices(dmnd_ctx* c, int64_t n_keep, const int8_t* matrices, in
 		c->adj_matrices.release();
 		c->adj_matrices = bigger;
 	}
-	if (n > 0) HIP_TRY(copy_now(c->stream, c->adj_matrices.as<int8_t>() + (size_t)n_keep * M, matrices, (size_t)n * M, hipMemcpyHostToDevice));
+	if (n > 0 && matrices) HIP_TRY(copy_now(c->stream, c->adj_matrices.as<int8_t>() + (size_t)n_keep * M, matrices, (size_t)n * M, hipMemcpyHostToDevice));
 	c->n_adj_matrices = n_keep + n;
 	return DMND_OK;
+}
+
+int dmnd_reserve_matrices(dmnd_ctx* c, int64_t n_keep, int64_t n)
+{
+	if (!c || n_keep < 0 || n < 0 || n_keep > c->n_adj_matrices) return fail(DMND_E_ARG, "dmnd_reserve_matrices: bad argument");
+	return append_matrices(c, n_keep, nullptr, n);
+}
+
+int dmnd_append_matrices(dmnd_ctx* c, int64_t n_keep, const int8_t* matrices, int64_t n)
+{
+	if (n == 0 && n_keep == 0 && c) { c->n_adj_matrices = 0; return DMND_OK; }
+	if (!c || n_keep < 0 || n < 0 || n_keep > c->n_adj_matrices || (n > 0 && !matrices)) return fail(DMND_E_ARG, "dmnd_upload_matrices: bad argument");
+	return append_matrices(c, n_keep, matrices, n);
 }
 
 extern "C" int dmnd_upload_matrices(dmnd_ctx* c, const int8_t* matrices, int64_t n)

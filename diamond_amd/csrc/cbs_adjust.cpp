@@ -126,7 +126,7 @@ void kkt_solve(const Kkt& s, double* x, double* z, double* work)
 
 // Target frequencies x closest (in relative entropy) to q whose row sums are row[], column sums col[] and whose own relative
 // entropy is `re`. Returns 0 = converged to a minimiser, 1 = not.          (Blast_OptimizeTargetFrequencies, ncbi.cpp:660-790)
-int optimise_target_freqs(double* x, const double* q, const double* row, const double* col, double re, double tol, int maxits)
+int optimise_target_freqs(double* x, const double* q, const double* row, const double* col, double re, double tol, int maxits, CbsHostTrace* tr)
 {
 	double old_scores[NN], grad0[NN], grad1[NN], rx[NN], work[NN], z[M], rz[M], rnorm = 0.0;
 	Kkt kkt;
@@ -159,6 +159,7 @@ int optimise_target_freqs(double* x, const double* q, const double* row, const d
 		rz[M - 1] = re - v1;
 		const double norm_z = norm2(rz, M);
 		rnorm = std::sqrt(norm_x * norm_x + norm_z * norm_z);
+		if (tr) { if (tr->n_rnorm < CbsHostTrace::CAP) tr->rnorm[tr->n_rnorm++] = rnorm; tr->its = its; }
 		if (!(rnorm > tol)) break;                    // also leaves on NaN
 		if (++its <= maxits) {
 			kkt_factor(kkt, x, z, grad1, work);
@@ -173,6 +174,7 @@ int optimise_target_freqs(double* x, const double* q, const double* row, const d
 			for (int i = 0; i < M; ++i) z[i] += alpha * rz[i];
 		}
 	}
+	if (tr) tr->eta = z[M - 1];
 	return (its <= maxits && rnorm <= tol && z[M - 1] < 1) ? 0 : 1;
 }
 
@@ -211,7 +213,7 @@ int round_score(double f) { return f < INT_MIN ? INT_MIN : (int)std::round(f); }
 struct IntTable { int v[STD][STD]; };
 
 // target frequencies -> rounded scores on scale lambda          (s_ScoresStdAlphabet, matrix_adjust.cpp:170-208)
-void scores_from_freqs(IntTable& out, const double* freq, const double* row_prob, const double* col_prob, double lambda)
+void scores_from_freqs(IntTable& out, const double* freq, const double* row_prob, const double* col_prob, double lambda, CbsHostTrace* tr)
 {
 	double S[STD][STD];
 	double sum = 0.0;
@@ -226,20 +228,24 @@ void scores_from_freqs(IntTable& out, const double* freq, const double* row_prob
 	for (int i = 0; i < STD; ++i)
 		for (int j = 0; j < STD; ++j) S[i][j] = 0.0 == S[i][j] ? SCORE_MIN : std::log(S[i][j]) / lambda;
 	set_x_scores(S, row_prob, col_prob);
+	if (tr)
+		for (int a = 0; a <= N; ++a)
+			for (int b = 0; b <= N; ++b) tr->scores[a * (N + 1) + b] = S[a < N ? a : X_LETTER][b < N ? b : X_LETTER];
 	for (int i = 0; i < STD; ++i)
 		for (int j = 0; j < STD; ++j) out.v[i][j] = round_score(S[i][j]);
 }
 
 // CompositionMatrixAdjust (matrix_adjust.cpp:455-476) = Blast_CompositionMatrixAdj with the fixed relative entropy
-bool relative_entropy_adjust(const CbsModel& m, IntTable& out, int query_len, int target_len, const double* query_comp, const double* target_comp)
+bool relative_entropy_adjust(const CbsModel& m, IntTable& out, int query_len, int target_len, const double* query_comp, const double* target_comp, CbsHostTrace* tr)
 {
 	double row[N], col[N], x[NN];
 	std::copy(query_comp, query_comp + N, row);
 	std::copy(target_comp, target_comp + N, col);
 	apply_pseudocounts(row, query_len, m.background);
 	apply_pseudocounts(col, target_len, m.background);
-	if (optimise_target_freqs(x, m.joint_probs, row, col, FIXED_RE, m.err_tolerance, m.it_limit) != 0) return false;
-	scores_from_freqs(out, x, row, col, m.ideal_lambda / m.scale);
+	if (optimise_target_freqs(x, m.joint_probs, row, col, FIXED_RE, m.err_tolerance, m.it_limit, tr) != 0) return false;
+	if (tr) tr->converged = 1;
+	scores_from_freqs(out, x, row, col, m.ideal_lambda / m.scale, tr);
 	return true;
 }
 
@@ -416,7 +422,7 @@ void cbs_composition(const int8_t* seq, int len, double comp[20], int* true_aa)
 	for (int i = 0; i < N; ++i) comp[i] /= n;
 }
 
-int cbs_rule(const CbsModel& m, int mode, const double query_comp[20], int query_true_aa, const int8_t* target, int target_len)
+int cbs_rule(const CbsModel& m, int mode, const double query_comp[20], int query_true_aa, const int8_t* target, int target_len, CbsHostTrace* tr)
 {
 	if (!cbs_matrix_adjust(mode) || target_len == 0 || query_true_aa == 0) return CBS_RULE_NONE;
 	if (!cbs_conditioned(mode)) return CBS_RULE_REL_ENTROPY;
@@ -428,6 +434,7 @@ int cbs_rule(const CbsModel& m, int mode, const double query_comp[20], int query
 		d_m_q = composition_distance(tc, query_comp);
 	double angle = std::acos((d_m_mat * d_m_mat + d_q_mat * d_q_mat - d_m_q * d_m_q) / 2.0 / d_m_mat / d_q_mat);
 	angle = angle * 180 / 3.1415926543;
+	if (tr) tr->angle = angle;
 	const double len_q = 1.0 * query_true_aa, len_m = 1.0 * target_len;
 	const double len_large = len_q > len_m ? len_q : len_m, len_small = len_q > len_m ? len_m : len_q;
 	int rule;
@@ -438,7 +445,7 @@ int cbs_rule(const CbsModel& m, int mode, const double query_comp[20], int query
 	return rule == CBS_RULE_REL_ENTROPY ? CBS_RULE_REL_ENTROPY : CBS_RULE_NONE;
 }
 
-void cbs_target_matrix(const CbsModel& m, int rule, const double query_comp[20], int query_true_aa, const int8_t* target, int target_len, int8_t* out)
+void cbs_target_matrix(const CbsModel& m, int rule, const double query_comp[20], int query_true_aa, const int8_t* target, int target_len, int8_t* out, CbsHostTrace* tr)
 {
 	double tc[N];
 	int target_true_aa = 0;
@@ -446,7 +453,8 @@ void cbs_target_matrix(const CbsModel& m, int rule, const double query_comp[20],
 	IntTable t;
 	bool ok = false;
 	if (rule == CBS_RULE_SCALE_OLD) ok = lambda_rescale(m, t, query_comp, tc);
-	if (!ok) ok = relative_entropy_adjust(m, t, query_true_aa, target_true_aa, query_comp, tc);
+	if (tr) { tr->n_rnorm = 0; tr->its = 0; tr->converged = 0; tr->eta = 0.0; }
+	if (!ok) ok = relative_entropy_adjust(m, t, query_true_aa, target_true_aa, query_comp, tc, tr);
 	if (!ok)                                          // the optimisation did not converge: the standard scores (matrix_adjust.cpp:470-474)
 		for (int i = 0; i < STD; ++i)
 			for (int j = 0; j < STD; ++j) t.v[i][j] = m.matrix8[i * 32 + j] * m.scale;

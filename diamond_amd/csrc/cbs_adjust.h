@@ -44,11 +44,23 @@ void cbs_model_init(CbsModel& m, const dmnd_params& params);
 // Stats::composition + count_true_aa (cbs.cpp:52-77): frequencies of the 20 residues among the residues of seq
 void cbs_composition(const int8_t* seq, int len, double comp[20], int* true_aa);
 
+// What the arithmetic went through on its way to the integers, for the measurement of the device form's guards (cbs_core.h,
+// tests/emu/cbs_emu.cpp): the angle of the rule, the residual norm at every convergence test, the Newton steps taken, the
+// relative-entropy multiplier at the end and the 21 x 21 unrounded scores [query letter][target letter] (index 20 = mask letter).
+// Filled where a caller passes one; the results do not depend on it.
+struct CbsHostTrace {
+	enum { CAP = 256 };
+	double rnorm[CAP];
+	int n_rnorm = 0, its = 0, converged = 0;
+	double angle = 0.0, eta = 0.0;
+	double scores[21 * 21];
+};
+
 // Stats::adjust_matrix: CBS_RULE_* for this pair. query_true_aa = count_true_aa(query context 0)
-int cbs_rule(const CbsModel& m, int mode, const double query_comp[20], int query_true_aa, const int8_t* target, int target_len);
+int cbs_rule(const CbsModel& m, int mode, const double query_comp[20], int query_true_aa, const int8_t* target, int target_len, CbsHostTrace* tr = nullptr);
 
 // Stats::TargetMatrix::TargetMatrix: out[target letter * 32 + query letter], 32 x 32 with the rows and columns of the
 // letters above 25 at -128 like the standard table; rule = what cbs_rule returned (not CBS_RULE_NONE)
-void cbs_target_matrix(const CbsModel& m, int rule, const double query_comp[20], int query_true_aa, const int8_t* target, int target_len, int8_t* out);
+void cbs_target_matrix(const CbsModel& m, int rule, const double query_comp[20], int query_true_aa, const int8_t* target, int target_len, int8_t* out, CbsHostTrace* tr = nullptr);
 
 }  // namespace dmnd

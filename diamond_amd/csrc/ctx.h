@@ -103,6 +103,9 @@ struct dmnd_ctx {
 	dmnd::DevBuf block[2], cbs, matrix, bias_ids;
 	dmnd::DevBuf adj_matrices;                 // composition-adjusted scoring matrices of the items this context sweeps (dmnd_upload_matrices;
 	int64_t n_adj_matrices = 0;                // dmnd_extend: those of the targets planned so far), 32 x 32 int8 each
+	dmnd::DevBuf cbs_dev;                      // matrix adjustment on the device (cbs_kernels.hip): model, pair list, rules and statuses of one launch ...
+	dmnd::PinBuf cbs_host;                     // ... and their page-locked staging
+	double cbs_dev_stats[6] = { 0, 0, 0, 0, 0, 0 };      // of the last dmnd_extend on this (work) context: pairs offered, decided on the device, handed back by rounding / iterations / rule, kernel ms
 	dmnd::DevBuf xd_hits, xd_out;             // device x-drop stage of dmnd_extend: the call's seed hits, one XdropSeg per hit
 	dmnd::PinBuf xd_host;
 	dmnd::DevBuf plan_dev;                    // device planner of dmnd_extend (plan_kernels.hip): its work arrays ...
@@ -264,6 +267,16 @@ int dmnd_extend_frameshift(dmnd_ctx* c, const int8_t* qdata, const int8_t* tdata
 	std::vector<dmnd_match>& out, uint8_t* transcript, int64_t transcript_cap, int64_t* transcript_used);
 // the first n_keep adjusted matrices of c stay, n more are appended (dmnd_upload_matrices = the same with n_keep = 0)
 int dmnd_append_matrices(dmnd_ctx* c, int64_t n_keep, const int8_t* matrices, int64_t n);
+// the same without an upload: room for n more matrices behind the first n_keep, which stay (the kernel of cbs_kernels.hip fills the new slots)
+int dmnd_reserve_matrices(dmnd_ctx* c, int64_t n_keep, int64_t n);
+// cbs_kernels.hip: the matrix adjustment of n (query, target) pairs on w's stream. comp (n_q x 20) / true_aa (n_q): the queries;
+// pair k is query qidx[k] (qidx NULL: query k) against the tlen[k] letters at letters_dev + toff[k]. The table of pair k goes to
+// tables_dev + k * 1024 (device), its 21 x 21 unrounded scores to scores_dev + k * 441 (device, may be NULL); rule_out / status_out: host.
+// max_its <= 0: the built-in cap. *kernel_ms: the kernel alone.
+namespace dmnd { struct CbsModel; }
+int dmnd_cbs_adjust_device(dmnd_ctx* w, const dmnd::CbsModel& model, int mode, int max_its, const int8_t* letters_dev, int64_t n_q, const double* comp, const int32_t* true_aa,
+	int64_t n, const int32_t* qidx, const int64_t* toff, const int32_t* tlen, int8_t* tables_dev, double* scores_dev, int32_t* rule_out, uint8_t* status_out, double* kernel_ms);
+int dmnd_cbs_env_max_its();      // DMND_CBS_DEVICE_MAX_ITS (test hook, read per call); 0 = the built-in cap
 // seed_api.hip: fills c->qid_of for the query block's limits on the context's stream, unless it holds them already
 int dmnd_seed_query_ids(dmnd_ctx* c);
 // k-th of `split` auxiliary contexts of c (created on first use; owned and destroyed by c)

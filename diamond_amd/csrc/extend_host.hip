@@ -53,6 +53,7 @@
 #include "host_pool.h"
 #include "bias_kernels.h"
 #include "cbs_adjust.h"
+#include "cbs_core.h"
 #include "read_coverage.h"
 #include "plan_kernels.h"
 #include "extend_kernels.h"
@@ -711,6 +712,17 @@ static int extend_range(const dmnd_ctx* c, dmnd_ctx* w, const HostCfg& h, const 
 		return dmnd_dp_target{ ql[q], tl[t], mat >= 0 ? (h.ext_full ? matrix_code(mat) : (int64_t)-2 - mat) : h.use_cbs ? ql[q] : (int64_t)-1, (int32_t)(ql[q + 1] - ql[q] - 1), (int32_t)(tl[t + 1] - tl[t] - 1), d0, d1 };
 	};
 	const bool adjust = cbs_matrix_adjust(h.cbs_mode);
+	// DMND_CBS_DEVICE=0 (read per call): the matrices of modes 2 - 5 are computed by the host threads and uploaded, the form before
+	// cbs_kernels.hip and the second implementation its parity tests compare with. Default: the planning threads only list the new
+	// (query, target) pairs, one launch fills their slots of the matrix store, the host computes the pairs it hands back.
+	const bool cbs_device = adjust && [] { const char* e = std::getenv("DMND_CBS_DEVICE"); return !e || e[0] != '0'; }();
+	const int cbs_max_its = cbs_device ? dmnd_cbs_env_max_its() : 0;
+	struct CbsStep {                     // the device form's lists of one planning step (pair k takes slot `before + k` of the store)
+		std::vector<Ref> pair_of;        // (query state, its row in q_comp) per pair ...
+		std::vector<uint32_t> target;    // ... and its target
+		std::vector<double> q_comp; std::vector<int32_t> q_true_aa, qidx, tlen, rule, mat; std::vector<int64_t> toff, handed;
+		std::vector<uint8_t> status, keep; std::vector<int8_t> patch; std::vector<CbsPatchRun> runs;
+	} cs;
 	// The reference's full-matrix sweep cannot trace an alignment back on an adjusted matrix: Hsp traceback(...) of
 	// dp/swipe/full_swipe.h:97-102 throws as soon as such a target has an HSP to report (--ext full, and the alternative HSPs of
 	// --max-hsps != 1). Same refusal here, with its message.
@@ -755,6 +767,14 @@ static int extend_range(const dmnd_ctx* c, dmnd_ctx* w, const HostCfg& h, const 
 					// WorkTarget::WorkTarget; only the sweeps read it)
 					const uint32_t q0 = s.w.query * C;
 					if (s.true_aa < 0) cbs_composition(qdata + ql[q0], (int)(ql[q0 + 1] - ql[q0] - 1), s.comp, &s.true_aa);
+					if (cbs_device) {                                // only list the new pairs: rule and table come from the kernel
+						for (const PlanTarget& p : s.plan) {
+							if (s.mat_of.count(p.target)) continue;
+							s.mat_of[p.target] = -2 - (int32_t)me.new_refs.size();
+							me.new_refs.push_back(NewMatrix{ i, p.target });
+						}
+						continue;
+					}
 					for (const PlanTarget& p : s.plan) {
 						if (s.mat_of.count(p.target)) continue;
 						const int8_t* tseq = tdata + tl[p.target];
@@ -772,7 +792,62 @@ static int extend_range(const dmnd_ctx* c, dmnd_ctx* w, const HostCfg& h, const 
 			size_t total = 0;
 			for (Slice& x : sl) { any |= x.any; x.item_off = total; total += x.n_items; }
 			if (!any) break;
-			if (adjust) {
+			if (cbs_device) {
+				// the step's new pairs take the slots [before, next) of the matrix store in slice order; one launch fills them
+				const int64_t before = w->n_adj_matrices;
+				cs.pair_of.clear(); cs.target.clear(); cs.q_comp.clear(); cs.q_true_aa.clear(); cs.qidx.clear(); cs.tlen.clear(); cs.toff.clear();
+				for (Slice& x : sl) {
+					for (const NewMatrix& r : x.new_refs) {
+						if (cs.pair_of.empty() || cs.pair_of.back().q != r.q) {      // (a query's pairs are consecutive: it lives in one slice)
+							cs.q_comp.insert(cs.q_comp.end(), qs[r.q].comp, qs[r.q].comp + 20);
+							cs.q_true_aa.push_back(qs[r.q].true_aa);
+						}
+						cs.pair_of.push_back(Ref{ r.q, cs.q_true_aa.size() - 1 });
+						cs.target.push_back(r.target);
+						cs.qidx.push_back((int32_t)(cs.q_true_aa.size() - 1));
+						cs.toff.push_back(tl[r.target]);
+						cs.tlen.push_back((int32_t)(tl[r.target + 1] - tl[r.target] - 1));
+					}
+					x.new_refs.clear();
+				}
+				const int64_t n_new = (int64_t)cs.pair_of.size();
+				if (before + n_new > 0x7fffffff) return fail(DMND_E_CAP, "dmnd_extend: more than 2^31 adjusted matrices in one call");
+				if (n_new > 0) {
+					if (int rc = dmnd_reserve_matrices(w, before, n_new)) return rc;
+					cs.rule.resize((size_t)n_new); cs.status.resize((size_t)n_new); cs.mat.resize((size_t)n_new); cs.handed.resize((size_t)n_new);
+					double ms = 0;
+					if (int rc = dmnd_cbs_adjust_device(w, *h.cbs_model, h.cbs_mode, cbs_max_its, c->block[DMND_TARGET].as<int8_t>(), (int64_t)cs.q_true_aa.size(), cs.q_comp.data(),
+						cs.q_true_aa.data(), n_new, cs.qidx.data(), cs.toff.data(), cs.tlen.data(), w->adj_matrices.as<int8_t>() + (size_t)before * 32 * 32, nullptr,
+						cs.rule.data(), cs.status.data(), &ms)) return rc;
+					int64_t by_status[4];
+					const int64_t n_handed = cbs_slots_assign(before, n_new, cs.rule.data(), cs.status.data(), cs.mat.data(), cs.handed.data(), by_status);
+					if (n_handed > 0) {
+						// handed-back pairs: rule and table from the host form, patched into their slots before the sweeps are launched
+						cs.patch.resize((size_t)n_handed * 32 * 32); cs.keep.assign((size_t)n_handed, 0); cs.runs.resize((size_t)n_handed);
+						parallel_each(T, [&](int t) {
+							for (int64_t x = n_handed * t / T; x < n_handed * (t + 1) / T; ++x) {
+								const int64_t k = cs.handed[(size_t)x];
+								const QueryState& s = qs[cs.pair_of[(size_t)k].q];
+								const int8_t* tseq = tdata + cs.toff[(size_t)k];
+								const int rule = cbs_rule(*h.cbs_model, h.cbs_mode, s.comp, s.true_aa, tseq, cs.tlen[(size_t)k]);
+								if (rule == CBS_RULE_NONE) { cs.mat[(size_t)k] = -1; continue; }
+								cs.keep[(size_t)x] = 1;
+								cbs_target_matrix(*h.cbs_model, rule, s.comp, s.true_aa, tseq, cs.tlen[(size_t)k], cs.patch.data() + (size_t)x * 32 * 32);
+							}
+						});
+						const int64_t n_runs = cbs_patch_runs(before, cs.handed.data(), cs.keep.data(), n_handed, cs.runs.data());
+						for (int64_t r = 0; r < n_runs; ++r)
+							HIP_TRY(hipMemcpyAsync(w->adj_matrices.as<int8_t>() + (size_t)cs.runs[(size_t)r].first_slot * 32 * 32, cs.patch.data() + (size_t)cs.runs[(size_t)r].first_patch * 32 * 32,
+								(size_t)cs.runs[(size_t)r].n * 32 * 32, hipMemcpyHostToDevice, w->stream));
+						HIP_TRY(sync_stream(w->stream));
+					}
+					for (int64_t k = 0; k < n_new; ++k) qs[cs.pair_of[(size_t)k].q].mat_of[cs.target[(size_t)k]] = cs.mat[(size_t)k];
+					w->cbs_dev_stats[0] += (double)n_new;
+					for (int k = 0; k < 4; ++k) w->cbs_dev_stats[1 + k] += (double)by_status[k];
+					w->cbs_dev_stats[5] += ms;
+				}
+			}
+			else if (adjust) {
 				// the step's new matrices get their numbers (slice order) and go to the device behind the ones already there
 				const int64_t before = w->n_adj_matrices;
 				int64_t next = before;
@@ -1446,6 +1521,8 @@ extern "C" int dmnd_extend(dmnd_ctx* c, const int8_t* qdata, const int8_t* tdata
 	threads = std::max(1, threads);
 	for (double& x : c->ext_stats) x = 0;
 	for (double& x : c->host_ms) x = 0;
+	for (double& x : c->cbs_dev_stats) x = 0;
+	for (dmnd_ctx* a : c->aux) for (double& x : a->cbs_dev_stats) x = 0;
 	auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
 	double t_mark = now();
 	g_extend_t0 = t_mark;
@@ -1567,7 +1644,8 @@ extern "C" int dmnd_extend(dmnd_ctx* c, const int8_t* qdata, const int8_t* tdata
 		// A block pair of 1e5-1e6 queries would ask for tens of GB of matrices in one call. So the queries go through in passes
 		// of at most DMND_CBS_PASS_HITS seed hits (default 2 M: a pair needs a seed hit, so <= 2 GB of matrices, in practice a tenth);
 		// a pass frees its matrices (extend_range starts from none). The result does not depend on the cut: queries are independent.
-		static const int64_t pass_hits = [] { const char* e = std::getenv("DMND_CBS_PASS_HITS"); return e ? std::max<int64_t>(1, std::atoll(e)) : (int64_t)2 << 20; }();
+		// (read per call, like DMND_CBS_DEVICE: a test runs one block pair with several cuts in one process)
+		const int64_t pass_hits = [] { const char* e = std::getenv("DMND_CBS_PASS_HITS"); return e ? std::max<int64_t>(1, std::atoll(e)) : (int64_t)2 << 20; }();
 		int64_t t_used = 0;
 		double stats[12] = { 0 };
 		for (size_t b = 0; b < qr_run.size() && rcs[0] == DMND_OK;) {

@@ -86,7 +86,7 @@ EXPORTS = ["dmnd_abi_version", "dmnd_last_error", "dmnd_default_params", "dmnd_c
            "dmnd_seed_params_set_query_indexed", "dmnd_auto_query_indexed", "dmnd_set_motif_table", "dmnd_motif_table_size",
            "dmnd_soft_mask_block", "dmnd_download_block", "dmnd_seg_mask_block_device", "dmnd_seg_mask_sequences_device", "dmnd_seg_ranges_device", "dmnd_seg_device_stats", "dmnd_output_fields", "dmnd_format_fields", "dmnd_format_pairwise_intro", "dmnd_format_pairwise",
            "dmnd_format_paf", "dmnd_device_count", "dmnd_set_top_percent", "dmnd_join_blocks_top", "dmnd_set_filters", "dmnd_format_sam", "dmnd_set_query_source_lengths", "dmnd_format_fields_unaligned", "dmnd_format_fields_header", "dmnd_set_query_index_reuse", "dmnd_set_no_self_hits", "dmnd_matrix_params", "dmnd_masking_lambda", "dmnd_translate_opts", "dmnd_set_extension_mode", "dmnd_format_xml_header", "dmnd_format_xml_query_intro", "dmnd_format_xml", "dmnd_format_xml_query_epilog", "dmnd_format_daa_header", "dmnd_format_daa_query", "dmnd_format_daa_match", "dmnd_seg_ranges", "dmnd_seg_mask_block", "dmnd_seg_lnfact", "dmnd_daa_match_read", "dmnd_hsp_from_transcript", "dmnd_hsp_from_transcript_frames", "dmnd_set_format_flags", "dmnd_host_alloc", "dmnd_host_free", "dmnd_share_block", "dmnd_copy_block", "dmnd_init", "dmnd_seed_reserve", "dmnd_mask_sequences", "dmnd_set_max_hsps", "dmnd_rank_targets", "dmnd_rank_update", "dmnd_set_global_ranking", "dmnd_rank_targets_device", "dmnd_rank_device_stats", "dmnd_seed_hit_count", "dmnd_set_seed_hits_resident",
-           "dmnd_upload_matrices", "dmnd_frameshift_swipe", "dmnd_set_frameshift", "dmnd_set_context_motif_table", "dmnd_cbs_composition", "dmnd_cbs_rule", "dmnd_cbs_target_matrix", "dmnd_cbs_ideal_lambda", "dmnd_join_blocks_range", "dmnd_join_blocks_device", "dmnd_join_blocks_device_host", "dmnd_join_ranks", "dmnd_join_ranks_plan", "dmnd_xdrop_ungapped"]
+           "dmnd_upload_matrices", "dmnd_frameshift_swipe", "dmnd_set_frameshift", "dmnd_set_context_motif_table", "dmnd_cbs_composition", "dmnd_cbs_rule", "dmnd_cbs_target_matrix", "dmnd_cbs_ideal_lambda", "dmnd_cbs_target_matrices_device", "dmnd_cbs_device_stats", "dmnd_join_blocks_range", "dmnd_join_blocks_device", "dmnd_join_blocks_device_host", "dmnd_join_ranks", "dmnd_join_ranks_plan", "dmnd_xdrop_ungapped"]
 
 
 def set_motif_table(codes):
@@ -882,6 +882,35 @@ class Context:
         out = (ctypes.c_double * 4)()
         self._check(self.lib.dmnd_seg_device_stats(self.h, out))
         return dict(work=int(out[0]), handed_back=int(out[1]), ranges=int(out[2]), kernel_ms=float(out[3]))
+
+    def cbs_target_matrices_device(self, mode, query_comp, query_true_aa, targets, matrices=None, with_scores=False):
+        """The matrix adjustment of --comp-based-stats 2 - 5 on the device (dmnd_cbs_target_matrices_device), pair k = (query_comp[k],
+        query_true_aa[k]) against targets[k] (a list of int8 arrays). No host fallback. Returns (rule int32[n], status uint8[n] -- 0 = the
+        device decided, 1 / 2 / 3 = handed back by the rounding, iteration, rule guard --, matrices int8[n, 32, 32] -- written where status
+        is 0 and rule is 4, otherwise as passed in `matrices` (zeros if None) -- [, scores float64[n, 21, 21], NaN where none])."""
+        n = len(targets)
+        qc = np.ascontiguousarray(query_comp, dtype=np.float64).reshape(n, 20)
+        aa = np.ascontiguousarray(query_true_aa, dtype=np.int32).reshape(n)
+        seqs = [np.ascontiguousarray(t, dtype=np.int8) for t in targets]
+        off = np.zeros(n + 1, np.int64)
+        off[1:] = np.cumsum([len(t) for t in seqs])
+        cat = np.concatenate(seqs) if n and off[-1] else np.zeros(1, np.int8)
+        rule, status = np.full(n, 99, np.int32), np.full(n, 99, np.uint8)
+        m = np.zeros((n, 32, 32), np.int8) if matrices is None else np.ascontiguousarray(matrices, dtype=np.int8).reshape(n, 32, 32).copy()
+        sc = np.full((n, 21, 21), np.nan) if with_scores else None
+        v = ctypes.c_void_p
+        self.lib.dmnd_cbs_target_matrices_device.argtypes = [v, ctypes.c_int, ctypes.c_int64, v, v, v, v, v, v, v, v]
+        self._check(self.lib.dmnd_cbs_target_matrices_device(self.h, int(mode), n, qc.ctypes.data, aa.ctypes.data, cat.ctypes.data, off.ctypes.data,
+                                                             rule.ctypes.data, status.ctypes.data, m.ctypes.data, sc.ctypes.data if with_scores else None))
+        return (rule, status, m, sc) if with_scores else (rule, status, m)
+
+    def cbs_device_stats(self):
+        """Of the last extend() in modes 2 - 5: dict(pairs=offered to the kernel, device=decided there, rounding / iterations / rule=handed
+        back to the host by that guard (rule: with every lambda-rescaling pair of mode 5), kernel_ms)."""
+        self.lib.dmnd_cbs_device_stats.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        out = (ctypes.c_double * 6)()
+        self._check(self.lib.dmnd_cbs_device_stats(self.h, out))
+        return dict(pairs=int(out[0]), device=int(out[1]), rounding=int(out[2]), iterations=int(out[3]), rule=int(out[4]), kernel_ms=float(out[5]))
 
     def soft_mask_block(self, which):
         """Motif soft masking of the uploaded block (after mask_block): builds the view that seeds are generated from; the

@@ -492,6 +492,28 @@ int dmnd_cbs_composition(const int8_t* seq, int32_t len, double* comp20, int32_t
 int dmnd_cbs_rule(const dmnd_params* params, int mode, const double* query_comp20, int32_t query_true_aa, const int8_t* target, int32_t target_len, int32_t* rule);
 int dmnd_cbs_target_matrix(const dmnd_params* params, int rule, const double* query_comp20, int32_t query_true_aa, const int8_t* target, int32_t target_len, int8_t* matrix_out);
 double dmnd_cbs_ideal_lambda(const dmnd_params* params);
+/* The same adjustment on the device (csrc/cbs_kernels.hip; arithmetic and lane schedule shared with the CPU emulator in
+ * csrc/cbs_core.h): one wavefront per pair computes the target's composition, the rule (Stats::adjust_matrix) and, for
+ * rule 4, the table (Stats::TargetMatrix::TargetMatrix, CompositionMatrixAdjust, Blast_OptimizeTargetFrequencies). dmnd_extend uses
+ * it for the pairs of every planning step in modes 2 - 5 (DMND_CBS_DEVICE=0: the host form above). The device's log / acos and its
+ * order of addition are not the host's, so a pair whose decisions lie within a guard band of a threshold is NOT decided on the
+ * device: status 1 = an unrounded score within 1e-7 of a .5 boundary, 2 = a convergence test within a relative 1e-3 of the
+ * tolerance / the device's iteration cap (64; DMND_CBS_DEVICE_MAX_ITS=n lowers it, a test hook) reached / no convergence,
+ * 3 = the rule's angle within 1e-7 degrees of its threshold (or its acos argument within 1e-9 of -1), and every pair of rule 0 (the lambda rescaling stays on the host).
+ * dmnd_extend computes those pairs with the host form; status 0 = the device's result stands. Inside dmnd_extend the kernel reads the
+ * targets from the reference block resident on the device, the host form from the caller's tdata: the two must hold the same letters
+ * (masks applied on the device mirrored into the host copy), as dmnd_extend requires anyway.
+ *   dmnd_cbs_target_matrices_device: the kernel on n uploaded pairs, with the matrix of ctx's parameters. query_comp20 = n x 20,
+ *     query_true_aa = n, targets = the target letters concatenated, target_off = n + 1 offsets into them. rule_out (n) and
+ *     status_out (n) are always written. matrices_out (n x 1024, host) receives the table of every pair with status 0 and rule 4
+ *     and is left untouched elsewhere: no host fallback here, a caller sees what the device itself produced. scores_out (may be
+ *     NULL; n x 21 x 21 doubles, [query letter][target letter], index 20 = the mask letter): the unrounded scores of the pairs
+ *     whose optimisation converged on the device, NaN elsewhere.
+ *   dmnd_cbs_device_stats: of the last dmnd_extend -- out[0] = pairs offered to the kernel, out[1] = pairs whose result the
+ *     device decided, out[2..4] = pairs handed back by status 1, 2, 3, out[5] = kernel milliseconds. */
+int dmnd_cbs_target_matrices_device(dmnd_ctx* ctx, int mode, int64_t n, const double* query_comp20, const int32_t* query_true_aa,
+	const int8_t* targets, const int64_t* target_off, int32_t* rule_out, uint8_t* status_out, int8_t* matrices_out, double* scores_out);
+int dmnd_cbs_device_stats(const dmnd_ctx* ctx, double out[6]);
 /* The part of the sensitivity that the extension stage reads: the band widths around a chain (Extension::Mode::BANDED_FAST up to
  * --sensitive, BANDED_SLOW from --more-sensitive up: src/align/extend.cpp:62-75, gapped_score.cpp:41-73), and ranking_chunk_size's
  * unit of reference-block letters (2e9, or 8e8 from --very-sensitive up: extend.cpp:79-92). */

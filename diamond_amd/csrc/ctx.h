@@ -210,12 +210,12 @@ struct dmnd_ctx {
 	uint64_t query_generation = 0;             // bumped whenever the query block or its masks change
 	uint64_t target_generation = 0;            // bumped whenever the reference block's letters, limits, soft-mask view or alias change
 	// sliced long-seed stream (seed_slices_core.h, seed_ref_state.h): what a block generation's searches keep of the reference side -- the
-	// class nibbles and, per shape, the windows of every level-1 filter slice. Built by the second search with the same key, released
-	// with the block.
+	// class nibbles and, per shape, the windows of every level-1 filter slice with hash a of each window's key beside it, in list order.
+	// Built by the second search with the same key, released with the block.
 	dmnd::SeedRefState seed_ref;
 	int64_t seed_last_joined = -1;             // joined reference positions (all shapes) of the context's last seed search; -1: none since a block changed
-	dmnd::DevBuf seed_ref_codes, seed_ref_lists, seed_ref_counts;
-	void release_seed_ref_buffers() { seed_ref_codes.release(); seed_ref_lists.release(); seed_ref_counts.release(); }
+	dmnd::DevBuf seed_ref_codes, seed_ref_lists, seed_ref_hashes, seed_ref_counts;
+	void release_seed_ref_buffers() { seed_ref_codes.release(); seed_ref_lists.release(); seed_ref_hashes.release(); seed_ref_counts.release(); }
 	void release_seed_ref() { release_seed_ref_buffers(); seed_ref.seen = 0; seed_ref.key.clear(); }
 	uint64_t cbs_generation = ~(uint64_t)0;    // query_generation the Hauser bias in `cbs` was computed for by dmnd_extend (all sequences); ~0: none / someone else's
 	std::string qindex_signature;              // what the resident query seed index was built for (empty: nothing resident)

@@ -687,7 +687,7 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 			&& (force == 1 || (t_end - t_begin >= min_letters && sparse_filter && c->seed_last_joined <= tuning().seed_slices_max_joined));
 		const int8_t* tseed = c->soft_valid[DMND_TARGET] ? c->soft[DMND_TARGET].as<int8_t>() : c->block[DMND_TARGET].as<int8_t>();
 		bool drop = false;
-		ref_use = seed_ref_decide(c->seed_ref, seed_ref_key_of(c->target_generation, tseed, t_begin, t_end, sp, slice_bits), force, eligible, seed_ref_cache_bytes(t_begin, t_end, S), budget, &drop);
+		ref_use = seed_ref_decide(c->seed_ref, seed_ref_key_of(c->target_generation, tseed, t_begin, t_end, sp, slice_bits), force, eligible, seed_ref_cache_bytes(t_begin, t_end, S) + seed_ref_hash_bytes(t_begin, t_end, S), budget, &drop);
 		if (drop) c->release_seed_ref_buffers();            // (nothing on the stream reads them: the last search has been waited for; the state is seed_ref_decide's)
 		if (ref_use == SEED_REF_BUILT) {
 			// class nibbles (kept), flags and routing bytes (scratch of the build), then per shape one radix pass into its lists.
@@ -703,14 +703,18 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 				return true;
 			};
 			bool ok = exact(c->seed_ref_codes, (size_t)n_groups * sizeof(uint64_t)) && c->seed_tflags.ensure((size_t)n_groups * sizeof(uint32_t)) == DMND_OK
-				&& exact(c->seed_ref_lists, (size_t)S * (size_t)ref_windows * sizeof(uint32_t)) && exact(c->seed_ref_counts, (size_t)S * 64 * sizeof(uint32_t))
+				&& exact(c->seed_ref_lists, (size_t)S * (size_t)ref_windows * sizeof(uint32_t)) && exact(c->seed_ref_hashes, (size_t)S * (size_t)ref_windows * sizeof(uint32_t))
+				&& exact(c->seed_ref_counts, (size_t)S * 64 * sizeof(uint32_t))
 				&& exact(route[0], (size_t)ref_windows) && exact(route[1], (size_t)ref_windows);
 			if (ok) {
 				tm.start();
 				hipError_t e = launch_seed_codes(sp, tseed, t_begin, t_end, c->seed_ref_codes.as<uint64_t>(), c->seed_tflags.as<uint32_t>(), nullptr, st);
-				for (int sid = 0; sid < S && e == hipSuccess; ++sid)
+				for (int sid = 0; sid < S && e == hipSuccess; ++sid) {
+					uint32_t* list = c->seed_ref_lists.as<uint32_t>() + (size_t)sid * (size_t)ref_windows;
 					e = launch_seed_route(sp, sid, c->seed_ref_codes.as<uint64_t>(), c->seed_tflags.as<uint32_t>(), t_begin, t_end, slice_bits, route[0].as<uint8_t>(), route[1].as<uint8_t>(),
-						c->seed_ref_lists.as<uint32_t>() + (size_t)sid * (size_t)ref_windows, c->seed_ref_counts.as<uint32_t>() + (size_t)sid * 64, &c->sort_tmp, &c->sort_tmp_bytes, st);
+						list, c->seed_ref_counts.as<uint32_t>() + (size_t)sid * 64, &c->sort_tmp, &c->sort_tmp_bytes, st);
+					if (e == hipSuccess) e = launch_seed_ref_hashes(sp, sid, c->seed_ref_codes.as<uint64_t>(), list, t_begin, t_end, c->seed_ref_hashes.as<uint32_t>() + (size_t)sid * (size_t)ref_windows, st);
+				}
 				tm.stop(c->seed_ms[0]);
 				if (e == hipSuccess) e = sync_stream(st);          // the scratch goes away below
 				if (e != hipSuccess) { route[0].release(); route[1].release(); c->release_seed_ref(); HIP_TRY(e); }
@@ -725,7 +729,7 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 	auto stream_shape = [&](const SeedArgs& a, int sid) -> hipError_t {
 		if (ref_use == SEED_REF_NONE) return launch_seed_stream(a, sid, st);
 		return launch_seed_stream_slices(a, sid, c->seed_ref_codes.as<uint64_t>(), c->seed_ref_lists.as<uint32_t>() + (size_t)sid * (size_t)ref_windows,
-			c->seed_ref_counts.as<uint32_t>() + (size_t)sid * 64, slice_bits, st);
+			c->seed_ref_hashes.as<uint32_t>() + (size_t)sid * (size_t)ref_windows, c->seed_ref_counts.as<uint32_t>() + (size_t)sid * 64, slice_bits, st);
 	};
 	// the query side of one shape: built (table, position lists, bitmaps), or -- kept from an earlier call -- its marks reset
 	auto query_side = [&](const SeedArgs& a, int sid, bool build) -> int {
@@ -1188,7 +1192,7 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 		for (int sid = 0; sid < S && (size_t)(S + sid) < c->seed_trace.size(); ++sid) std::fprintf(stderr, " %llu", c->seed_trace[S + sid]);
 		std::fprintf(stderr, " | hits %lld | ms index %.2f stream %.2f mask %.2f pairs %.2f | path: %s\n", (long long)c->n_seed_hits, c->seed_ms[0], c->seed_ms[1], c->seed_ms[2], c->seed_ms[3], path);
 		// which stream ran, and what this call did about the reference cache (its own line: the one above ends with the path)
-		const size_t held = c->seed_ref_codes.cap + c->seed_ref_lists.cap + c->seed_ref_counts.cap;
+		const size_t held = c->seed_ref_codes.cap + c->seed_ref_lists.cap + c->seed_ref_hashes.cap + c->seed_ref_counts.cap;
 		if (ref_use == SEED_REF_NONE) std::fprintf(stderr, "dmnd_seed_search: stream: plain, reference cache: none, %zu bytes held\n", held);
 		else std::fprintf(stderr, "dmnd_seed_search: stream: slices (%d x %g KB), reference cache: %s, %zu bytes held\n", 1 << slice_bits, (double)(bm1_words >> slice_bits) * 4 / 1024, ref_use == SEED_REF_BUILT ? "built" : "kept", held);
 	}

@@ -134,8 +134,10 @@ bool seed_stream_can_fuse(const SeedParams& c);
 // the windows per slice; route / route_sorted: one byte per window each, scratch. Spaced nibble-mode shapes, fewer than 2^31 windows.
 hipError_t launch_seed_route(const SeedParams& c, int sid, const uint64_t* codes, const uint32_t* flags, int64_t t_begin, int64_t t_end, int slice_bits,
 	uint8_t* route, uint8_t* route_sorted, uint32_t* list, uint32_t* counts, void** tmp, size_t* tmp_bytes, hipStream_t st);
+// ... and beside every list entry hash a of its window's key (seed_ref_hash_entry): hashes receives seed_ref_windows words, in list order
+hipError_t launch_seed_ref_hashes(const SeedParams& c, int sid, const uint64_t* codes, const uint32_t* list, int64_t t_begin, int64_t t_end, uint32_t* hashes, hipStream_t st);
 // launch_seed_stream's work for a search without key classes, from that routing: the same joined positions, in another order
-hipError_t launch_seed_stream_slices(const SeedArgs& a, int sid, const uint64_t* codes, const uint32_t* list, const uint32_t* counts, int slice_bits, hipStream_t st);
+hipError_t launch_seed_stream_slices(const SeedArgs& a, int sid, const uint64_t* codes, const uint32_t* list, const uint32_t* hashes, const uint32_t* counts, int slice_bits, hipStream_t st);
 // n_matched >= 0: the number of joined positions in a.matched_* (few of them: the kernel walks that list instead of the table)
 hipError_t launch_seed_mask(const SeedArgs& a, int sid, hipStream_t st, int64_t n_matched = -1);
 hipError_t launch_seed_pairs(const SeedArgs& a, int sid, int64_t n_matched, hipStream_t st);

@@ -851,27 +851,28 @@ __global__ __launch_bounds__(256) void seed_stream_fast_kernel(SeedArgs a, int s
 // The plain stream sends one 4-byte level-1 probe per window to L2, each lane's its own request, and runs at the rate the L2s accept
 // requests. Here a workgroup loads ONE slice of the filter into LDS and walks the list of the windows whose keys fall into that
 // slice (the routing, built once per uploaded reference block: seed_route_kernel + one stable radix pass): the probe is an LDS read,
-// and what goes to L2 is coalesced -- the list (4 bytes per window, consecutive) and the class nibbles of windows that lie some 2^b
-// letters apart (16 bytes per window out of neighbouring lines).
-// Workgroup w serves slice w mod 2^b and the (w >> b)-th share of its list; no workgroup waits for another. The shares of all slices
-// cover the same stretch of the block at the same time, so a line of nibbles is pulled into an XCD's L2 once for its slices.
+// and what goes to L2 is a coalesced stream -- per window the list entry and hash a of the window's key (seed_ref_hash_kernel: without
+// key classes word and bits of the probe are functions of that hash alone), 16 bytes per lane and load each. The class nibbles are
+// gathered for the level-1 positives only, which need the key for level 2 and the table.
+// Workgroup w serves slice w mod 2^b and the (w >> b)-th share of its list; no workgroup waits for another.
 // One workgroup of 16 wavefronts fits a CU beside the slice, so nothing in the loop may make a wavefront wait for the others: behind
 // the slice load there is no workgroup barrier (a barrier also drains the loads a wavefront has requested ahead). Every wavefront
 // keeps its own queue of level-1 positives and its own staging area in LDS, addressed with ballots instead of atomics:
-//  * list entries are requested two rounds ahead and nibbles one round ahead of the round whose keys are hashed and probed;
-//  * level-1 positives (3.1 % of the windows with C2's 3 MB filter and three bits per seed, 9.7 % with 2 MB and two: seed_sizes) are queued, and 64 of them at a time take the plain kernel's path -- level-2 bitmap,
+//  * list entries and hashes are requested SEED_SLICE_DEPTH rounds ahead of the round that is probed (C2's blocks, kernel alone: 0.709 ms
+//    at 2 rounds, 0.696 at 4, 0.697 at 8);
+//  * level-1 positives (3.1 % of the windows with C2's 3 MB filter and three bits per seed, 9.7 % with 2 MB and two: seed_sizes) are queued by
+//    their window offsets, and 64 of them at a time form their keys from the nibbles and take the plain kernel's path -- level-2 bitmap,
 //    table, SLOT_JOINED -- with all lanes busy, instead of a chain of dependent reads in the few lanes that found one;
 //  * joins are staged and go out with one matched_count atomic per flush; direct append when the staging area is full.
 // Spaced seeds only (hashed seeds stay on the plain kernel: their windows with a mask / stop letter are keyed from the raw letters).
-enum { SEED_SLICE_THREADS = 1024, SEED_SLICE_BATCH = 4, SEED_SLICE_QUEUE = 128, SEED_SLICE_STAGE = 32 };
+enum { SEED_SLICE_THREADS = 1024, SEED_SLICE_BATCH = 4, SEED_SLICE_DEPTH = 4, SEED_SLICE_QUEUE = 128, SEED_SLICE_STAGE = 32 };
 __global__ __launch_bounds__(SEED_SLICE_THREADS) void seed_stream_slices_kernel(SeedArgs a, int64_t base, uint64_t care64, const uint64_t* __restrict__ codes,
-	const uint32_t* __restrict__ list, const uint32_t* __restrict__ counts, int slice_bits, uint32_t slice_words)
+	const uint32_t* __restrict__ list, const uint32_t* __restrict__ hashes, const uint32_t* __restrict__ counts, int slice_bits, uint32_t slice_words)
 {
-	constexpr int B = SEED_SLICE_BATCH;                       // windows of a thread per round
+	constexpr int B = SEED_SLICE_BATCH, DEPTH = SEED_SLICE_DEPTH;      // windows of a thread per round; rounds requested ahead
 	constexpr unsigned WAVES = SEED_SLICE_THREADS / 64, QW = SEED_SLICE_QUEUE, ST = SEED_SLICE_STAGE;
 	static_assert(QW >= 128, "a wavefront queues up to 63 + 64 positives before it probes 64");
 	__shared__ uint32_t slice[SEED_SLICE_MAX_WORDS];
-	__shared__ uint64_t q_key[WAVES][QW];
 	__shared__ uint32_t q_off[WAVES][QW];
 	__shared__ uint32_t st_slot[WAVES][ST], st_off[WAVES][ST];
 	const unsigned s = blockIdx.x & ((1u << slice_bits) - 1), share = blockIdx.x >> slice_bits, shares = gridDim.x >> slice_bits;
@@ -931,63 +932,59 @@ __global__ __launch_bounds__(SEED_SLICE_THREADS) void seed_stream_slices_kernel(
 		sn += (unsigned)__builtin_popcountll(jb);
 		if (sn >= ST / 2) flush();
 	};
-	const uint64_t stride = (uint64_t)B * blockDim.x;
-	auto entries = [&](uint64_t k0, uint32_t* o) {
-#pragma unroll
-		for (int j = 0; j < B; ++j) {
-			const uint64_t k = k0 + (uint64_t)j * blockDim.x + threadIdx.x;
-			o[j] = k < hi ? list[k] : 0xffffffffu;
+	// a queued positive: the key of its window from the nibbles, then `probe`
+	auto probe_queued = [&](bool active, uint32_t e) {
+		const uint32_t off = active ? e : 0u;
+		const uint64_t seed = seed_window_key(codes[off >> 4], codes[(off >> 4) + 1], off & 15u, care64);
+		probe(active, seed, off);
+	};
+	// Rounds of B consecutive entries per lane, one 16-byte load each, from the list's last multiple of B at or below lo (the lists of
+	// a shape start at a multiple of 16 entries and end at one: the loads are aligned and stay inside); what lies outside [lo, hi)
+	// is dropped by `pass`. DEPTH rounds are requested ahead of the one that is probed.
+	typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+	static_assert(B == 4, "one 16-byte load per round");
+	const uint64_t stride = (uint64_t)B * blockDim.x, first = (lo & ~(uint64_t)(B - 1)) + (uint64_t)B * threadIdx.x;
+	u32x4 hv[DEPTH], ov[DEPTH];
+	auto request = [&](uint64_t k, u32x4& h, u32x4& o) {
+		h = 0; o = 0;
+		if (k < hi) {
+			h = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(hashes + k));
+			o = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(list + k));
 		}
 	};
-	auto nibbles = [&](const uint32_t* o, uint64_t* c0, uint64_t* c1) {
 #pragma unroll
-		for (int j = 0; j < B; ++j) {
-			const uint32_t g = o[j] == 0xffffffffu ? 0u : o[j] >> 4;
-			c0[j] = codes[g]; c1[j] = codes[g + 1];
-		}
-	};
-	uint32_t off[B], off1[B], off2[B];
-	uint64_t c0[B], c1[B], n0[B], n1[B];
-	entries(lo, off);
-	entries(lo + stride, off1);
-	nibbles(off, c0, c1);
-	for (uint64_t k0 = lo; k0 < hi; k0 += stride) {
-		entries(k0 + 2 * stride, off2);
-		nibbles(off1, n0, n1);
+	for (int d = 0; d < DEPTH; ++d) request(first + (uint64_t)d * stride, hv[d], ov[d]);
+	for (uint64_t k0 = first; k0 < hi + (uint64_t)B * threadIdx.x; k0 += (uint64_t)DEPTH * stride) {      // (workgroup-uniform trip count: k0 - B * threadIdx.x < hi)
 #pragma unroll
-		for (int j = 0; j < B; ++j) {
-			const int sh = (int)(off[j] & 15u) * 4;
-			const uint64_t key = (sh == 0 ? c0[j] : (c0[j] >> sh) | (c1[j] << (64 - sh))) & care64;
-			const uint32_t h = seed_hash_a(key);
-			// inside the slice by the slice identity (seed_slices_core.h; the launch checks its conditions). The clamp below is for the
-			// padding entries behind the end of the list (0xffffffff: their key is of group 0 and may fall into any slice), which `pass` drops
-			const uint32_t lw = a.bm1_index(h, key) - word0;
-			const uint32_t bw = slice[lw < slice_words ? lw : 0u], need = bm1_bits(h, a.bitmap1_k3);
-			const bool pass = off[j] != 0xffffffffu && (bw & need) == need;
-			const unsigned long long pb = __ballot(pass);
-			if (pb) {
-				if (pass) { const unsigned k = qn + rank_in(pb); q_key[wave][k] = key; q_off[wave][k] = off[j]; }
-				qn += (unsigned)__builtin_popcountll(pb);
-				if (qn >= 64) {                                      // (wavefront-uniform)
-					wave_sync();
-					qn -= 64;
-					const uint64_t seed = q_key[wave][qn + lane];
-					const uint32_t o = q_off[wave][qn + lane];
-					wave_sync();
-					probe(true, seed, o);
+		for (int d = 0; d < DEPTH; ++d) {
+			const u32x4 h4 = hv[d], o4 = ov[d];
+			const uint64_t k = k0 + (uint64_t)d * stride;
+			request(k + (uint64_t)DEPTH * stride, hv[d], ov[d]);
+#pragma unroll
+			for (int j = 0; j < B; ++j) {
+				const uint32_t h = h4[j];
+				// inside the slice by the slice identity (seed_slices_core.h; the launch checks its conditions). The clamp below is for
+				// the entries outside [lo, hi) (another slice's, or none), which `pass` drops
+				const uint32_t lw = seed_slice_word(h, a.bm1_hmask, a.bitmap1_words) - word0;
+				const uint32_t bw = slice[lw < slice_words ? lw : 0u], need = bm1_bits(h, a.bitmap1_k3);
+				const bool pass = k + j >= lo && k + j < hi && (bw & need) == need;
+				const unsigned long long pb = __ballot(pass);
+				if (pb) {
+					if (pass) q_off[wave][qn + rank_in(pb)] = o4[j];
+					qn += (unsigned)__builtin_popcountll(pb);
+					if (qn >= 64) {                                      // (wavefront-uniform)
+						wave_sync();
+						qn -= 64;
+						const uint32_t e = q_off[wave][qn + lane];
+						wave_sync();
+						probe_queued(true, e);
+					}
 				}
 			}
 		}
-#pragma unroll
-		for (int j = 0; j < B; ++j) { off[j] = off1[j]; off1[j] = off2[j]; c0[j] = n0[j]; c1[j] = n1[j]; }
 	}
 	wave_sync();
-	{
-		const bool active = lane < qn;
-		const uint64_t seed = active ? q_key[wave][lane] : 0;
-		const uint32_t o = active ? q_off[wave][lane] : 0;
-		probe(active, seed, o);
-	}
+	probe_queued(lane < qn, lane < qn ? q_off[wave][lane] : 0u);
 	if (sn) flush();
 }
 
@@ -2035,7 +2032,7 @@ hipError_t launch_seed_route(const SeedParams& c, int sid, const uint64_t* codes
 	return hipGetLastError();
 }
 
-hipError_t launch_seed_stream_slices(const SeedArgs& a, int sid, const uint64_t* codes, const uint32_t* list, const uint32_t* counts, int slice_bits, hipStream_t st)
+hipError_t launch_seed_stream_slices(const SeedArgs& a, int sid, const uint64_t* codes, const uint32_t* list, const uint32_t* hashes, const uint32_t* counts, int slice_bits, hipStream_t st)
 {
 	const SeedParams& c = a.params;
 	if (a.classes || a.fused || !seed_nibble_mode(c, sid) || c.seed_encoding != SEED_SPACED || slice_bits < 0 || slice_bits > SEED_SLICE_MAX_BITS) return hipErrorInvalidValue;
@@ -2048,8 +2045,24 @@ hipError_t launch_seed_stream_slices(const SeedArgs& a, int sid, const uint64_t*
 	if (e != hipSuccess) return e;
 	n_cus = std::max(n_cus, 1);
 	const unsigned slices = 1u << slice_bits, shares = std::max(1u, (unsigned)n_cus / slices);
-	hipLaunchKernelGGL(seed_stream_slices_kernel, dim3(slices * shares), dim3(SEED_SLICE_THREADS), 0, st, a, a.t_begin & ~(int64_t)15, care64_of(c, sid), codes, list, counts, slice_bits,
-		a.bitmap1_words >> slice_bits);
+	hipLaunchKernelGGL(seed_stream_slices_kernel, dim3(slices * shares), dim3(SEED_SLICE_THREADS), 0, st, a, a.t_begin & ~(int64_t)15, care64_of(c, sid), codes, list, hashes,
+		counts, slice_bits, a.bitmap1_words >> slice_bits);
+	return hipGetLastError();
+}
+
+// hash a of the key of every list entry's window, in list order (seed_ref_hash_entry)
+__global__ __launch_bounds__(256) void seed_ref_hash_kernel(const uint64_t* __restrict__ codes, const uint32_t* __restrict__ list, int64_t n, uint64_t care64, uint32_t* __restrict__ hashes)
+{
+	const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (k < n) hashes[k] = seed_ref_hash_entry(codes, list[k], care64);
+}
+
+hipError_t launch_seed_ref_hashes(const SeedParams& c, int sid, const uint64_t* codes, const uint32_t* list, int64_t t_begin, int64_t t_end, uint32_t* hashes, hipStream_t st)
+{
+	if (!seed_nibble_mode(c, sid) || c.seed_encoding != SEED_SPACED) return hipErrorInvalidValue;
+	const int64_t n = seed_ref_windows(t_begin, t_end);
+	if (n <= 0 || n >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
+	hipLaunchKernelGGL(seed_ref_hash_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, st, codes, list, n, care64_of(c, sid), hashes);
 	return hipGetLastError();
 }
 

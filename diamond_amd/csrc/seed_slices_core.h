@@ -33,6 +33,23 @@ DMND_HD int seed_slice_bits(uint64_t words, int slot_bits, uint32_t max_words)
 // slice of a key's hash a
 DMND_HD uint32_t seed_slice_of(uint32_t h, int slice_bits) { return slice_bits ? h >> (32 - slice_bits) : 0u; }
 
+// Without key classes the level-1 probe of a window is a function of h = seed_hash_a(key) alone -- the word below (bm1_word_of_key
+// for classes = 0) and bm1_bits(h, k3) -- and h is a reference-side fact as the slice is: the cache keeps it beside every list entry
+// (seed_ref_hash_entry), and the stream reads list entry and hash instead of gathering the window's nibbles. Only a window that passes
+// level 1 needs its key again (level-2 word, table): seed_window_key from the kept nibbles.
+DMND_HD uint32_t seed_slice_word(uint32_t h, uint32_t hmask, uint32_t words) { return bm1_word(h & hmask, words); }
+// table key of the window that starts at nibble `at` (0..15) of c0, c0 / c1 the class nibbles of its group of 16 letters and the next
+DMND_HD uint64_t seed_window_key(uint64_t c0, uint64_t c1, uint32_t at, uint64_t care64)
+{
+	const int sh = 4 * (int)at;
+	return (sh == 0 ? c0 : (c0 >> sh) | (c1 << (64 - sh))) & care64;
+}
+// what the cache keeps beside a list entry (window offset `off` from the block's base): hash a of the window's key
+DMND_HD uint32_t seed_ref_hash_entry(const uint64_t* codes, uint32_t off, uint64_t care64)
+{
+	return seed_hash_a(seed_window_key(codes[off >> 4], codes[(off >> 4) + 1], off & 15u, care64));
+}
+
 // The routing bytes of the 16 windows that start in one group of 16 reference letters: slice of the window's key, or SEED_ROUTE_NONE.
 // c0 / c1: class nibbles of this group and the next one (seed_codes_kernel); f0 / f1: their flag words (delimiters low, letters
 // without a class high); first / last: the block's window range relative to the group's first letter. A window is a seed exactly
@@ -45,8 +62,7 @@ DMND_HD void seed_route_group(uint64_t c0, uint64_t c1, uint32_t f0, uint32_t f1
 	for (int w = 0; w < 16; ++w) {
 		const bool inside = w >= first && w < last && ((delim >> w) & span) == 0;
 		const bool ok = inside && ((bad >> w) & care) == 0;
-		const int sh = 4 * w;
-		const uint64_t key = (sh == 0 ? c0 : (c0 >> sh) | (c1 << (64 - sh))) & care64;
+		const uint64_t key = seed_window_key(c0, c1, (uint32_t)w, care64);
 		out[w] = ok ? (uint8_t)seed_slice_of(seed_hash_a(key), slice_bits) : (uint8_t)SEED_ROUTE_NONE;
 	}
 }
@@ -83,6 +99,11 @@ inline uint64_t seed_ref_cache_bytes(int64_t t_begin, int64_t t_end, int n_shape
 {
 	const uint64_t n = (uint64_t)seed_ref_windows(t_begin, t_end);
 	return (uint64_t)n_shapes * (n * sizeof(uint32_t) + 64 * sizeof(uint32_t)) + (n / 16 + 2) * sizeof(uint64_t);
+}
+// ... and for the hashes beside the list entries: per shape one 32-bit word per window more. The budget counts the sum of the two.
+inline uint64_t seed_ref_hash_bytes(int64_t t_begin, int64_t t_end, int n_shapes)
+{
+	return (uint64_t)n_shapes * (uint64_t)seed_ref_windows(t_begin, t_end) * sizeof(uint32_t);
 }
 
 // What a search does about the cache. NONE: the plain stream, nothing built (the first search of a block generation, an ineligible

@@ -2,6 +2,8 @@
 searches with DMND_SEED_SLICES=0 and =1 on the same context, the hits compared.
   python tools/seed_slices_probe.py              C2's block pair (10 000 queries, 100 000 families of 10): the stage gate
   python tools/seed_slices_probe.py --sizes      C2's query block against reference blocks of 100 ... 30 000 families: the threshold
+  python tools/seed_slices_probe.py --libs parent=PATH/libdiamond_hip.so,this=   the stage gate once per library, all loaded into this
+                                                 process one after the other (empty path: this tree's): one object per label
 Prints one JSON object."""
 import json
 import os
@@ -28,9 +30,21 @@ def timed(ctx, sp, n, slices):
 
 
 def main():
+    if "--libs" in sys.argv:
+        out, own = {}, hip.LIB_PATH
+        for item in sys.argv[sys.argv.index("--libs") + 1].split(","):
+            label, _, path = item.partition("=")
+            hip._lib, hip.LIB_PATH = None, path or own
+            out[label] = measure(False)
+        print(json.dumps(out))
+    else:
+        print(json.dumps(measure("--sizes" in sys.argv)))
+
+
+def measure(sizes):
     sp = hip.seed_params_fast(threads=8)
     out = {}
-    if "--sizes" in sys.argv:
+    if sizes:
         _, _, q, qoff = synth.generate(1000, members=10, queries=10_000, seed=20260923)
         qd, ql = workload.sequence_set(q, qoff)
         out["sizes"] = []
@@ -61,7 +75,7 @@ def main():
         out["hits"] = int(len(h0))
         out["hits_equal"] = bool(np.array_equal(h0, h1) and np.array_equal(h0, h2) and np.array_equal(h0, h3))
         ctx.close()
-    print(json.dumps(out))
+    return out
 
 
 if __name__ == "__main__":

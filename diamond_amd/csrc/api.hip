@@ -360,6 +360,7 @@ extern "C" void dmnd_destroy(dmnd_ctx* c)
 	c->cbs_dev.release(); c->cbs_host.release();
 	c->ext_dev.release(); c->ext_trace.release(); c->ext_host.release(); c->ext_ev.release();
 	for (DevBuf& b : c->ext_trace_more) b.release();
+	c->ext_cbs.release();
 	c->ext_tr.release(); c->ext_tr_raw.release(); c->ext_tr_store.release(); c->ext_tr_out.release(); c->ext_source_lens.release();
 	if (c->plan_tmp) { (void)hipFree(c->plan_tmp); c->plan_tmp = nullptr; c->plan_tmp_bytes = 0; }
 	for (int i = 0; i < 2; ++i) { c->up_stage[i].release(); if (c->up_ev[i]) (void)hipEventDestroy(c->up_ev[i]); c->up_ev[i] = nullptr; }
@@ -1067,9 +1068,12 @@ int dmnd_sweep_classes(dmnd_ctx* work, const dmnd_ctx* c, const dmnd_dp_target* 
 	for (int k = 0; k < n_classes; ++k) {
 		const int64_t count = class_count[k];
 		if (count == 0) continue;
-		const int P = class_of_index(k);
+		// classes 16 .. 31 (n_classes = 32: a call of the device half with adjusted matrices, extend_cbs_core.h): the items scored with a
+		// matrix of their own out of the work context's store -- behind all others in the launch order, 32-bit kernels only
+		const bool own = k >= 16;
+		const int P = class_of_index(own ? k - 16 : k);
 		const int64_t per = class_items_per_wave16(P), waves = (count + per - 1) / per;
-		const bool k16 = !force_swipe32() && sw16_class(P) && (int64_t)class_max_steps[k] <= 2 * (int64_t)SW16_MAX_PAIRS;
+		const bool k16 = !own && !force_swipe32() && sw16_class(P) && (int64_t)class_max_steps[k] <= 2 * (int64_t)SW16_MAX_PAIRS;
 		if (row_class(P) && !k16) return fail(DMND_E_ARG, "dmnd_sweep_classes: a row class outside the 16-bit kernels");
 		if (k16) {
 			Swipe16Args a;
@@ -1082,7 +1086,7 @@ int dmnd_sweep_classes(dmnd_ctx* work, const dmnd_ctx* c, const dmnd_dp_target* 
 		}
 		else {
 			SwipeArgs a;
-			a.qblock = c->block[DMND_QUERY].as<int8_t>(); a.tblock = c->block[DMND_TARGET].as<int8_t>(); a.cbs = cbs; a.matrix = c->matrix.as<int8_t>(); a.matrices = nullptr;
+			a.qblock = c->block[DMND_QUERY].as<int8_t>(); a.tblock = c->block[DMND_TARGET].as<int8_t>(); a.cbs = cbs; a.matrix = c->matrix.as<int8_t>(); a.matrices = own ? work->adj_matrices.as<int8_t>() : nullptr;
 			a.items = d_items; a.order = order_dev + s0; a.trace_off = trace_dev ? off_slot_dev + s0 : nullptr; a.trace = trace_dev; a.ends = ends_dev;
 			a.n = count;
 			a.gap_open = c->params.gap_open; a.gap_extend = c->params.gap_extend;

@@ -37,6 +37,22 @@ size_t up8(size_t x) { return (x + 7) & ~(size_t)7; }
 
 }
 
+// The kernel over lists that lie in HBM already (the device half of dmnd_extend lists its pairs there, extend_kernels.h): enqueued on
+// w's stream between w->ev0 and w->ev1, nothing is waited for; rule_dev / status_dev stay on the device.
+int dmnd_cbs_adjust_lists(dmnd_ctx* w, const CbsDevModel* model_dev, int64_t n, const double* comp_dev, const int32_t* true_aa_dev, const int32_t* qidx_dev,
+	const int64_t* toff_dev, const int32_t* tlen_dev, const int8_t* letters_dev, int8_t* tables_dev, double* scores_dev, int32_t* rule_dev, uint8_t* status_dev)
+{
+	if (n <= 0) return DMND_OK;
+	hipStream_t st = w->stream;
+	static const int cus = [] { int d = 0, v = 0; return hipGetDevice(&d) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, d) == hipSuccess && v > 0 ? v : 256; }();
+	const unsigned grid = (unsigned)std::min<int64_t>(n, (int64_t)cus * 6);
+	HIP_TRY(hipEventRecord(w->ev0, st));
+	hipLaunchKernelGGL(cbs_adjust_kernel, dim3(grid), dim3(64), 0, st, model_dev, n, comp_dev, true_aa_dev, qidx_dev, toff_dev, tlen_dev, letters_dev, tables_dev, scores_dev, rule_dev, status_dev);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipEventRecord(w->ev1, st));
+	return DMND_OK;
+}
+
 int dmnd_cbs_adjust_device(dmnd_ctx* w, const CbsModel& model, int mode, int max_its, const int8_t* letters_dev, int64_t n_q, const double* comp, const int32_t* true_aa,
 	int64_t n, const int32_t* qidx, const int64_t* toff, const int32_t* tlen, int8_t* tables_dev, double* scores_dev, int32_t* rule_out, uint8_t* status_out, double* kernel_ms)
 {
@@ -59,14 +75,9 @@ int dmnd_cbs_adjust_device(dmnd_ctx* w, const CbsModel& model, int mode, int max
 	std::memcpy(hs + o_tlen, tlen, (size_t)n * sizeof(int32_t));
 	hipStream_t st = w->stream;
 	HIP_TRY(hipMemcpyAsync(ds, hs, in_bytes, hipMemcpyHostToDevice, st));
-	static const int cus = [] { int d = 0, v = 0; return hipGetDevice(&d) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, d) == hipSuccess && v > 0 ? v : 256; }();
-	const unsigned grid = (unsigned)std::min<int64_t>(n, (int64_t)cus * 6);
-	HIP_TRY(hipEventRecord(w->ev0, st));
-	hipLaunchKernelGGL(cbs_adjust_kernel, dim3(grid), dim3(64), 0, st, reinterpret_cast<const CbsDevModel*>(ds + o_model), n, reinterpret_cast<const double*>(ds + o_comp),
+	if (int rc = dmnd_cbs_adjust_lists(w, reinterpret_cast<const CbsDevModel*>(ds + o_model), n, reinterpret_cast<const double*>(ds + o_comp),
 		reinterpret_cast<const int32_t*>(ds + o_aa), qidx ? reinterpret_cast<const int32_t*>(ds + o_qidx) : nullptr, reinterpret_cast<const int64_t*>(ds + o_toff),
-		reinterpret_cast<const int32_t*>(ds + o_tlen), letters_dev, tables_dev, scores_dev, reinterpret_cast<int32_t*>(ds + o_rule), reinterpret_cast<uint8_t*>(ds + o_status));
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipEventRecord(w->ev1, st));
+		reinterpret_cast<const int32_t*>(ds + o_tlen), letters_dev, tables_dev, scores_dev, reinterpret_cast<int32_t*>(ds + o_rule), reinterpret_cast<uint8_t*>(ds + o_status))) return rc;
 	HIP_TRY(hipMemcpyAsync(hs + o_rule, ds + o_rule, all_bytes - o_rule, hipMemcpyDeviceToHost, st));
 	HIP_TRY(sync_stream(st));
 	std::memcpy(rule_out, hs + o_rule, (size_t)n * sizeof(int32_t));
@@ -82,6 +93,14 @@ int dmnd_cbs_env_max_its()
 {
 	const char* e = std::getenv("DMND_CBS_DEVICE_MAX_ITS");
 	return e ? std::max(0, std::atoi(e)) : 0;
+}
+
+// DMND_CBS_PASS_HITS=n (read per call): seed hits per pass of the host path (extend_host.hip); a pair needs a seed hit, so also
+// the 1 KB matrix slots one pass -- or one call of the device half -- may ask for. Default 2 M: 2 GB of matrices
+int64_t dmnd_cbs_pass_hits()
+{
+	const char* e = std::getenv("DMND_CBS_PASS_HITS");
+	return e ? std::max<int64_t>(1, std::atoll(e)) : (int64_t)2 << 20;
 }
 
 extern "C" int dmnd_cbs_target_matrices_device(dmnd_ctx* c, int mode, int64_t n, const double* query_comp, const int32_t* query_true_aa,

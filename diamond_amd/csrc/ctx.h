@@ -116,7 +116,8 @@ struct dmnd_ctx {
 	dmnd::DevBuf ext_dev, ext_trace;          // device half of dmnd_extend behind the planner (extend_kernels.hip): work arrays, kept traces
 	std::vector<dmnd::DevBuf> ext_trace_more; // ... the kept traces of the ranking chunks behind the first
 	dmnd::DevBuf ext_tr, ext_tr_raw, ext_tr_store, ext_tr_out;      // ... with a transcript arena: the transcript arrays (extend_core.h tr_layout), the raw slots of one walked piece, the store of the kept transcripts, the gathered output
-	dmnd::DevBuf ext_ev;                      // the host's (e-value, bit score) pairs on their way into the device copy of the records
+	dmnd::DevBuf ext_cbs;                     // ... with --comp-based-stats 2 - 5: the arrays of the matrix adjustment step (extend_cbs_core.h ext_cbs_layout)
+	dmnd::DevBuf ext_ev;                    // the host's (e-value, bit score) pairs on their way into the device copy of the records
 	const dmnd_match* ext_records_dev = nullptr; int64_t ext_records_n = -1;      // the records of the last dmnd_extend where they lie in HBM (complete: host e-values in); n = -1: part of them only exists on the host
 	dmnd::PinBuf ext_host;                    // ... its counters, records and query states on the host
 	double ext_filter_stats[2] = { 0, 0 };     // of the last dmnd_extend: records removed by a filter on the device, queries handed back to the host because a filter value lay on its threshold
@@ -273,7 +274,12 @@ int dmnd_reserve_matrices(dmnd_ctx* c, int64_t n_keep, int64_t n);
 // pair k is query qidx[k] (qidx NULL: query k) against the tlen[k] letters at letters_dev + toff[k]. The table of pair k goes to
 // tables_dev + k * 1024 (device), its 21 x 21 unrounded scores to scores_dev + k * 441 (device, may be NULL); rule_out / status_out: host.
 // max_its <= 0: the built-in cap. *kernel_ms: the kernel alone.
-namespace dmnd { struct CbsModel; }
+namespace dmnd { struct CbsModel; struct CbsDevModel; }
+// ... the same kernel over lists that lie in HBM already (every pointer a device pointer; scores_dev may be NULL): enqueued on w's
+// stream between w->ev0 and w->ev1, nothing is waited for and nothing copied
+int dmnd_cbs_adjust_lists(dmnd_ctx* w, const dmnd::CbsDevModel* model_dev, int64_t n, const double* comp_dev, const int32_t* true_aa_dev, const int32_t* qidx_dev,
+	const int64_t* toff_dev, const int32_t* tlen_dev, const int8_t* letters_dev, int8_t* tables_dev, double* scores_dev, int32_t* rule_dev, uint8_t* status_dev);
+int64_t dmnd_cbs_pass_hits();     // DMND_CBS_PASS_HITS (read per call): seed hits of one pass of a --comp-based-stats 2 - 5 call on the host path = 1 KB matrix slots a call may ask for; default 2 M
 int dmnd_cbs_adjust_device(dmnd_ctx* w, const dmnd::CbsModel& model, int mode, int max_its, const int8_t* letters_dev, int64_t n_q, const double* comp, const int32_t* true_aa,
 	int64_t n, const int32_t* qidx, const int64_t* toff, const int32_t* tlen, int8_t* tables_dev, double* scores_dev, int32_t* rule_out, uint8_t* status_out, double* kernel_ms);
 int dmnd_cbs_env_max_its();      // DMND_CBS_DEVICE_MAX_ITS (test hook, read per call); 0 = the built-in cap

@@ -9,6 +9,8 @@
 
 namespace dmnd {
 
+struct CbsModel;
+
 // what the two halves need of the call's configuration (extend_host.hip HostCfg)
 struct DeviceCfg {
 	int gap_open = 11, gap_extend = 1;
@@ -23,7 +25,9 @@ struct DeviceCfg {
 	double top = -1.0;                   // --top: >= 0 = the targets within this percentage of the best bit score, -k plays no part
 	int contexts = 1;                    // 6: translated queries -- the planner groups per read, the records carry the winning frame
 	bool ext_full = false;               // Extension::Mode::FULL: one full-matrix DpTarget per (context, target) unit with a hit (plan_full_kernel); max_swipe_dp is held against query length x target length
-	int global_ranking = 0;              // > 0: the final pass of --global-ranking -- one hit per ranked target, at most this many per query, ONE ranking chunk of that size (extend.cpp:80)
+	int cbs_mode = 1;                    // --comp-based-stats; 2 - 5 with cbs_model: the device half adjusts the matrix of every (query, target) pair it sweeps (cbs_kernels.hip)
+	const CbsModel* cbs_model = nullptr;
+	int global_ranking = 0;            // > 0: the final pass of --global-ranking -- one hit per ranked target, at most this many per query, ONE ranking chunk of that size (extend.cpp:80)
 };
 
 // What the device planner hands over (page-locked host copies of its lists; valid until the context's next dmnd_extend)
@@ -52,7 +56,8 @@ int plan_fetch_lists(dmnd_ctx* c, DevPlan& plan);
 // and a 0 terminator each) are written to it from offset 0 on in record order, hsp.transcript_off of each record points at its own,
 // *transcript_used = their bytes; more than transcript_cap: DMND_E_CAP, nothing written. The records then do not stay in HBM for a
 // join (c->ext_records_dev stays NULL). transcript == NULL: no transcripts, hsp.transcript_off = -1.
+// qdata / tdata: the caller's blocks; read only with h.cbs_model, for the pairs the adjustment kernel hands back to the host form.
 int extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan, int threads, std::vector<dmnd_match>& records, std::vector<uint8_t>& qstate, bool& done,
-	uint8_t* transcript = nullptr, int64_t transcript_cap = 0, int64_t* transcript_used = nullptr);
+	uint8_t* transcript = nullptr, int64_t transcript_cap = 0, int64_t* transcript_used = nullptr, const int8_t* qdata = nullptr, const int8_t* tdata = nullptr);
 
 }  // namespace dmnd

@@ -19,6 +19,8 @@
 #include "extend_kernels.h"
 #include "extend_device.h"
 #include "match_order.h"
+#include "cbs_adjust.h"
+#include "cbs_model.h"
 
 using namespace dmnd;
 
@@ -210,7 +212,8 @@ int dmnd::plan_fetch_lists(dmnd_ctx* c, DevPlan& plan)
 	return DMND_OK;
 }
 
-static bool keep_traces_dev() { static const bool v = [] { const char* e = std::getenv("DMND_EXTEND_KEEP_TRACE"); return !e || e[0] != '0'; }(); return v; }
+// DMND_EXTEND_KEEP_TRACE=0 (read per call, like the hooks above: a test compares both forms in one process): round 1 keeps no trace rows
+static bool keep_traces_dev() { const char* e = std::getenv("DMND_EXTEND_KEEP_TRACE"); return !e || e[0] != '0'; }
 
 // The extension of the planned queries, ranking chunk by ranking chunk, in HBM from the planner's bands to the match records
 // (extend_kernels.h): -k culling by e-value, or -- h.top >= 0 -- the --top culling by score, either with or without the HSP filters.
@@ -219,13 +222,18 @@ static bool keep_traces_dev() { static const bool v = [] { const char* e = std::
 // has to extend the query. done = false: nothing was done here (no eligible query, or the kept traces would not fit the context's
 // trace budget), every query goes to the host path.
 int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan, int threads, std::vector<dmnd_match>& records, std::vector<uint8_t>& qstate, bool& done,
-	uint8_t* transcript, int64_t transcript_cap, int64_t* transcript_used)
+	uint8_t* transcript, int64_t transcript_cap, int64_t* transcript_used, const int8_t* qdata, const int8_t* tdata)
 {
 	done = false;
 	if (transcript_used) *transcript_used = 0;
 	TraceLaps tr("dmnd_extend (device half)");
 	const int64_t chunk = h.ranking_chunk;
 	if (chunk > EXT_MAX_CHUNK || plan.n_bands == 0) return DMND_OK;
+	// --comp-based-stats 2 - 5: every group that is swept owns a 1 KB slot of the context's matrix store until the call ends (g_mat). A
+	// call whose groups could ask for more than one pass of the host path may hold (DMND_CBS_PASS_HITS slots, 2 GB by default) is
+	// left to the host path and its passes as a whole.
+	const bool adjust = h.cbs_model != nullptr && cbs_matrix_adjust(h.cbs_mode);
+	if (adjust && (h.ext_full || h.contexts > 1 || !qdata || !tdata || (int64_t)plan.n_groups > dmnd_cbs_pass_hits())) return DMND_OK;
 	const bool top = h.top >= 0.0;                      // (--top: no LDS list, -k plays no part)
 	if (!top && ((size_t)h.max_target_seqs + 2 * (size_t)chunk) * 24 > ((size_t)60 << 10)) return DMND_OK;      // (the LDS lists of ext_append_kernel)
 	const bool filt = filters_on(h.filters);
@@ -272,6 +280,18 @@ int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan,
 		HIP_TRY(hipMemsetAsync(ta.g_store, 0xff, L.nG * sizeof(int64_t), c->stream));      // (-1: no transcript of the group in the store)
 		HIP_TRY(hipMemsetAsync(ta.ctr, 0, sizeof(TrCounters), c->stream));
 	}
+	// with matrix adjustment: the arrays of that step in a buffer of their own (extend_cbs_core.h ext_cbs_layout); page-locked beside
+	// them the step's counters, the kernel's model and what comes back of an iteration's pairs
+	const ExtCbsLayout X = ext_cbs_layout(L.nG, nQ);
+	if (adjust) if (int rc = c->ext_cbs.ensure(X.bytes)) return rc;
+	Guard guard_cbs(c->ext_cbs, X.bytes, c->stream);
+	if (adjust) if (int rc = guard_cbs.arm()) return rc;
+	auto up64 = [](size_t x) { return (x + 63) & ~(size_t)63; };
+	const size_t hx_ctr = 0, hx_model = up64(sizeof(ExtCbsCounters)), hx_rule = up64(hx_model + sizeof(CbsDevModel)), hx_status = up64(hx_rule + L.nG * 4),
+		hx_qidx = up64(hx_status + L.nG), hx_toff = up64(hx_qidx + L.nG * 4), hx_tlen = up64(hx_toff + L.nG * 8), hx_qoff = up64(hx_tlen + L.nG * 4),
+		hx_qlen = up64(hx_qoff + L.nG * 8), hx_keep = up64(hx_qlen + L.nG * 4), hx_bytes = up64(hx_keep + L.nG);
+	if (adjust) if (int rc = c->cbs_host.ensure(hx_bytes)) return rc;
+	char* const hx = adjust ? c->cbs_host.as<char>() : nullptr;
 	const int64_t piece_limit = tr_piece_bytes();
 	size_t tr_pieces = 0, tr_raw = 0, tr_kept = 0, tr_gathered = 0;      // of the call: pieces walked, raw-slot bytes, bytes in the store, bytes in the arena
 	double ms_tr_walk = 0, ms_tr_keep = 0, ms_tr_gather = 0;
@@ -317,6 +337,22 @@ int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan,
 	a.records = reinterpret_cast<dmnd_match*>(d + L.o_records);
 	a.ctr = reinterpret_cast<ExtCounters*>(d + L.o_ctr);
 	a.scan_tmp = &c->plan_tmp; a.scan_tmp_bytes = &c->plan_tmp_bytes;
+	a.g_mat = nullptr; a.g_row = nullptr; a.q_comp = nullptr; a.q_true_aa = nullptr; a.c_flag = nullptr; a.c_pos = nullptr;
+	a.pair_group = nullptr; a.pair_qidx = nullptr; a.pair_toff = nullptr; a.pair_tlen = nullptr; a.pair_qoff = nullptr; a.pair_qlen = nullptr;
+	a.pair_rule = nullptr; a.pair_status = nullptr; a.pair_keep = nullptr; a.cbs_ctr = nullptr;
+	const CbsDevModel* cbs_model_dev = nullptr;
+	if (adjust) {
+		char* dx = c->ext_cbs.as<char>();
+		a.g_mat = reinterpret_cast<int32_t*>(dx + X.o_g_mat); a.g_row = reinterpret_cast<uint32_t*>(dx + X.o_g_row);
+		a.q_comp = reinterpret_cast<double*>(dx + X.o_comp); a.q_true_aa = reinterpret_cast<int32_t*>(dx + X.o_true_aa);
+		a.c_flag = reinterpret_cast<uint32_t*>(dx + X.o_flag); a.c_pos = reinterpret_cast<uint32_t*>(dx + X.o_pos);
+		a.pair_group = reinterpret_cast<uint32_t*>(dx + X.o_pair_group); a.pair_qidx = reinterpret_cast<int32_t*>(dx + X.o_qidx);
+		a.pair_toff = reinterpret_cast<int64_t*>(dx + X.o_toff); a.pair_tlen = reinterpret_cast<int32_t*>(dx + X.o_tlen);
+		a.pair_qoff = reinterpret_cast<int64_t*>(dx + X.o_qoff); a.pair_qlen = reinterpret_cast<int32_t*>(dx + X.o_qlen);
+		a.pair_rule = reinterpret_cast<int32_t*>(dx + X.o_rule); a.pair_status = reinterpret_cast<uint8_t*>(dx + X.o_status);
+		a.pair_keep = reinterpret_cast<uint8_t*>(dx + X.o_keep); a.cbs_ctr = reinterpret_cast<ExtCbsCounters*>(dx + X.o_ctr);
+		cbs_model_dev = reinterpret_cast<const CbsDevModel*>(dx + X.o_model);
+	}
 	hipStream_t st = c->stream;
 	// (page-locked, behind the counters: the transcript counters, one 64-bit value, the bounds of a walk's pieces)
 	const size_t h_trc = (sizeof(ExtCounters) + 63) & ~(size_t)63, h_val = h_trc + ((sizeof(TrCounters) + 63) & ~(size_t)63), h_pieces = h_val + 64;
@@ -341,6 +377,101 @@ int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan,
 	};
 	HIP_TRY(launch_ext_begin(a, st));
 	ExtCounters ctr;
+	// the matrix adjustment step of a ranking iteration (extend_kernels.h): state of the call
+	const int cbs_max_its = adjust ? dmnd_cbs_env_max_its() : 0;
+	std::vector<uint32_t> cbs_tally;                      // per planned query: pairs by status (a query that goes back to the host path takes its pairs along)
+	std::vector<int32_t> cbs_mat;
+	std::vector<int64_t> cbs_handed;
+	std::vector<uint8_t> cbs_kept;
+	std::vector<int8_t> cbs_patch;
+	std::vector<CbsPatchRun> cbs_runs;
+	double cbs_ms = 0;
+	if (adjust) {
+		c->n_adj_matrices = 0;                              // (the store starts empty, as extend_range's does)
+		cbs_dev_model(*reinterpret_cast<CbsDevModel*>(hx + hx_model), *h.cbs_model, h.cbs_mode, cbs_max_its);
+		HIP_TRY(hipMemcpyAsync(const_cast<CbsDevModel*>(cbs_model_dev), hx + hx_model, sizeof(CbsDevModel), hipMemcpyHostToDevice, st));
+		HIP_TRY(launch_ext_cbs_begin(a, c->block[DMND_QUERY].as<int8_t>(), st));
+		cbs_tally.assign(nQ * 4, 0);
+	}
+	// the iteration's counters on the host; the launch classes as dmnd_sweep_classes takes them: with matrix adjustment the classes of
+	// the own-matrix items behind the sixteen of the standard matrix
+	uint32_t cls_count[EXT_ALL_CLASSES] = { 0 }, cls_steps[EXT_ALL_CLASSES] = { 0 };
+	const int n_cls = adjust ? (int)EXT_ALL_CLASSES : (int)EXT_CLASSES;
+	auto read_counters = [&]() -> int {
+		HIP_TRY(hipMemcpyAsync(c->ext_host.p, a.ctr, sizeof(ExtCounters), hipMemcpyDeviceToHost, st));
+		if (adjust) HIP_TRY(hipMemcpyAsync(hx + hx_ctr, a.cbs_ctr, sizeof(ExtCbsCounters), hipMemcpyDeviceToHost, st));
+		HIP_TRY(sync_stream(st));
+		ctr = *c->ext_host.as<ExtCounters>();
+		std::memcpy(cls_count, ctr.class_count, sizeof ctr.class_count); std::memcpy(cls_steps, ctr.class_max_steps, sizeof ctr.class_max_steps);
+		if (adjust) {
+			const ExtCbsCounters& xc = *reinterpret_cast<const ExtCbsCounters*>(hx + hx_ctr);
+			std::memcpy(cls_count + EXT_OWN_CLASS, xc.class_count, sizeof xc.class_count); std::memcpy(cls_steps + EXT_OWN_CLASS, xc.class_max_steps, sizeof xc.class_max_steps);
+		}
+		return DMND_OK;
+	};
+	// One iteration's new pairs, listed in HBM by launch_ext_cbs_window: the kernel fills their slots of the store, rule, status and
+	// query row come back (9 bytes per pair), the host form computes the handed-back pairs from the caller's blocks and patches their
+	// slots (cbs_slots_assign / cbs_patch_runs, as extend_range does), then every pair's group gets its matrix number.
+	auto adjust_pairs = [&]() -> int {
+		HIP_TRY(copy_now(st, hx + hx_ctr, a.cbs_ctr, sizeof(ExtCbsCounters), hipMemcpyDeviceToHost));
+		const int64_t n_new = reinterpret_cast<const ExtCbsCounters*>(hx + hx_ctr)->n_pairs, before = c->n_adj_matrices;
+		if (n_new == 0) return DMND_OK;
+		if ((size_t)n_new > L.nG || before + n_new > (int64_t)L.nG) return fail(DMND_E_CAP, "dmnd_extend: more pairs to adjust than groups");
+		if (int rc = dmnd_reserve_matrices(c, before, n_new)) return rc;
+		if (int rc = dmnd_cbs_adjust_lists(c, cbs_model_dev, n_new, a.q_comp, a.q_true_aa, a.pair_qidx, a.pair_toff, a.pair_tlen, c->block[DMND_TARGET].as<int8_t>(),
+			c->adj_matrices.as<int8_t>() + (size_t)before * 32 * 32, nullptr, a.pair_rule, a.pair_status)) return rc;
+		const size_t n = (size_t)n_new;
+		HIP_TRY(hipMemcpyAsync(hx + hx_rule, a.pair_rule, n * 4, hipMemcpyDeviceToHost, st));
+		HIP_TRY(hipMemcpyAsync(hx + hx_status, a.pair_status, n, hipMemcpyDeviceToHost, st));
+		HIP_TRY(hipMemcpyAsync(hx + hx_qidx, a.pair_qidx, n * 4, hipMemcpyDeviceToHost, st));
+		HIP_TRY(sync_stream(st));
+		float ms = 0.f;
+		HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+		cbs_ms += ms;
+		const int32_t* rule = reinterpret_cast<const int32_t*>(hx + hx_rule);
+		const uint8_t* status = reinterpret_cast<const uint8_t*>(hx + hx_status);
+		const int32_t* qidx = reinterpret_cast<const int32_t*>(hx + hx_qidx);
+		cbs_mat.resize(n); cbs_handed.resize(n);
+		int64_t by_status[4];
+		const int64_t n_handed = cbs_slots_assign(before, n_new, rule, status, cbs_mat.data(), cbs_handed.data(), by_status);
+		for (size_t k = 0; k < n; ++k) {
+			if ((size_t)qidx[k] >= nQ) return fail(DMND_E_DEVICE, "dmnd_extend: a pair of the matrix adjustment without a query");
+			++cbs_tally[(size_t)qidx[k] * 4 + (status[k] < 4 ? status[k] : CBS_ST_ITERATIONS)];
+		}
+		if (n_handed > 0) {
+			HIP_TRY(hipMemcpyAsync(hx + hx_toff, a.pair_toff, n * 8, hipMemcpyDeviceToHost, st));
+			HIP_TRY(hipMemcpyAsync(hx + hx_tlen, a.pair_tlen, n * 4, hipMemcpyDeviceToHost, st));
+			HIP_TRY(hipMemcpyAsync(hx + hx_qoff, a.pair_qoff, n * 8, hipMemcpyDeviceToHost, st));
+			HIP_TRY(hipMemcpyAsync(hx + hx_qlen, a.pair_qlen, n * 4, hipMemcpyDeviceToHost, st));
+			HIP_TRY(sync_stream(st));
+			const int64_t* toff = reinterpret_cast<const int64_t*>(hx + hx_toff);
+			const int32_t* tlen = reinterpret_cast<const int32_t*>(hx + hx_tlen);
+			const int64_t* qoff = reinterpret_cast<const int64_t*>(hx + hx_qoff);
+			const int32_t* qlen = reinterpret_cast<const int32_t*>(hx + hx_qlen);
+			uint8_t* keep = reinterpret_cast<uint8_t*>(hx + hx_keep);      // per pair, for ext_pair_matrix
+			std::memset(keep, 1, n);
+			cbs_patch.resize((size_t)n_handed * 32 * 32); cbs_kept.assign((size_t)n_handed, 0); cbs_runs.resize((size_t)n_handed);
+			parallel_for((size_t)n_handed, std::max(1, std::min(threads, (int)((n_handed + 7) / 8))), [&](size_t x, int) {
+				const size_t k = (size_t)cbs_handed[x];
+				double comp[20];
+				int true_aa = 0;
+				cbs_composition(qdata + qoff[k], qlen[k], comp, &true_aa);
+				const int8_t* tseq = tdata + toff[k];
+				const int r = cbs_rule(*h.cbs_model, h.cbs_mode, comp, true_aa, tseq, tlen[k]);
+				if (r == CBS_RULE_NONE) { keep[k] = 0; return; }
+				cbs_kept[x] = 1;
+				cbs_target_matrix(*h.cbs_model, r, comp, true_aa, tseq, tlen[k], cbs_patch.data() + x * 32 * 32);
+			});
+			const int64_t n_runs = cbs_patch_runs(before, cbs_handed.data(), cbs_kept.data(), n_handed, cbs_runs.data());
+			for (int64_t r = 0; r < n_runs; ++r)
+				HIP_TRY(hipMemcpyAsync(c->adj_matrices.as<int8_t>() + (size_t)cbs_runs[(size_t)r].first_slot * 32 * 32, cbs_patch.data() + (size_t)cbs_runs[(size_t)r].first_patch * 32 * 32,
+					(size_t)cbs_runs[(size_t)r].n * 32 * 32, hipMemcpyHostToDevice, st));
+			HIP_TRY(hipMemcpyAsync(a.pair_keep, keep, n, hipMemcpyHostToDevice, st));
+			HIP_TRY(sync_stream(st));
+		}
+		HIP_TRY(launch_ext_cbs_matrices(a, before, (uint32_t)n_new, n_handed > 0, st));
+		return DMND_OK;
+	};
 	// the trace walk over the first n entries of the round-2 list
 	// (with a transcript arena: piece by piece, each piece's transcripts written into raw slots and kept in the store -- a chunk's
 	// trace rows may be gone after the next sweep, so this is the one place where transcripts are made, in every mode)
@@ -348,7 +479,7 @@ int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan,
 	auto walk = [&](uint32_t n) -> int {
 		TracebackArgs t;
 		t.qblock = c->block[DMND_QUERY].as<int8_t>(); t.tblock = c->block[DMND_TARGET].as<int8_t>(); t.cbs = c->cbs_len > 0 ? c->cbs.as<int8_t>() : nullptr;
-		t.matrix = c->matrix.as<int8_t>(); t.matrices = nullptr;
+		t.matrix = c->matrix.as<int8_t>(); t.matrices = adjust ? c->adj_matrices.as<int8_t>() : nullptr;      // (an item with a matrix code is walked on its own matrix)
 		t.items = a.items; t.order = a.r2_order; t.p_of_slot = a.r2_p; t.trace_off = a.r2_off; t.transcript_off = a.r2_tr;
 		t.trace = c->ext_trace.as<uint8_t>(); t.transcript = nullptr; t.ends = a.ends; t.hsps = a.hsps; t.status = &a.ctr->tb_status;
 		t.n = n; t.gap_open = c->params.gap_open; t.gap_extend = c->params.gap_extend;
@@ -409,15 +540,14 @@ int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan,
 	// the list's entries whose round-1 sweep kept no trace rows, swept again with traceback as one more iteration (copies of their items)
 	auto resweep = [&](uint32_t n_listed, double& ms) -> int {
 		HIP_TRY(launch_ext_resweep(a, n_listed, st));
-		HIP_TRY(copy_now(st, c->ext_host.p, a.ctr, sizeof(ExtCounters), hipMemcpyDeviceToHost));
-		ctr = *c->ext_host.as<ExtCounters>();
+		if (int rc = read_counters()) return rc;
 		// (these rows are not held against the budget of round 1, only against a hard limit)
 		if ((size_t)ctr.total_rows > std::max(c->trace_arena_max * 4, (size_t)4 << 30)) return fail(DMND_E_NOMEM, "dmnd_extend: the trace rows of round 2 exceed the trace limit (4 x DMND_TRACE_ARENA_MB, at least 4 GB)");
 		DevBuf* arena = nullptr;
 		int64_t rel = 0;
 		if (int rc = arena_for((size_t)ctr.total_rows, arena, rel)) return rc;
 		HIP_TRY(hipEventRecord(c->ev0, st));
-		if (int rc = dmnd_sweep_classes(c, c, a.items + a.item_base, ctr.class_count, ctr.class_max_steps, EXT_CLASSES, reinterpret_cast<const int32_t*>(a.order), a.off_slot, a.pairs,
+		if (int rc = dmnd_sweep_classes(c, c, a.items + a.item_base, cls_count, cls_steps, n_cls, reinterpret_cast<const int32_t*>(a.order), a.off_slot, a.pairs,
 			a.off_item + a.item_base, arena->as<uint8_t>(), a.ends + a.item_base)) return rc;
 		HIP_TRY(hipEventRecord(c->ev1, st));
 		HIP_TRY(launch_ext_rewalk(a, ctr.n_items, n_listed, rel, st));
@@ -437,9 +567,14 @@ int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan,
 		// the kept rows' and the one of a chunk swept again -- are used again, so a call never holds more than one chunk's rows
 		if (fchunk) { trace_used = 0; n_more = 0; }
 		// 1. the chunk's items, launch order, trace offsets, pairs
-		HIP_TRY(launch_ext_prepare(a, st));
-		HIP_TRY(copy_now(st, c->ext_host.p, a.ctr, sizeof(ExtCounters), hipMemcpyDeviceToHost));
-		ctr = *c->ext_host.as<ExtCounters>();
+		// (with matrix adjustment: the windows and the new pairs, their matrices, then the items with their matrix codes)
+		if (adjust) {
+			HIP_TRY(launch_ext_cbs_window(a, st));
+			if (int rc = adjust_pairs()) return rc;
+			HIP_TRY(launch_ext_cbs_items(a, st));
+		}
+		else HIP_TRY(launch_ext_prepare(a, st));
+		if (int rc = read_counters()) return rc;
 		if (iter == 0) tr.lap("items, launch order, trace offsets");
 		if (iter == 0 && ctr.n_items == 0) return guard.check("dmnd_extend (device half)");
 		// a call whose first ranking iteration took the row classes keeps them for its later, smaller iterations and for the copies
@@ -461,7 +596,7 @@ int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan,
 			if (kept) if (int rc = arena_for((size_t)ctr.total_rows, arena, rel)) return rc;
 			if (iter == 0) tr.lap("trace arena");
 			HIP_TRY(hipEventRecord(c->ev0, st));
-			if (int rc = dmnd_sweep_classes(c, c, a.items + a.item_base, ctr.class_count, ctr.class_max_steps, EXT_CLASSES, reinterpret_cast<const int32_t*>(a.order), a.off_slot, a.pairs,
+			if (int rc = dmnd_sweep_classes(c, c, a.items + a.item_base, cls_count, cls_steps, n_cls, reinterpret_cast<const int32_t*>(a.order), a.off_slot, a.pairs,
 				a.off_item + a.item_base, kept ? arena->as<uint8_t>() : nullptr, a.ends + a.item_base)) return rc;
 			HIP_TRY(hipEventRecord(c->ev1, st));
 		}
@@ -631,6 +766,18 @@ int dmnd::extend_on_device(dmnd_ctx* c, const DeviceCfg& h, const DevPlan& plan,
 		n_eligible, ctr.n_ambiguous + ctr.n_saturated + ctr.n_capped, ctr.n_ambiguous, ctr.n_saturated, ctr.n_capped, max_chunks, n, plan.n_groups, plan.n_bands, L.bytes);
 	if (tr.on && with_tr) std::fprintf(stderr, "dmnd_extend (device half) transcripts: %zu pieces of at most %lld raw bytes, %zu raw bytes, %zu kept bytes, %zu gathered bytes; walk %.3f ms, keep %.3f ms, gather %.3f ms\n",
 		tr_pieces, (long long)piece_limit, tr_raw, tr_kept, tr_gathered, ms_tr_walk, ms_tr_keep, ms_tr_gather);
+	if (adjust) {
+		// dmnd_cbs_device_stats: the pairs of the queries done here. A query that goes back takes its pairs out of these tallies -- the
+		// host path lists and counts them again --, so a pair is counted once whichever half ends up with its query.
+		double by_status[4] = { 0, 0, 0, 0 };
+		for (size_t q = 0; q < nQ; ++q)
+			if (qstate[q] == EXT_Q_DEVICE) for (int s = 0; s < 4; ++s) by_status[s] += (double)cbs_tally[q * 4 + (size_t)s];
+		for (int s = 0; s < 4; ++s) { c->cbs_dev_stats[0] += by_status[s]; c->cbs_dev_stats[1 + s] += by_status[s]; }
+		c->cbs_dev_stats[5] += cbs_ms;
+		if (tr.on) std::fprintf(stderr, "dmnd_extend (device half) matrix adjustment: %lld slots of the store, %.0f pairs of the queries done here (%.0f handed back to the host form), kernel %.3f ms\n",
+			(long long)c->n_adj_matrices, by_status[0] + by_status[1] + by_status[2] + by_status[3], by_status[1] + by_status[2] + by_status[3], cbs_ms);
+		if (int rc = guard_cbs.check("dmnd_extend (device half, matrix adjustment arrays)")) return rc;
+	}
 	if (int rc = guard.check("dmnd_extend (device half)")) return rc;
 	if (with_tr) if (int rc = guard_tr.check("dmnd_extend (device half, transcript arrays)")) return rc;
 	if (read_lens) if (int rc = guard_sl.check("dmnd_extend (device half, read lengths)")) return rc;

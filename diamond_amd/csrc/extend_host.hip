@@ -175,6 +175,7 @@ DeviceCfg device_cfg(const HostCfg& h)      // what the device half reads of the
 	d.filters.min_id = h.min_id; d.filters.approx_id = h.approx_id; d.filters.query_cover = h.query_cover; d.filters.subject_cover = h.subject_cover;
 	d.contexts = h.contexts;
 	d.ext_full = h.ext_full; d.global_ranking = h.global_ranking;
+	d.cbs_mode = h.cbs_mode; d.cbs_model = h.cbs_model;
 	// the final pass of the global ranking: one chunk holds all ranked targets of a query (extend.cpp:80; rank_groups below) -- the
 	// table is cut at global_ranking entries per query, so a chunk of that size holds every query's groups
 	if (h.global_ranking > 0) d.ranking_chunk = h.global_ranking;
@@ -1537,13 +1538,17 @@ extern "C" int dmnd_extend(dmnd_ctx* c, const int8_t* qdata, const int8_t* tdata
 	// DMND_EXTEND_DEVICE=0: all queries on the host path, as up to round 5. Read per call, like the hooks of extend_device.hip
 	// (DESIGN.md 9): a test compares the two paths in one process.
 	const bool ext_gpu = [] { const char* e = std::getenv("DMND_EXTEND_DEVICE"); return !e || e[0] != '0'; }();
-	// what the device half extends: one HSP per target, Hauser bias or none, banded or full-matrix extension (--ext full; the final pass
+	// what the device half extends: one HSP per target, Hauser bias or none or -- banded protein searches -- the adjusted matrices of
+	// --comp-based-stats 2 - 5 (extend_cbs_core.h), banded or full-matrix extension (--ext full; the final pass
 	// of --global-ranking, whose one ranking chunk per query extend_on_device accepts up to EXT_MAX_CHUNK), -k or --top, one query context
 	// or six (blastx). With six contexts and the HSP filters the query cover is measured on the DNA read: such a call is taken when the context
 	// holds the block's read lengths (dmnd_set_query_source_lengths; the device half copies them to HBM), and stays on the host path as a
 	// whole without them -- there every cover is measured against 1 (--query-cover itself is refused by extend_cfg)
 	const bool have_read_lens = c->source_lens.size() == (ql.size() - 1) / (size_t)h.contexts;
-	const bool device_takes = ext_gpu && h.max_hsps == 1 && !cbs_matrix_adjust(h.cbs_mode)
+	// --comp-based-stats 2 - 5: the device half adjusts the matrices itself (cbs_kernels.hip from its own pair lists) for a banded protein
+	// search; --ext full keeps the host path and its refusal, DMND_CBS_DEVICE=0 the host path with the host arithmetic
+	const bool adjust_on_device = !h.ext_full && h.contexts == 1 && h.global_ranking == 0 && [] { const char* e = std::getenv("DMND_CBS_DEVICE"); return !e || e[0] != '0'; }();
+	const bool device_takes = ext_gpu && h.max_hsps == 1 && (!cbs_matrix_adjust(h.cbs_mode) || adjust_on_device)
 		&& !c->same_title && h.max_target_seqs > 0 && (h.contexts == 1 || !h.have_filters() || have_read_lens);
 	ExtendFront f;
 	if (int rc = extend_front(c, h, hits, n_hits, qr.size(), lap, trp, f, device_takes, device_takes)) return rc;
@@ -1566,8 +1571,10 @@ extern "C" int dmnd_extend(dmnd_ctx* c, const int8_t* qdata, const int8_t* tdata
 	// The queries are extended in HBM from here on (extend_kernels.hip), ranking chunk by ranking chunk: the default search of a
 	// protein or translated query block -- one HSP per target, -k culling by e-value or --top culling by score, Hauser bias or none,
 	// with or without the HSP filters (translated: with the block's read lengths), with or without a transcript arena (its transcripts
-	// come first in the arena), banded or -- --ext full, the final pass of --global-ranking -- over the whole matrix. The queries the
-	// device half hands back, and every query of any other mode (-F, --max-hsps != 1, matrix adjustment), take the host path below.
+	// come first in the arena), banded or -- --ext full, the final pass of --global-ranking -- over the whole matrix; a banded protein
+	// search also with the matrix adjustment of --comp-based-stats 2 - 5 (inside every ranking iteration; unless DMND_CBS_DEVICE=0, or the
+	// planner found more groups than one pass's DMND_CBS_PASS_HITS matrix slots). The queries the device half hands back, and every query
+	// of any other mode (-F, --max-hsps != 1, --ext full with matrix adjustment), take the host path below.
 	c->ext_records_dev = nullptr; c->ext_records_n = -1;
 	std::vector<dmnd_match> dev_records;
 	std::vector<Range> qr_host;
@@ -1580,7 +1587,7 @@ extern "C" int dmnd_extend(dmnd_ctx* c, const int8_t* qdata, const int8_t* tdata
 		std::vector<uint8_t> qstate;
 		double kept[12];
 		for (int i = 0; i < 12; ++i) kept[i] = c->ext_stats[i];
-		if (int rc = extend_on_device(c, device_cfg(h), plan, threads, dev_records, qstate, on_device, transcript, transcript_cap, &used_dev)) return rc;
+		if (int rc = extend_on_device(c, device_cfg(h), plan, threads, dev_records, qstate, on_device, transcript, transcript_cap, &used_dev, qdata, tdata)) return rc;
 		bias_pending = false;                               // (it has waited for the stream)
 		if (on_device) {
 			for (size_t k = 0; k < qr.size(); ++k)
@@ -1645,8 +1652,8 @@ extern "C" int dmnd_extend(dmnd_ctx* c, const int8_t* qdata, const int8_t* tdata
 		// of at most DMND_CBS_PASS_HITS seed hits (default 2 M: a pair needs a seed hit, so <= 2 GB of matrices, in practice a tenth);
 		// a pass frees its matrices (extend_range starts from none). The result does not depend on the cut: queries are independent.
 		// (read per call, like DMND_CBS_DEVICE: a test runs one block pair with several cuts in one process)
-		const int64_t pass_hits = [] { const char* e = std::getenv("DMND_CBS_PASS_HITS"); return e ? std::max<int64_t>(1, std::atoll(e)) : (int64_t)2 << 20; }();
-		int64_t t_used = 0;
+		const int64_t pass_hits = dmnd_cbs_pass_hits();
+		int64_t t_used = used_dev;                          // (behind the device half's transcripts, if it ran)
 		double stats[12] = { 0 };
 		for (size_t b = 0; b < qr_run.size() && rcs[0] == DMND_OK;) {
 			size_t e = b + 1;

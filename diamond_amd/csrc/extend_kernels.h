@@ -23,6 +23,7 @@
 #include <stdint.h>
 #include "../../include/diamond_hip.h"
 #include "extend_core.h"
+#include "extend_cbs_core.h"
 #include "filter_core.h"
 #include "top_core.h"
 #include "transcript_core.h"
@@ -98,6 +99,14 @@ struct ExtArgs {
 	dmnd_match* records;
 	ExtCounters* ctr;
 	void** scan_tmp; size_t* scan_tmp_bytes;
+	// --comp-based-stats 2 - 5 (extend_cbs_core.h; layout: ext_cbs_layout): g_mat == NULL -- every other call -- and none of these is read
+	int32_t* g_mat;                // per group: EXT_MAT_UNSET until the group is listed as a pair, then EXT_MAT_STANDARD or its slot of the matrix store
+	uint32_t* g_row;               // per group: its planned query
+	double* q_comp; int32_t* q_true_aa;      // per planned query: composition (20 doubles), true amino acids
+	uint32_t* c_flag; uint32_t* c_pos;       // (+ 1) per group: a new pair of this iteration, exclusive scan
+	uint32_t* pair_group; int32_t* pair_qidx; int64_t* pair_toff; int32_t* pair_tlen; int64_t* pair_qoff; int32_t* pair_qlen;      // per pair of this iteration
+	int32_t* pair_rule; uint8_t* pair_status; uint8_t* pair_keep;
+	ExtCbsCounters* cbs_ctr;
 	int tr_on;                     // the call returns transcripts: a record leaves the records kernels with its GROUP in hsp.transcript_off
 	                               // (launch_tr_gather turns it into the offset); 0: -1, as ever
 };
@@ -136,6 +145,19 @@ hipError_t launch_ext_begin(const ExtArgs& a, hipStream_t st);
 // one iteration, before its sweeps: the DpTargets of every active query's current chunk, launch order, trace offsets, pairs
 // (a.item_base = items of the earlier iterations); the counts stay in ctr
 hipError_t launch_ext_prepare(const ExtArgs& a, hipStream_t st);
+// The same in three steps for a call with matrix adjustment (a.g_mat != NULL; --comp-based-stats 2 - 5). launch_ext_cbs_begin,
+// once per call behind launch_ext_begin: the composition of every planned query (one wavefront each, the counting and the single
+// division of cbsd_pair's target side), every group's query row, g_mat = EXT_MAT_UNSET. launch_ext_cbs_window: the windows (cnt per
+// group) and the iteration's new pairs -- every group with cnt > 0 and no matrix number yet, in group order: pair k -> group, query
+// row, target offset and length (the lists cbs_adjust_kernel takes), cbs_ctr->n_pairs. The host has the kernel fill the slots
+// before + k of the matrix store (dmnd_cbs_adjust_lists), computes the pairs it hands back and patches their slots.
+// launch_ext_cbs_matrices: g_mat of the pairs' groups from rule, status and -- keep != 0 -- pair_keep (ext_pair_matrix).
+// launch_ext_cbs_items: the rest of launch_ext_prepare; an item of a group with a matrix carries its code (ext_matrix_code) and
+// is counted in a launch class of its own (cbs_ctr->class_count: 32-bit kernels only, never a row class).
+hipError_t launch_ext_cbs_begin(const ExtArgs& a, const int8_t* qblock, hipStream_t st);
+hipError_t launch_ext_cbs_window(const ExtArgs& a, hipStream_t st);
+hipError_t launch_ext_cbs_matrices(const ExtArgs& a, int64_t before, uint32_t n_pairs, bool keep, hipStream_t st);
+hipError_t launch_ext_cbs_items(const ExtArgs& a, hipStream_t st);
 // ... behind its sweeps: best HSP per target, append_hits, the next chunk or the end of the query's ranking. kept: the sweeps ran in
 // traceback mode and their trace rows stay (rel = the iteration's arena relative to the first one); else round 2 sweeps the
 // survivors of this iteration again. Then -- speculatively: it only counts if ctr->n_active comes back 0 -- the final culling and

@@ -177,9 +177,62 @@ __global__ __launch_bounds__(256) void ext_init_kernel(ExtArgs a)
 }
 
 // launch class of an item (api.hip sweep_class: the row classes take what the packed 16-bit kernels take)
-__device__ inline int ext_class(bool rows, int band, int64_t steps)
+// (own: the item is scored with a matrix of its own -- 32-bit kernels only, extend_cbs_core.h)
+__device__ inline int ext_class(bool rows, bool own, int band, int64_t steps)
 {
-	return rows && steps <= 2 * (int64_t)SW16_MAX_PAIRS ? band_class_rows(band) : band_class(band);
+	return ext_item_class(rows, own, band, steps, (int64_t)SW16_MAX_PAIRS);
+}
+
+// ---- matrix adjustment inside the device half (--comp-based-stats 2 - 5; extend_kernels.h, extend_cbs_core.h) ----
+// One wavefront per planned query: its composition as cbs_composition (cbs_adjust.cpp) and the target side of cbsd_pair (cbs_core.h)
+// compute it -- exact integer counts, one correctly rounded division each, so the doubles are the host's --, and its groups' rows.
+__global__ __launch_bounds__(64) void ext_cbs_comp_kernel(ExtArgs a, const int8_t* qblock)
+{
+	__shared__ int cnt[CBSD_N];
+	const uint32_t q = blockIdx.x, lane = threadIdx.x;
+	const uint32_t query = a.queries[q].query;
+	const int64_t q0 = a.qlimits[query];
+	const int64_t len = a.qlimits[query + 1] - q0 - 1;
+	if (lane < CBSD_N) cnt[lane] = 0;
+	__syncthreads();
+	for (int64_t p = lane; p < len; p += 64) { const int l = qblock[q0 + p] & 31; if (l < CBSD_N) atomicAdd(&cnt[l], 1); }
+	__syncthreads();
+	int n = 0;
+	for (int i = 0; i < CBSD_N; ++i) n += cnt[i];
+	if (lane < CBSD_N) a.q_comp[(size_t)q * CBSD_N + lane] = n == 0 ? 0.0 : (double)cnt[lane] / n;
+	if (lane == 0) a.q_true_aa[q] = n;
+	const uint32_t g0 = a.queries[q].group_begin, g1 = a.queries[q + 1].group_begin;
+	for (uint32_t g = g0 + lane; g < g1; g += 64) { a.g_row[g] = q; a.g_mat[g] = EXT_MAT_UNSET; }
+}
+
+// the iteration's new pairs: groups of the windows that have items and no matrix number yet
+__global__ __launch_bounds__(256) void ext_cbs_flag_kernel(ExtArgs a)
+{
+	const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+	if (g < a.n_groups) a.c_flag[g] = a.cnt[g] > 0 && a.g_mat[g] == EXT_MAT_UNSET ? 1u : 0u;
+	else if (g == a.n_groups) a.c_flag[g] = 0;
+}
+
+__global__ __launch_bounds__(256) void ext_cbs_pairs_kernel(ExtArgs a)
+{
+	const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+	if (g == 0) {
+		a.cbs_ctr->n_pairs = a.c_pos[a.n_groups];
+		for (int c = 0; c < EXT_OWN_CLASS; ++c) { a.cbs_ctr->class_count[c] = 0; a.cbs_ctr->class_max_steps[c] = 0; }
+	}
+	if (g >= a.n_groups || !a.c_flag[g]) return;
+	const uint32_t k = a.c_pos[g], row = a.g_row[g];
+	const uint32_t target = a.groups[g].target, query = a.queries[row].query;
+	const int64_t t0 = a.tlimits[target], q0 = a.qlimits[query];
+	a.pair_group[k] = g; a.pair_qidx[k] = (int32_t)row;
+	a.pair_toff[k] = t0; a.pair_tlen[k] = (int32_t)(a.tlimits[target + 1] - t0 - 1);
+	a.pair_qoff[k] = q0; a.pair_qlen[k] = (int32_t)(a.qlimits[query + 1] - q0 - 1);
+}
+
+__global__ __launch_bounds__(256) void ext_cbs_matrices_kernel(ExtArgs a, int64_t before, uint32_t n_pairs, int keep)
+{
+	const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+	if (k < n_pairs) a.g_mat[a.pair_group[k]] = ext_pair_matrix(before, (int64_t)k, a.pair_rule[k], a.pair_status[k], keep ? a.pair_keep[k] : (uint8_t)1);
 }
 
 __global__ __launch_bounds__(256) void ext_items_kernel(ExtArgs a)
@@ -187,7 +240,9 @@ __global__ __launch_bounds__(256) void ext_items_kernel(ExtArgs a)
 	__shared__ uint32_t h_count[EXT_CLASSES], h_steps[EXT_CLASSES];
 	__shared__ unsigned long long h_cells, h_diag, h_lane;
 	__shared__ uint32_t h_targets, h_bound;
+	__shared__ uint32_t h_own_count[EXT_OWN_CLASS], h_own_steps[EXT_OWN_CLASS];      // items with a matrix of their own (a.g_mat)
 	if (threadIdx.x < EXT_CLASSES) { h_count[threadIdx.x] = 0; h_steps[threadIdx.x] = 0; }
+	if (threadIdx.x < EXT_OWN_CLASS) { h_own_count[threadIdx.x] = 0; h_own_steps[threadIdx.x] = 0; }
 	if (threadIdx.x == 0) { h_cells = 0; h_diag = 0; h_lane = 0; h_targets = 0; h_bound = 0; }
 	__syncthreads();
 	const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
@@ -208,24 +263,28 @@ __global__ __launch_bounds__(256) void ext_items_kernel(ExtArgs a)
 			const uint32_t local = a.item_off[g], first = a.item_base + local;
 			a.g_first[g] = first; a.g_cnt[g] = n;
 			unsigned long long cells = 0, diag = 0, lanes = 0;
+			// the group's adjusted matrix, if it has one: its items are swept with it and without the bias (extend_host.hip item_of)
+			const int32_t mat = a.g_mat ? a.g_mat[g] : (int32_t)EXT_MAT_STANDARD;
+			const bool own = mat >= 0;
 			for (uint32_t k = 0; k < n; ++k) {
 				const PlanBand b = a.bands[grp.band_begin + k];
 				if (a.band_query) {      // the item reads the sequence, bias and length of its band's context
 					const uint32_t bq = a.band_query[grp.band_begin + k];
 					q0 = a.qlimits[bq]; qlen = (int)(a.qlimits[bq + 1] - q0 - 1);
 				}
-				const dmnd_dp_target d{ q0, t0, a.use_cbs ? q0 : (int64_t)-1, qlen, tlen, b.d_begin, b.d_end };
+				const dmnd_dp_target d{ q0, t0, ext_matrix_code(mat, a.use_cbs != 0, q0), qlen, tlen, b.d_begin, b.d_end };
 				a.items[first + k] = d;
 				const Geom geom = make_geom(qlen, tlen, b.d_begin, b.d_end);
 				const int64_t steps = n_steps(geom);
-				const int P = ext_class(rows, b.d_end - b.d_begin, steps);
-				const int c = class_index(P);
+				const int P = ext_class(rows, own, b.d_end - b.d_begin, steps);
+				const int c = ext_class_slot(P, own);
 				a.p_of_item[first + k] = P;
 				a.rows[local + k] = trace_bytes(geom, P);
 				const int64_t s16 = steps >> 4;
 				a.keys[local + k] = ((uint32_t)c << 10) | (uint32_t)(1023 - (s16 < 1023 ? s16 : 1023));
-				atomicAdd(&h_count[c], 1u);
-				atomicMax(&h_steps[c], (uint32_t)(steps < 0x7fffffff ? steps : 0x7fffffff));
+				const uint32_t steps32 = (uint32_t)(steps < 0x7fffffff ? steps : 0x7fffffff);
+				if (own) { atomicAdd(&h_own_count[c - EXT_OWN_CLASS], 1u); atomicMax(&h_own_steps[c - EXT_OWN_CLASS], steps32); }
+				else { atomicAdd(&h_count[c], 1u); atomicMax(&h_steps[c], steps32); }
 				cells += (unsigned long long)ext_cells(d);
 				diag += (unsigned long long)(b.d_end - b.d_begin) * (unsigned long long)steps;
 				lanes += (unsigned long long)(2 * P * class_lanes(P)) * (unsigned long long)steps;
@@ -238,6 +297,10 @@ __global__ __launch_bounds__(256) void ext_items_kernel(ExtArgs a)
 	if (threadIdx.x < EXT_CLASSES && h_count[threadIdx.x]) {
 		atomicAdd(&a.ctr->class_count[threadIdx.x], h_count[threadIdx.x]);
 		atomicMax(&a.ctr->class_max_steps[threadIdx.x], h_steps[threadIdx.x]);
+	}
+	if (a.g_mat && threadIdx.x < EXT_OWN_CLASS && h_own_count[threadIdx.x]) {
+		atomicAdd(&a.cbs_ctr->class_count[threadIdx.x], h_own_count[threadIdx.x]);
+		atomicMax(&a.cbs_ctr->class_max_steps[threadIdx.x], h_own_steps[threadIdx.x]);
 	}
 	if (threadIdx.x == 0 && h_cells) { atomicAdd(&a.ctr->cells1, h_cells); atomicAdd(&a.ctr->diag_steps, h_diag); atomicAdd(&a.ctr->lane_steps, h_lane); }
 	if (threadIdx.x == 0 && h_targets) { atomicAdd(&a.ctr->window_targets, (unsigned long long)h_targets); atomicAdd(&a.ctr->window_bound, (unsigned long long)h_bound); }
@@ -261,6 +324,7 @@ __global__ __launch_bounds__(256) void ext_offsets_kernel(ExtArgs a)
 	// the packed 16-bit launches take their items in pairs (eights for a row class) of neighbours of the launch order; every class
 	// starts a new wavefront, and the last wavefront of a class is filled up with -1 (dmnd_sweep_classes reads the same layout)
 	const uint32_t c = a.keys_sorted[s] >> 10;
+	if (c >= EXT_CLASSES) return;                        // (an own-matrix class: behind all others in the launch order, never in a packed launch)
 	uint32_t s0 = 0, pair0 = 0;
 	for (uint32_t x = 0; x < c; ++x) {
 		const uint32_t per = (uint32_t)class_items_per_wave16(class_of_index((int)x));
@@ -485,24 +549,28 @@ __global__ __launch_bounds__(256) void ext_resweep_kernel(ExtArgs a, uint32_t n_
 {
 	__shared__ uint32_t h_count[EXT_CLASSES], h_steps[EXT_CLASSES];
 	__shared__ unsigned long long h_cells;
+	__shared__ uint32_t h_own_count[EXT_OWN_CLASS], h_own_steps[EXT_OWN_CLASS];
 	if (threadIdx.x < EXT_CLASSES) { h_count[threadIdx.x] = 0; h_steps[threadIdx.x] = 0; }
+	if (threadIdx.x < EXT_OWN_CLASS) { h_own_count[threadIdx.x] = 0; h_own_steps[threadIdx.x] = 0; }
 	if (threadIdx.x == 0) h_cells = 0;
 	__syncthreads();
 	const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
 	if (k < n_kept && a.r2_off[k] < 0) {
 		const uint32_t local = atomicAdd(&a.ctr->n_items, 1u), copy = a.item_base + local;
 		const dmnd_dp_target d = a.items[a.r2_order[k]];
-		a.items[copy] = d;
+		a.items[copy] = d;                        // (with its matrix code)
+		const bool own = a.g_mat && d.cbs_off <= -2;
 		const Geom geom = make_geom(d.query_len, d.target_len, d.d_begin, d.d_end);
 		const int64_t steps = n_steps(geom);
-		const int P = ext_class(a.ctr->n_resweep >= a.row_min_items, d.d_end - d.d_begin, steps);
-		const int c = class_index(P);
+		const int P = ext_class(a.ctr->n_resweep >= a.row_min_items, own, d.d_end - d.d_begin, steps);
+		const int c = ext_class_slot(P, own);
 		a.p_of_item[copy] = P;
 		a.rows[local] = trace_bytes(geom, P);
 		const int64_t s16 = steps >> 4;
 		a.keys[local] = ((uint32_t)c << 10) | (uint32_t)(1023 - (s16 < 1023 ? s16 : 1023));
-		atomicAdd(&h_count[c], 1u);
-		atomicMax(&h_steps[c], (uint32_t)(steps < 0x7fffffff ? steps : 0x7fffffff));
+		const uint32_t steps32 = (uint32_t)(steps < 0x7fffffff ? steps : 0x7fffffff);
+		if (own) { atomicAdd(&h_own_count[c - EXT_OWN_CLASS], 1u); atomicMax(&h_own_steps[c - EXT_OWN_CLASS], steps32); }
+		else { atomicAdd(&h_count[c], 1u); atomicMax(&h_steps[c], steps32); }
 		a.r2_order[k] = (int32_t)copy;
 		a.r2_p[k] = P;                            // (the copy's class: the first sweep may have been in another one, ext_class)
 		a.cand_item[a.r2_group[k]] = copy;
@@ -512,6 +580,10 @@ __global__ __launch_bounds__(256) void ext_resweep_kernel(ExtArgs a, uint32_t n_
 	if (threadIdx.x < EXT_CLASSES && h_count[threadIdx.x]) {
 		atomicAdd(&a.ctr->class_count[threadIdx.x], h_count[threadIdx.x]);
 		atomicMax(&a.ctr->class_max_steps[threadIdx.x], h_steps[threadIdx.x]);
+	}
+	if (a.g_mat && threadIdx.x < EXT_OWN_CLASS && h_own_count[threadIdx.x]) {
+		atomicAdd(&a.cbs_ctr->class_count[threadIdx.x], h_own_count[threadIdx.x]);
+		atomicMax(&a.cbs_ctr->class_max_steps[threadIdx.x], h_own_steps[threadIdx.x]);
 	}
 	if (threadIdx.x == 0 && h_cells) atomicAdd(&a.ctr->cells_again, h_cells);
 }
@@ -1055,6 +1127,10 @@ hipError_t reset_iteration(const ExtArgs& a, hipStream_t st)
 {
 	hipError_t e = hipMemsetAsync(&a.ctr->n_items, 0, 2 * sizeof(uint32_t), st);
 	if (e != hipSuccess) return e;
+	if (a.g_mat) {
+		e = hipMemsetAsync(a.cbs_ctr->class_count, 0, 2 * EXT_OWN_CLASS * sizeof(uint32_t), st);
+		if (e != hipSuccess) return e;
+	}
 	return hipMemsetAsync(a.ctr->class_count, 0, 2 * EXT_CLASSES * sizeof(uint32_t) + sizeof(unsigned long long), st);
 }
 
@@ -1093,6 +1169,49 @@ hipError_t launch_ext_prepare(const ExtArgs& a, hipStream_t st)
 	if (e != hipSuccess) return e;
 	hipLaunchKernelGGL(ext_window_kernel, dim3(a.n_queries), dim3(64), 0, st, a);
 	if (n_left > 0) hipLaunchKernelGGL(ext_init_kernel, dim3((n_left + 255) / 256), dim3(256), 0, st, a);
+	e = rocprim::exclusive_scan(*a.scan_tmp, need_a, a.cnt, a.item_off, 0u, (size_t)a.n_groups + 1, rocprim::plus<uint32_t>(), st);
+	if (e != hipSuccess) return e;
+	hipLaunchKernelGGL(ext_items_kernel, dim3((a.n_groups + 255) / 256), dim3(256), 0, st, a);
+	return order_items(a, st);
+}
+
+hipError_t launch_ext_cbs_begin(const ExtArgs& a, const int8_t* qblock, hipStream_t st)
+{
+	hipLaunchKernelGGL(ext_cbs_comp_kernel, dim3(a.n_queries), dim3(64), 0, st, a, qblock);
+	return hipGetLastError();
+}
+
+hipError_t launch_ext_cbs_window(const ExtArgs& a, hipStream_t st)
+{
+	const uint32_t n_left = a.item_cap - a.item_base;
+	size_t need = 0;
+	hipError_t e = rocprim::exclusive_scan(nullptr, need, a.c_flag, a.c_pos, 0u, (size_t)a.n_groups + 1, rocprim::plus<uint32_t>(), st);
+	if (e != hipSuccess) return e;
+	e = ensure_tmp(a.scan_tmp, a.scan_tmp_bytes, need);
+	if (e != hipSuccess) return e;
+	hipLaunchKernelGGL(ext_window_kernel, dim3(a.n_queries), dim3(64), 0, st, a);
+	if (n_left > 0) hipLaunchKernelGGL(ext_init_kernel, dim3((n_left + 255) / 256), dim3(256), 0, st, a);
+	hipLaunchKernelGGL(ext_cbs_flag_kernel, dim3((a.n_groups + 1 + 255) / 256), dim3(256), 0, st, a);
+	e = rocprim::exclusive_scan(*a.scan_tmp, need, a.c_flag, a.c_pos, 0u, (size_t)a.n_groups + 1, rocprim::plus<uint32_t>(), st);
+	if (e != hipSuccess) return e;
+	hipLaunchKernelGGL(ext_cbs_pairs_kernel, dim3((a.n_groups + 255) / 256), dim3(256), 0, st, a);
+	return hipGetLastError();
+}
+
+hipError_t launch_ext_cbs_matrices(const ExtArgs& a, int64_t before, uint32_t n_pairs, bool keep, hipStream_t st)
+{
+	if (n_pairs == 0) return hipSuccess;
+	hipLaunchKernelGGL(ext_cbs_matrices_kernel, dim3((n_pairs + 255) / 256), dim3(256), 0, st, a, before, n_pairs, keep ? 1 : 0);
+	return hipGetLastError();
+}
+
+hipError_t launch_ext_cbs_items(const ExtArgs& a, hipStream_t st)
+{
+	size_t need_a = 0;
+	hipError_t e = rocprim::exclusive_scan(nullptr, need_a, a.cnt, a.item_off, 0u, (size_t)a.n_groups + 1, rocprim::plus<uint32_t>(), st);
+	if (e != hipSuccess) return e;
+	e = ensure_tmp(a.scan_tmp, a.scan_tmp_bytes, need_a);
+	if (e != hipSuccess) return e;
 	e = rocprim::exclusive_scan(*a.scan_tmp, need_a, a.cnt, a.item_off, 0u, (size_t)a.n_groups + 1, rocprim::plus<uint32_t>(), st);
 	if (e != hipSuccess) return e;
 	hipLaunchKernelGGL(ext_items_kernel, dim3((a.n_groups + 255) / 256), dim3(256), 0, st, a);

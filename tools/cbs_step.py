@@ -8,6 +8,10 @@ kernel's time, the pairs per step and the shares handed back. The records of the
                                                             host form only, so both columns then time the same code)
   python tools/cbs_step.py --host-only                     both columns run the host form: what the host form takes when no
                                                             device-form step runs between its steps
+  python tools/cbs_step.py --extend-device                 the matrix adjustment is the device form in both columns; the "host" column runs
+                                                            the host path's ranking loop around it (DMND_EXTEND_DEVICE=0), the "device" column
+                                                            the default: the device half of the extension stage with the adjustment inside.
+                                                            With --lib of a build without that route both columns time its default form
 The seed stage runs once, outside the timed region: every step extends the same seed hits."""
 import argparse
 import json
@@ -31,6 +35,7 @@ def main():
     ap.add_argument("--threads", type=int, default=12)
     ap.add_argument("--lib", default=None)
     ap.add_argument("--host-only", action="store_true")
+    ap.add_argument("--extend-device", action="store_true")
     args = ap.parse_args()
     if args.lib:
         hip.LIB_PATH = os.path.abspath(args.lib)
@@ -50,13 +55,14 @@ def main():
         for mode in args.modes:
             ctx.set_comp_based_stats(mode)
             forms = {"host": dict(wall=[], cpu=[]), "device": dict(wall=[], cpu=[])}
-            stats = None
+            stats = ext = None
+            switch = "DMND_EXTEND_DEVICE" if args.extend_device else "DMND_CBS_DEVICE"
             for s in range(args.warmup + args.steps):
                 for form in ("host", "device"):
                     if form == "host" or args.host_only:
-                        os.environ["DMND_CBS_DEVICE"] = "0"
+                        os.environ[switch] = "0"
                     else:
-                        os.environ.pop("DMND_CBS_DEVICE", None)
+                        os.environ.pop(switch, None)
                     c0, t0 = time.process_time(), time.perf_counter()
                     m, _ = ctx.extend(qd, td, hits, threads=args.threads)
                     t1, c1 = time.perf_counter(), time.process_time()
@@ -67,8 +73,9 @@ def main():
                     f["m"] = m
                     if form == "device" and have_stats:
                         stats = ctx.cbs_device_stats()
-            os.environ.pop("DMND_CBS_DEVICE", None)
-            out = dict(mode=mode, lib=args.lib or "this build", host_only=args.host_only, seed_hits=int(len(hits)), steps=args.steps, threads=args.threads,
+                        ext = ctx.extend_device_stats()
+            os.environ.pop(switch, None)
+            out = dict(mode=mode, lib=args.lib or "this build", host_only=args.host_only, extend_device=args.extend_device, seed_hits=int(len(hits)), steps=args.steps, threads=args.threads,
                        same_records=bool(np.array_equal(forms["host"]["m"], forms["device"]["m"])), records=len(forms["host"]["m"]))
             for form, f in forms.items():
                 out[form] = dict(wall_ms_median=float(np.median(f["wall"])), wall_ms_min=float(min(f["wall"])), wall_ms_max=float(max(f["wall"])),
@@ -77,6 +84,8 @@ def main():
                 n = stats["pairs"]
                 out["device"].update(kernel_ms=stats["kernel_ms"], pairs=n, decided_on_device=stats["device"] / n, back_by_rounding=stats["rounding"] / n,
                                      back_by_iterations=stats["iterations"] / n, back_by_rule=stats["rule"] / n)
+            if ext and args.extend_device:
+                out["device"].update(queries_on_device=ext["queries"], queries_back_to_host=ext["queries_back_to_host"])
             print(json.dumps(out), flush=True)
     finally:
         ctx.close()

@@ -34,6 +34,7 @@
 #include <sys/stat.h>
 #include "../../include/diamond_hip.h"
 #include "filter_core.h"
+#include "length_ratio_core.h"
 
 namespace {
 
@@ -52,6 +53,7 @@ struct SeqBlock {
 	Letters data;                    // SequenceSet layout
 	std::vector<int64_t> limits;
 	std::vector<std::string> ids;
+	std::vector<int64_t> rec_begin;  // a FASTA file's records: byte offset of every '>' in the (inflated) text, then the text's size; empty for other input
 	int64_t letters = 0;
 	void begin() { data.assign(256, 31); limits.assign(1, 256); }
 	void push(const std::vector<int8_t>& s, const std::string& id)
@@ -89,8 +91,9 @@ std::string short_id(const std::string& title)
 // (File::Flags::DETECT_COMPRESSION, data/fasta/fasta_file.cpp:68; zlib inflates it, also concatenated members); FASTQ
 // (first character '@', guess_format fasta_file.cpp:43-52) is rewritten as FASTA text -- title, letters up to the '+' line, as many
 // quality characters as letters skipped (FastqTokenizer::read_record, data/fasta/parser.h:238-270).
-std::vector<char> read_sequence_text(const std::string& path)
+std::vector<char> read_sequence_text(const std::string& path, bool* fastq = nullptr)
 {
+	if (fastq) *fastq = false;
 	std::vector<char> file;
 	unsigned char magic[2] = { 0, 0 };
 	const bool from_stdin = path.empty() || path == "-";       // File::Flags::TREAT_BLANK_AS_STDIN: zlib reads plain and gzip data alike
@@ -125,6 +128,7 @@ std::vector<char> read_sequence_text(const std::string& path)
 	if (file[0] != '>' && file[0] != '@')
 		throw std::runtime_error("Error detecting input file format (when treating as text file). First line must begin with '>' (FASTA) or '@' (FASTQ).");
 	if (file[0] == '>') return file;
+	if (fastq) *fastq = true;
 	std::vector<char> fasta;
 	fasta.reserve(file.size() / 2 + 16);
 	const char* p = file.data();
@@ -162,7 +166,8 @@ std::vector<char> read_sequence_text(const std::string& path)
 
 void read_fasta(const std::string& path, SeqBlock& b)
 {
-	const std::vector<char> file = read_sequence_text(path);
+	bool fastq = false;
+	const std::vector<char> file = read_sequence_text(path, &fastq);
 	b.begin();
 	b.data.reserve(256 + file.size() + 256);
 	letter_of('A');                                        // builds the letter map
@@ -185,7 +190,7 @@ void read_fasta(const std::string& path, SeqBlock& b)
 		const char* next = nl ? nl + 1 : end;
 		if (le > p && le[-1] == '\r') --le;
 		if (le > p) {
-			if (*p == '>') { flush(); id.assign(p + 1, le); have = true; seq_begin = b.data.size(); }
+			if (*p == '>') { flush(); id.assign(p + 1, le); have = true; seq_begin = b.data.size(); if (!fastq) b.rec_begin.push_back((int64_t)(p - file.data())); }
 			else {
 				if (!have) throw std::runtime_error("FASTA format error: missing '>' in " + path);
 				for (const char* c = p; c < le; ++c) {
@@ -199,6 +204,7 @@ void read_fasta(const std::string& path, SeqBlock& b)
 		p = next;
 	}
 	flush();
+	if (!fastq) b.rec_begin.push_back((int64_t)file.size());
 	b.finish();
 }
 
@@ -480,6 +486,7 @@ struct Options {
 	int unal = -1;                  // --unal: report queries without alignments (-1 = the format's default)
 	std::string header;             // --header [simple|verbose|0]
 	double min_id = 0, query_cover = 0, subject_cover = 0, min_score = 0;      // --id, --query-cover, --subject-cover, --min-score
+	double min_len_ratio = 0;       // --min-len-ratio: the mutual-coverage search's length-ratio cutoff in the seed stage (0 = not given)
 	double approx_id = 0; bool approx_id_given = false;      // --approx-id (config.approx_min_id)
 };
 
@@ -519,6 +526,7 @@ Options parse(int argc, char** argv)
 		else if (a == "--approx-id") { o.approx_id = std::atof(need(i).c_str()); o.approx_id_given = true; }
 		else if (a == "--query-cover") o.query_cover = std::atof(need(i).c_str());
 		else if (a == "--subject-cover") o.subject_cover = std::atof(need(i).c_str());
+		else if (a == "--min-len-ratio") o.min_len_ratio = std::atof(need(i).c_str());
 		else if (a == "--min-score") o.min_score = std::atof(need(i).c_str());
 		else if (a == "--no-self-hits") o.no_self_hits = true;
 		else if (a == "--matrix") o.matrix = need(i);
@@ -670,6 +678,46 @@ std::vector<Range> split_blocks(const std::vector<int64_t>& unit_letters, int64_
 	return r;
 }
 
+// Block::length_sorted (data/block/block.cpp:229-255) of the sequences [begin, end) of b, in place: they are put into
+// (length, index) descending order, their ids with them; the sequences outside the range stay. order (optional) receives
+// for every place of the range the index, counted from `begin`, of the sequence that now stands there.
+void length_sort_range(SeqBlock& b, size_t begin, size_t end, std::vector<int64_t>* order_out = nullptr)
+{
+	std::vector<int64_t> order(end - begin);
+	dmnd::length_sort_order(b.limits.data() + begin, (int64_t)(end - begin), order.data());
+	const Letters old(b.data.begin() + b.limits[begin], b.data.begin() + b.limits[end]);
+	const std::vector<int64_t> old_limits(b.limits.begin() + (ptrdiff_t)begin, b.limits.begin() + (ptrdiff_t)end + 1);
+	std::vector<std::string> old_ids;
+	if (b.ids.size() >= end) old_ids.assign(std::make_move_iterator(b.ids.begin() + (ptrdiff_t)begin), std::make_move_iterator(b.ids.begin() + (ptrdiff_t)end));
+	int64_t at = b.limits[begin];
+	for (size_t k = 0; k < order.size(); ++k) {
+		const size_t j = (size_t)order[k];
+		const int64_t n = old_limits[j + 1] - old_limits[j];      // letters + delimiter
+		std::memcpy(b.data.data() + at, old.data() + (old_limits[j] - old_limits[0]), (size_t)n);
+		at += n;
+		b.limits[begin + k + 1] = at;
+		if (!old_ids.empty()) b.ids[begin + k] = std::move(old_ids[j]);
+	}
+	if (order_out) order_out->swap(order);
+}
+
+// The reference reads a FASTA file by bytes (SequenceFile::load_parallel with byte_limited, FastaFile::raw_chunk): a block takes
+// max_bytes of the text and then the rest of the record it stopped in, i.e. every record that begins less than max_bytes behind
+// the block's first. rec_begin: SeqBlock::rec_begin.
+std::vector<Range> split_blocks_bytes(const std::vector<int64_t>& rec_begin, int64_t max_bytes)
+{
+	std::vector<Range> r;
+	const size_t n = rec_begin.size() - 1;
+	size_t i = 0;
+	while (i < n) {
+		Range b{ i, i };
+		do { ++b.end; } while (b.end < n && rec_begin[b.end] - rec_begin[i] < max_bytes);
+		r.push_back(b);
+		i = b.end;
+	}
+	return r;
+}
+
 // sequences [begin, end) of a loaded file as a block of their own (SequenceSet layout with its padding)
 SeqBlock slice(const SeqBlock& all, size_t begin, size_t end)
 {
@@ -700,10 +748,14 @@ int run_blastp(const Options& o)
 	if (!tantan && !seg && o.masking != "0" && o.masking != "none")
 		throw std::runtime_error("Invalid value for --masking: " + o.masking + " (none / 0, seg, tantan / 1)");
 	if (!o.motif_masking.empty() && o.motif_masking != "0" && o.motif_masking != "1") throw std::runtime_error("Permitted values for --motif-masking: 0, 1");
-	// equal query and subject cover of 50 % and more switches the reference to its mutual-coverage search (length-sorted blocks, a
-	// length-ratio cutoff inside the seed stage: run/config.cpp:156-159) -- a clustering path that is not part of this build
-	if (o.command == "blastp" && o.query_cover >= 50 && o.query_cover == o.subject_cover)
-		throw std::runtime_error("--query-cover equal to --subject-cover (>= 50) selects the reference's mutual-coverage search, which is not part of this build; use different values");
+	// The mutual-coverage search (run/config.cpp:156-165): --min-len-ratio, or equal query and subject cover of 50 % and more, which
+	// stand for a ratio of their own. Both blocks of every pair are length-sorted then (Block::length_sorted) and the seed stage
+	// only compares pairs whose lengths pass the ratio (dmnd_set_min_length_ratio); all output follows the sorted query order.
+	if (o.command == "blastx" && o.min_len_ratio != 0.0) throw std::runtime_error("--min-len-ratio is not supported for translated searches");
+	const double mlr = o.command == "blastp" ? dmnd::mutual_cover_ratio(o.query_cover, o.subject_cover, o.min_len_ratio) : 0.0;
+	if (mlr < 0.0 || mlr > 1.0) throw std::runtime_error("Invalid value for --min-len-ratio: a ratio lies in [0, 1].");
+	if (mlr > 0.0 && o.global_ranking > 0) throw std::runtime_error("--global-ranking together with a minimum length ratio (--min-len-ratio, or equal --query-cover and --subject-cover of 50 and more) is not part of this build.");
+	if (mlr > 0.0 && o.gpus > 1) throw std::runtime_error("--gpus above 1 together with a minimum length ratio (--min-len-ratio, or equal --query-cover and --subject-cover of 50 and more) is not part of this build.");
 	// basic/config.cpp:688, :822-825: frameshift alignment is for translated queries, range culling for frameshift alignment
 	if (o.global_ranking > 0 && (o.range_culling || o.frameshift > 0)) throw std::runtime_error("Global ranking is not supported in this mode.");
 	if (o.frameshift != 0 && o.command == "blastp") throw std::runtime_error("Frameshift alignments are only supported for translated searches.");
@@ -848,7 +900,31 @@ int run_blastp(const Options& o)
 	}
 	int64_t t_max_letters = max_letters;
 	if (n_gpus > 1) t_max_letters = std::min<int64_t>(max_letters, (db.letters + n_gpus - 1) / n_gpus);
-	const std::vector<Range> q_blocks = split_blocks(q_units, max_letters), t_blocks = split_blocks(t_units, t_max_letters);
+	// (which query block a query falls into shows in the output of the mutual-coverage search alone, whose order is that of the
+	// length-sorted blocks: there the cut of a FASTA query file is the reference's, by bytes)
+	const bool q_by_bytes = mlr > 0.0 && q_all.rec_begin.size() == n_queries + 1 && n_queries > 0;
+	const std::vector<Range> q_blocks = q_by_bytes ? split_blocks_bytes(q_all.rec_begin, max_letters) : split_blocks(q_units, max_letters), t_blocks = split_blocks(t_units, t_max_letters);
+	// mutual-coverage search: every query block is replaced by its length-sorted copy before it is masked (run/double_indexed.cpp:727-731),
+	// and the records, --un and --al follow that order. The block cut above is the file's; from here on q_all IS the sorted file, and
+	// q_oid keeps every query's place in the file for the one format that prints it (XML).
+	std::vector<uint32_t> q_oid;
+	if (mlr > 0.0) {
+		std::cerr << "Min length ratio: " << mlr << "\n";
+		q_oid.resize(n_queries);
+		for (const Range& qr : q_blocks) {
+			std::vector<int64_t> order;
+			length_sort_range(q_all, qr.begin, qr.end, &order);
+			for (size_t k = 0; k < order.size(); ++k) q_oid[qr.begin + k] = (uint32_t)(qr.begin + (size_t)order[k]);
+		}
+	}
+	// ... and so is every reference block, right after it was read (run/double_indexed.cpp:112-115): ord = block id -> database ordinal
+	auto sort_reference_block = [mlr](SeqBlock& b, const Range& tr, std::vector<uint32_t>& ord) {
+		if (mlr <= 0.0) return;
+		std::vector<int64_t> order;
+		length_sort_range(b, 0, tr.end - tr.begin, &order);
+		ord.resize(order.size());
+		for (size_t k = 0; k < order.size(); ++k) ord[k] = (uint32_t)(tr.begin + (size_t)order[k]);
+	};
 	if (q_blocks.size() > 1 || t_blocks.size() > 1)
 		std::cerr << "Block size = " << max_letters << "  query blocks=" << q_blocks.size() << " reference blocks=" << t_blocks.size() << "\n";
 	const int load_threads = o.threads > 0 ? o.threads : 8;
@@ -894,6 +970,7 @@ int run_blastp(const Options& o)
 		chk(dmnd_set_top_percent(c, o.top));
 		chk(dmnd_set_filters(c, o.min_id, o.query_cover, o.subject_cover, o.min_score));
 		chk(dmnd_set_approx_id(c, std::max(0.0, o.approx_id)));      // (the reference reads a value <= 0 as off)
+		chk(dmnd_set_min_length_ratio(c, mlr));
 		chk(dmnd_set_comp_based_stats(c, o.cbs));
 		chk(dmnd_set_query_contexts(c, blastx ? 6 : 1));
 		if (o.global_ranking > 0 && !rank_host) chk(dmnd_set_seed_hits_resident(c, 1));      // the device form ranks the hits in HBM: the seed search brings none back
@@ -1011,7 +1088,7 @@ int run_blastp(const Options& o)
 	// --no-self-hits: the library finds query / target pairs with the same letters and asks here whether the titles agree too
 	struct SelfCtx { const std::vector<std::string>* qtitles; const Database* db; size_t q0 = 0, t0 = 0; const std::vector<uint32_t>* ordinals = nullptr; };      // ordinals: block id -> database ordinal (globally ranked targets)
 	std::vector<SelfCtx> self_ctx((size_t)n_gpus);
-	struct Held { SeqBlock block; size_t index = (size_t)-1; bool ahead = false; };      // ahead: read AND uploaded before the query phase, not yet masked
+	struct Held { SeqBlock block; size_t index = (size_t)-1; bool ahead = false; std::vector<uint32_t> ord; };      // ord (mutual-coverage search): the length-sorted block's ids -> database ordinals      // ahead: read AND uploaded before the query phase, not yet masked
 	std::vector<Held> held_blocks((size_t)n_gpus);                  // the reference block every GPU's thread holds in host memory
 	// f(g) on one host thread per GPU; the first error is rethrown on the calling thread
 	auto on_each_gpu = [&](const std::function<void(int)>& f) {
@@ -1041,6 +1118,7 @@ int run_blastp(const Options& o)
 					Held& h = held_blocks[(size_t)g];
 					h.block = first_block[(size_t)g].get();
 					h.index = (size_t)g;
+					sort_reference_block(h.block, t_blocks[(size_t)g], h.ord);
 					g_timeline.mark("reference block " + std::to_string(g) + " in host memory");
 					const auto t0 = std::chrono::steady_clock::now();
 					const Range& tr = t_blocks[(size_t)g];
@@ -1080,6 +1158,7 @@ int run_blastp(const Options& o)
 		std::vector<dmnd_ranked_target> rank_table(o.global_ranking > 0 ? (qr.end - qr.begin) * (size_t)o.global_ranking : 0, dmnd_ranked_target{ 0, 0, 0, 0, 0 });
 		std::vector<dmnd_match> joined;                       // the query block's records against all reference blocks
 		std::vector<uint8_t> joined_gpu;                      // ... and the GPU that produced each of them (the RCCL merge sends from there)
+		std::vector<uint32_t> joined_block;                   // ... and, mutual-coverage search, their reference block (the join below)
 		std::vector<uint8_t> arena;                           // ... and their transcripts, if the output format reads them
 		std::vector<char> seeded(qr.end - qr.begin, 0);       // queries with at least one seed hit (what the unaligned report depends on)
 		on_each_gpu([&](int g) {
@@ -1098,6 +1177,7 @@ int run_blastp(const Options& o)
 			if (fresh && !in_hbm) {
 				held.block = bi == (size_t)g && first_block[(size_t)g].valid() ? first_block[(size_t)g].get() : next.valid() ? next.get() : db.load(tr.begin, tr.end, threads);
 				held.index = bi;
+				sort_reference_block(held.block, tr, held.ord);
 				g_timeline.mark("reference block " + std::to_string(bi) + " in host memory");
 			}
 			const size_t bn = bi + (size_t)n_gpus;
@@ -1214,7 +1294,7 @@ int run_blastp(const Options& o)
 			t0 = std::chrono::steady_clock::now();
 			if (o.no_self_hits) {
 				if (blastx) throw std::runtime_error("--no-self-hits is not supported for blastx");      // basic/config.cpp:677
-				self_ctx[(size_t)g] = SelfCtx{ &qtitles, &db, qr.begin, tr.begin };
+				self_ctx[(size_t)g] = SelfCtx{ &qtitles, &db, qr.begin, tr.begin, mlr > 0.0 ? &held.ord : nullptr };
 				chk(dmnd_set_no_self_hits(ctx, [](void* u, uint32_t q, uint32_t t) -> int {
 					const SelfCtx& s = *static_cast<const SelfCtx*>(u);
 					return (*s.qtitles)[s.q0 + q] == s.db->title(s.ordinals ? (size_t)(*s.ordinals)[t] : s.t0 + t) ? 1 : 0;
@@ -1251,11 +1331,12 @@ int run_blastp(const Options& o)
 			std::lock_guard<std::mutex> lock(merge_mutex);
 			for (const dmnd_seed_hit& h : hits) seeded[h.query / C] = 1;
 			for (dmnd_match& m : mine) {
-				m.query += (uint32_t)qr.begin; m.target += (uint32_t)tr.begin;
+				m.query += (uint32_t)qr.begin; m.target = mlr > 0.0 ? held.ord[m.target] : m.target + (uint32_t)tr.begin;
 				if (need_transcripts) m.hsp.transcript_off += (int64_t)arena.size();
 			}
 			joined.insert(joined.end(), mine.begin(), mine.end());
 			joined_gpu.insert(joined_gpu.end(), mine.size(), (uint8_t)g);
+			if (mlr > 0.0) joined_block.insert(joined_block.end(), mine.size(), (uint32_t)bi);
 			arena.insert(arena.end(), my_arena.begin(), my_arena.end());
 			ms_upload += up; ms_mask += mk; ms_seed += sd; ms_ext += ex;
 			total_hits += n_hits;
@@ -1335,7 +1416,7 @@ int run_blastp(const Options& o)
 		// DMND_CLI_RCCL=1 takes that path with one GPU too (RCCL with itself), =0 keeps the host join.
 		static const int rccl_env = [] { const char* e = std::getenv("DMND_CLI_RCCL"); return e ? std::atoi(e) : -1; }();
 		const bool rank_join = t_blocks.size() > 1 && o.global_ranking == 0 && o.max_hsps == 1 && !o.range_culling && !joined.empty()
-			&& (rccl_env >= 0 ? rccl_env != 0 : n_gpus > 1);
+			&& mlr <= 0.0 && (rccl_env >= 0 ? rccl_env != 0 : n_gpus > 1);
 		bool rank_joined = false;
 		if (rank_join) {
 			std::vector<std::vector<dmnd_match>> per_gpu((size_t)n_gpus);
@@ -1363,11 +1444,49 @@ int run_blastp(const Options& o)
 			}
 			else chk(jrc);
 		}
+		// Mutual-coverage search over several reference blocks. The reference merges the blocks' lists of a query by their heads
+		// (JoinRecord::cmp_evalue: e-value, score, database ordinal), and a length-sorted block's list is in the order of ITS ids, so
+		// among targets with equal e-value and score a block's list is not in ordinal order and the merge is not a sort by ordinal: a
+		// target leaves its list when the largest ordinal of the tied targets of that list up to it is the smallest head. The targets
+		// get their places in that order as stand-in ordinals for the join and their database ordinals back behind it.
+		std::vector<uint32_t> place_oid;
+		if (mlr > 0.0 && t_blocks.size() > 1 && !joined.empty()) {
+			const bool by_score = o.top >= 0.0;                 // --top: the merge runs on JoinRecord::cmp_score
+			struct Grp { size_t first, n; uint32_t key; };
+			std::vector<Grp> grp;
+			for (size_t k = 0; k < joined.size();) {
+				size_t e = k + 1;                                 // the records of one target (--max-hsps) follow each other
+				while (e < joined.size() && joined_block[e] == joined_block[k] && joined[e].query == joined[k].query && joined[e].target == joined[k].target) ++e;
+				uint32_t key = joined[k].target;
+				if (!grp.empty()) {
+					const size_t pk = grp.back().first;
+					const dmnd_match& pm = joined[pk];
+					if (joined_block[pk] == joined_block[k] && pm.query == joined[k].query && pm.hsp.score == joined[k].hsp.score && (by_score || pm.evalue == joined[k].evalue))
+						key = std::max(key, grp.back().key);
+				}
+				grp.push_back(Grp{ k, e - k, key });
+				k = e;
+			}
+			std::stable_sort(grp.begin(), grp.end(), [&](const Grp& x, const Grp& y) {
+				const dmnd_match& a = joined[x.first];
+				const dmnd_match& b = joined[y.first];
+				if (a.query != b.query) return a.query < b.query;
+				if (!by_score && a.evalue != b.evalue) return a.evalue < b.evalue;
+				if (a.hsp.score != b.hsp.score) return a.hsp.score > b.hsp.score;
+				return x.key < y.key;                            // (equal keys: targets of one block, which stay in its order)
+			});
+			place_oid.resize(grp.size());
+			for (size_t i = 0; i < grp.size(); ++i) {
+				place_oid[i] = joined[grp[i].first].target;
+				for (size_t k = 0; k < grp[i].n; ++k) joined[grp[i].first + k].target = (uint32_t)i;
+			}
+		}
 		if (!rank_joined)
 		// the join's culler is the one TargetCulling::get picks (output/target_culling.cpp:22-28): RangeCulling with --range-culling
 		if (t_blocks.size() > 1 && o.global_ranking == 0) chk(o.range_culling ? dmnd_join_blocks_range(joined.data(), (int64_t)joined.size(), o.k, o.top, o.range_cover, &n_matches)
 			: o.top >= 0.0 ? dmnd_join_blocks_top(joined.data(), (int64_t)joined.size(), o.top, &n_matches)
 			: dmnd_join_blocks(joined.data(), (int64_t)joined.size(), o.k, &n_matches));
+		if (!place_oid.empty()) for (int64_t k = 0; k < n_matches; ++k) joined[(size_t)k].target = place_oid[joined[(size_t)k].target];
 		if (t_blocks.size() > 1 && o.frameshift > 0 && need_transcripts) {
 			// Several reference blocks: the reference prints from the joined IntermediateRecords, and with a frameshift penalty those
 			// carry transcripts (output_format.cpp:256-257), so every printed Hsp is re-counted from its transcript by HspContext::parse
@@ -1420,7 +1539,7 @@ int run_blastp(const Options& o)
 			const int32_t qlen = blastx ? source_len[qi] : (int32_t)(q_all.limits[qi + 1] - q_all.limits[qi] - 1);
 			big.resize(qtitles[qi].size() + 256);
 			if (fmt == FMT_PAIRWISE) put(dmnd_format_pairwise_intro(qtitles[qi].c_str(), qlen, has ? 0 : 1, big.data(), (int64_t)big.size()), big.data());
-			else if (fmt == FMT_XML) { big.resize(qtitles[qi].size() * 6 + 512); put(dmnd_format_xml_query_intro(qtitles[qi].c_str(), (int64_t)qi, qlen, big.data(), (int64_t)big.size()), big.data()); }
+			else if (fmt == FMT_XML) { big.resize(qtitles[qi].size() * 6 + 512); put(dmnd_format_xml_query_intro(qtitles[qi].c_str(), q_oid.empty() ? (int64_t)qi : (int64_t)q_oid[qi], qlen, big.data(), (int64_t)big.size()), big.data()); }
 			else if (!has && fmt == FMT_FIELDS) {
 				const size_t local = (qi - qr.begin) * C;
 				const int32_t l0 = (int32_t)(q.limits[local + 1] - q.limits[local] - 1);
@@ -1832,7 +1951,7 @@ int main(int argc, char** argv)
 				"scoring      --matrix BLOSUM45|50|62|80|90|PAM30|70|250  --gapopen N  --gapextend N  --comp-based-stats 0|1\n"
 				"masking      --masking tantan|seg|none  --motif-masking 0|1\n"
 				"extension    --ext banded-fast|banded-slow|full\n"
-				"reporting    -k N  --max-hsps N  --global-ranking N  --top PCT  -e EVALUE  --min-score BITS  --id PCT  --approx-id PCT  --query-cover PCT  --subject-cover PCT  --no-self-hits\n"
+				"reporting    -k N  --max-hsps N  --global-ranking N  --top PCT  -e EVALUE  --min-score BITS  --id PCT  --approx-id PCT  --query-cover PCT  --subject-cover PCT  --min-len-ratio R  --no-self-hits\n"
 				"             --unal 0|1  --un FILE  --al FILE  --header [simple|verbose]  --compress 1  --salltitles  --sallseqid\n"
 				"formats      -f 6 [FIELD...] | 0 (pairwise) | 5 (XML) | 100 (DAA) | 101 (SAM) | 103 (PAF)\n"
 				"translated   --strand both|plus|minus  --query-gencode N  --min-orf N\n"

@@ -208,6 +208,9 @@ struct dmnd_ctx {
 	dmnd_same_title_fn same_title = nullptr;   // --no-self-hits: title comparison of the caller (dmnd_set_no_self_hits)
 	void* same_title_user = nullptr;
 	bool reuse_query_index = false;            // dmnd_set_query_index_reuse
+	double min_length_ratio = 0.0;             // dmnd_set_min_length_ratio (mutual-coverage search); 0 = off
+	int64_t seed_qwin_n = 0;                   // ... targets the windows of the last search were built for; 0: it ran without a ratio
+	dmnd::DevBuf seed_qwin;                    // ... per target of the reference block its window of admissible query positions (rebuilt by every search)
 	uint64_t query_generation = 0;             // bumped whenever the query block or its masks change
 	uint64_t target_generation = 0;            // bumped whenever the reference block's letters, limits, soft-mask view or alias change
 	// sliced long-seed stream (seed_slices_core.h, seed_ref_state.h): what a block generation's searches keep of the reference side -- the

@@ -249,6 +249,30 @@ extern "C" int dmnd_set_query_index_reuse(dmnd_ctx* c, int on)
 	return DMND_OK;
 }
 
+extern "C" int dmnd_set_min_length_ratio(dmnd_ctx* c, double ratio)
+{
+	if (!c) return fail(DMND_E_ARG, "dmnd_set_min_length_ratio: ctx is NULL");
+	if (!(ratio >= 0.0 && ratio <= 1.0)) return fail(DMND_E_ARG, "dmnd_set_min_length_ratio: the ratio lies in [0, 1]");
+	c->min_length_ratio = ratio;
+	return DMND_OK;
+}
+
+extern "C" int dmnd_length_sort_order(const int64_t* limits, int64_t n, int64_t* order)
+{
+	if (n < 0 || (n > 0 && (!limits || !order))) return fail(DMND_E_ARG, "dmnd_length_sort_order: bad argument");
+	length_sort_order(limits, n, order);
+	return DMND_OK;
+}
+
+extern "C" int dmnd_seed_query_windows(dmnd_ctx* c, uint32_t* out, int64_t n_targets)
+{
+	if (!c || !out) return fail(DMND_E_ARG, "dmnd_seed_query_windows: NULL argument");
+	if (c->seed_qwin_n <= 0 || n_targets != c->seed_qwin_n) return fail(DMND_E_ARG, "dmnd_seed_query_windows: the last seed search built no windows for that many targets");
+	HIP_TRY(hipSetDevice(c->device));
+	static_assert(sizeof(SeedQueryWindow) == 2 * sizeof(uint32_t), "two words per window");
+	return download_bytes(c, out, c->seed_qwin.p, (size_t)n_targets * sizeof(SeedQueryWindow));
+}
+
 extern "C" int dmnd_seed_kernel_ms(const dmnd_ctx* c, double ms[5])
 {
 	if (!c || !ms) return fail(DMND_E_ARG, "dmnd_seed_kernel_ms: bad argument");
@@ -540,6 +564,14 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 		for (int i = 0; i < sp.n_shapes; ++i)
 			if (sp.shape_len[i] > 16) return fail(DMND_E_ARG, "dmnd_seed_search: query-indexed mode with a shape longer than 16 letters");
 	}
+	// mutual-coverage search (length_ratio_core.h): the windows of the pair filters are ranges only over length-sorted blocks
+	const bool mlr_on = c->min_length_ratio > 0.0;
+	c->seed_qwin_n = 0;
+	if (mlr_on) {
+		if (c->query_contexts != 1 || sp.query_translated) return fail(DMND_E_ARG, "dmnd_seed_search: a minimum length ratio is not supported for translated searches");
+		if (!lengths_non_increasing(ql.data(), (int64_t)ql.size() - 1)) return fail(DMND_E_ARG, "dmnd_seed_search: with a minimum length ratio the query block must be length-sorted (dmnd_length_sort_order)");
+		if (!lengths_non_increasing(tl.data(), (int64_t)tl.size() - 1)) return fail(DMND_E_ARG, "dmnd_seed_search: with a minimum length ratio the reference block must be length-sorted (dmnd_length_sort_order)");
+	}
 	HIP_TRY(hipSetDevice(c->device));
 	hipStream_t st = c->stream;
 	const int64_t q_begin = ql.front(), q_end = ql.back(), t_begin = tl.front(), t_end = tl.back();
@@ -597,6 +629,12 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 		HIP_TRY(launch_seed_clear(z, st));
 	}
 	bool pristine = true;                                // the counters and the need map are as the clear above left them
+	if (mlr_on) {                                         // per target of THIS reference block: rebuilt by every call, whatever is kept of the query side
+		const int64_t nt = (int64_t)tl.size() - 1;
+		if (int rc = c->seed_qwin.ensure((size_t)nt * sizeof(SeedQueryWindow))) return rc;
+		HIP_TRY(launch_seed_qwin(c->d_limits[DMND_QUERY].as<int64_t>(), (int64_t)ql.size() - 1, c->d_limits[DMND_TARGET].as<int64_t>(), nt, c->min_length_ratio, c->seed_qwin.as<SeedQueryWindow>(), st));
+		c->seed_qwin_n = nt;
+	}
 	if (int rc = dmnd_seed_query_ids(c)) return rc;      // (filled at the upload: nothing to do here but for a shared block or a grown buffer)
 
 	// fused pipeline: 4-bit copies of the query and the reference block for the Hamming pre-filter
@@ -628,6 +666,8 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 		a.qlimits = c->d_limits[DMND_QUERY].as<int64_t>();
 		a.q_begin = q_begin; a.q_end = q_end; a.t_begin = t_begin; a.t_end = t_end;
 		a.qid_of = c->qid_of.as<uint32_t>(); a.mask_time = c->mask_time.as<uint8_t>();
+		a.tlimits = c->d_limits[DMND_TARGET].as<int64_t>(); a.n_targets = (int64_t)tl.size() - 1;
+		a.qwin = mlr_on ? c->seed_qwin.as<SeedQueryWindow>() : nullptr;
 		a.slots = reinterpret_cast<SeedSlot*>(c->seed_keys.as<char>() + (size_t)own * slot_bytes);
 		a.slot_shift = z.slot_shift;
 		a.qlist = c->seed_qlist.as<uint32_t>() + (size_t)own * nq_pos;

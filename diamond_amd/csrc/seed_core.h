@@ -403,7 +403,11 @@ DMND_HD int ungapped_cutoff(const SeedParams& c, int query_len)
 // rank among the tile's Hamming survivors. Only needed when the exact score exceeds 255 (rare): such pairs are deferred
 // by the pair kernel and resolved in a second pass over a sorted copy of the joined positions of the seeds concerned.
 // locs[k] holds the position in its low 40 bits (the sort key of the second pass is seed slot << 40 | position).
-DMND_HD int simd_batch_size_sorted(const SeedParams& c, const uint64_t* locs, int64_t n, const int8_t* tdata, const int8_t* q, int64_t sloc)
+// admit(position): the mutual-coverage search's length test of the position's target against the pair's query
+// (length_ratio_core.h) -- the reference forms the batches behind it, so a joined position that fails it is no batch mate, while
+// the tiles are still cut over all joined positions of the seed.
+template<typename Admit>
+DMND_HD int simd_batch_size_sorted(const SeedParams& c, const uint64_t* locs, int64_t n, const int8_t* tdata, const int8_t* q, int64_t sloc, Admit admit)
 {
 	const uint64_t LOC = ((uint64_t)1 << 40) - 1;
 	int64_t lo = 0, hi = n;                                       // rank = number of positions < sloc
@@ -413,11 +417,17 @@ DMND_HD int simd_batch_size_sorted(const SeedParams& c, const uint64_t* locs, in
 	if (T > 0 && n > T) { t_lo = rank / T * T; t_hi = t_lo + T < n ? t_lo + T : n; }
 	int64_t L = 0, r = 0;
 	for (int64_t k = t_lo; k < t_hi; ++k) {
+		if (!admit((int64_t)(locs[k] & LOC))) continue;
 		if (fingerprint_id(q, tdata + (int64_t)(locs[k] & LOC)) < c.hamming_filter_id) continue;
 		++L; r += k < rank;
 	}
 	const int64_t lanes = c.simd_lanes, left = L - r / lanes * lanes;
 	return (int)(left < lanes ? left : lanes);
+}
+struct SeedAdmitAll { DMND_HD bool operator()(int64_t) const { return true; } };
+DMND_HD int simd_batch_size_sorted(const SeedParams& c, const uint64_t* locs, int64_t n, const int8_t* tdata, const int8_t* q, int64_t sloc)
+{
+	return simd_batch_size_sorted(c, locs, n, tdata, q, sloc, SeedAdmitAll());
 }
 
 // Hash of a seed for the query seed table: two independent 32-bit mixes (murmur3-style finalisers on 32-bit lanes).

@@ -6,6 +6,7 @@
 #include "seed_core.h"
 #include "seed_chain.h"
 #include "seed_slices_core.h"
+#include "length_ratio_core.h"
 
 namespace dmnd {
 
@@ -30,6 +31,10 @@ struct SeedDeferred { int64_t sloc; uint32_t slot, x; int32_t score, pad; };
 // A (joined reference position sloc of the seed in `slot`, query position x) pair that passed the Hamming filter
 struct SeedSurvivor { uint32_t slot, x; int64_t sloc; };
 
+// Mutual-coverage search (length_ratio_core.h): the query positions [first, end), counted from q_begin, of the queries whose
+// length passes the ratio test against one target -- one range, since both blocks are length-sorted (seed_qwin_kernel)
+struct SeedQueryWindow { uint32_t first, end; };
+
 // A survivor whose stage-2 ungapped score passed the cutoff: input of the left-most rule (seed_leftmost_kernel)
 struct SeedScored { uint32_t slot, x; int64_t sloc; int32_t score, chunk; };
 
@@ -40,6 +45,10 @@ struct SeedArgs {
 	const int64_t* qlimits;                       // query block limits (HBM)
 	int64_t q_begin, q_end, t_begin, t_end;       // letter ranges [limits[0], limits[n])
 	const uint32_t* qid_of;                       // query position -> query id
+	// mutual-coverage search: reference block limits (HBM) and per target its window of admissible query positions; qwin = NULL: ratio off,
+	// and then every launch takes the kernel instance that holds no length test at all
+	const int64_t* tlimits; int64_t n_targets;
+	const SeedQueryWindow* qwin;
 	uint8_t* mask_time;                           // per query letter: (shape, chunk) time of its SEED_MASK bit
 	// per-shape query seed table
 	SeedSlot* slots;              // 16-byte slots: key, list start (or the seed's one query position), state | list size
@@ -108,6 +117,8 @@ struct SeedClear {
 };
 hipError_t launch_seed_clear(const SeedClear& z, hipStream_t st);
 hipError_t launch_seed_qid(const int64_t* limits, int64_t n_seqs, uint32_t* qid_of, hipStream_t st);
+// qwin[t] for the n_targets targets of tlimits against the n_queries length-sorted queries of qlimits (both device arrays of n + 1 limits)
+hipError_t launch_seed_qwin(const int64_t* qlimits, int64_t n_queries, const int64_t* tlimits, int64_t n_targets, double min_length_ratio, SeedQueryWindow* qwin, hipStream_t st);
 // the folded need map that seed_collect's workgroups keep in LDS (2^13 words = 32 KB); it lies behind SeedArgs::need_bits
 enum { SEED_NEED_FOLD_WORDS = 8192 };
 // query seed positions whose shape window touches a soft-masked stretch get their mask time (MaskingTable::remove's bit mask)

@@ -492,13 +492,29 @@ __device__ __forceinline__ int window_identity(const uint32_t* a, const uint32_t
 // Lists longer than LIGHT are filtered by the whole workgroup. Pairs of a non-complex seed (SLOT_LOWC) are dropped: the seed
 // only gets its JOINED mark for seed_mask_kernel. FUSED implies BYCLASS: seed_api.hip fails a fused search whose geometry
 // has no key classes.
+// Mutual-coverage search: the window of admissible query positions of the target that holds reference position sloc -- the last
+// target that starts at or before it. Evaluated once per joined reference position; the pair test is then two integer compares.
+__device__ __forceinline__ SeedQueryWindow seed_window_at(const SeedArgs& a, int64_t sloc)
+{
+	int64_t lo = 0, hi = a.n_targets;
+	while (hi - lo > 1) {
+		const int64_t mid = (lo + hi) >> 1;
+		if (a.tlimits[mid] <= sloc) lo = mid; else hi = mid;
+	}
+	return a.qwin[lo];
+}
+__device__ __forceinline__ bool seed_window_holds(SeedQueryWindow w, uint32_t x) { return x >= w.first && x < w.end; }
+
 enum { SEED_CLASS_TILES = 4 };      // tiles of 4096 window starts per class workgroup (kernel and launch)
 // DMND_SEED_PHASES=1 (SeedArgs::phase_ticks): thread 0 of every workgroup adds the 100 MHz ticks between its phase boundaries
 #define PHASE_MARK(i) do { if (a.phase_ticks && threadIdx.x == 0) { const uint64_t now_ = wall_clock64(); atomicAdd(&a.phase_ticks[i], (unsigned long long)(now_ - phase_t_)); phase_t_ = now_; } } while (0)
-template<bool LEVEL2, bool HASHED, bool FUSED, bool BYCLASS = false>
+// MLR (FUSED only; mutual-coverage search, SeedArgs::qwin): the window of admissible query positions is found once per staged
+// join and kept beside it in LDS; a pair whose query position lies outside it is dropped before any letter is read.
+template<bool LEVEL2, bool HASHED, bool FUSED, bool BYCLASS = false, bool MLR = false>
 __global__ __launch_bounds__(256) void seed_stream_fast_kernel(SeedArgs a, int sid, uint64_t map_lo, uint64_t map_hi, int64_t base, uint64_t care64)
 {
 	static_assert(!FUSED || BYCLASS, "the fused stream runs by key class");
+	static_assert(!MLR || FUSED, "only the fused stream filters pairs");
 	// Joined positions are staged in LDS and flushed with ONE atomic on the shared counter per workgroup: an atomicAdd per
 	// match on a single address serialises at ~4.5 ns each (measured: 3.3 M matches = 14.8 ms per shape in default mode,
 	// 22 M = 98 ms per shape in --sensitive), which dwarfed the 1.6 ms stream itself.
@@ -515,6 +531,7 @@ __global__ __launch_bounds__(256) void seed_stream_fast_kernel(SeedArgs a, int s
 	constexpr unsigned SURV = FUSED ? 128 : 1, HEAVY = FUSED ? 64 : 1, FSTAGE = FUSED ? STAGE : 1;
 	__shared__ uint32_t st_head[FSTAGE];
 	__shared__ uint16_t st_count[FSTAGE];                    // saturated: a list that long is read back from its slot
+	__shared__ SeedQueryWindow st_win[MLR ? FSTAGE : 1];
 	__shared__ uint32_t sv_slot[SURV], sv_x[SURV];
 	__shared__ uint16_t sv_loc[SURV], hv_k[HEAVY];
 	__shared__ unsigned sv_n, hv_n;
@@ -553,7 +570,7 @@ __global__ __launch_bounds__(256) void seed_stream_fast_kernel(SeedArgs a, int s
 	// from the 3 MB block, which is what this kernel is short of (L2 capacity and fabric reads); the reference side from its
 	// folded copy too, half the lines of the letters for the eight class workgroups that read around every tile's joins. The
 	// ~2 % of the pairs that pass are counted exactly on the letters.
-	auto filter_list = [&](uint32_t slot, uint32_t head, uint32_t count, int64_t pos, uint32_t first, uint32_t step) {
+	auto filter_list = [&](uint32_t slot, uint32_t head, uint32_t count, int64_t pos, uint32_t first, uint32_t step, SeedQueryWindow win) {
 		uint32_t tw[12], tf[6];
 		{
 			const int64_t t0 = pos - 16;
@@ -567,6 +584,7 @@ __global__ __launch_bounds__(256) void seed_stream_fast_kernel(SeedArgs a, int s
 		}
 		for (uint32_t i = first; i < count; i += step) {
 			const uint32_t x = count == 1 ? head : a.qlist[head + i];
+			if (MLR && (x < win.first || x >= win.end)) continue;
 			const int64_t x0 = a.q_begin + (int64_t)x - 16;
 			uint32_t raw[8];
 			__builtin_memcpy(raw, a.qfold + (x0 >> 1), 32);
@@ -600,14 +618,17 @@ __global__ __launch_bounds__(256) void seed_stream_fast_kernel(SeedArgs a, int s
 		if (!(fl & SLOT_JOINED)) a.slot(slot).flags = fl | SLOT_JOINED;
 		if (FUSED && (fl & SLOT_LOWC)) return;
 		const unsigned k = atomicAdd(&st_n, 1u);                 // LDS atomic
+		SeedQueryWindow win{ 0, 0 };
+		if (MLR) win = seed_window_at(a, pos);
 		if (k < STAGE) {
 			st_slot[k] = (uint32_t)slot; st_loc[k] = (uint16_t)(pos - wg_base);
 			if (FUSED) { st_head[k] = head; st_count[k] = (uint16_t)((fl >> 8) < 0xffffu ? (fl >> 8) : 0xffffu); }
+			if (MLR) st_win[k] = win;
 		}
 		else {                                                    // staging area full (dense matches): direct append
 			const unsigned long long idx = atomicAdd(a.matched_count, 1ull);
 			if (idx < (unsigned long long)a.matched_cap) { a.matched_slot[idx] = (uint32_t)slot; a.matched_loc[idx] = pos; }
-			if (FUSED) filter_list((uint32_t)slot, head, fl >> 8, pos, 0, 1);
+			if (FUSED) filter_list((uint32_t)slot, head, fl >> 8, pos, 0, 1, win);
 		}
 	};
 	auto probe_table = [&](uint64_t seed, int64_t pos) {
@@ -798,14 +819,14 @@ __global__ __launch_bounds__(256) void seed_stream_fast_kernel(SeedArgs a, int s
 				const unsigned hk = atomicAdd(&hv_n, 1u);
 				if (hk < HEAVY) { hv_k[hk] = (uint16_t)k; continue; }
 				if (count == 0xffffu) count = a.slot(st_slot[k]).flags >> 8;
-				filter_list(st_slot[k], st_head[k], count, wg_base + st_loc[k], 0, 1);
+				filter_list(st_slot[k], st_head[k], count, wg_base + st_loc[k], 0, 1, (MLR ? st_win[k] : SeedQueryWindow{ 0, 0 }));
 				continue;
 			}
 			const unsigned at = atomicAdd(&pr_n, count);
 			if (at + count <= PAIRS) for (uint32_t i = 0; i < count; ++i) pr[at + i] = (uint16_t)((k << 3) | i);
 			else {                                                    // no room: on the spot (the slots of the reservation that exist are voided)
 				for (unsigned i = at; i < PAIRS; ++i) pr[i] = 0xffffu;
-				filter_list(st_slot[k], st_head[k], count, wg_base + st_loc[k], 0, 1);
+				filter_list(st_slot[k], st_head[k], count, wg_base + st_loc[k], 0, 1, (MLR ? st_win[k] : SeedQueryWindow{ 0, 0 }));
 			}
 		}
 		__syncthreads();
@@ -813,7 +834,7 @@ __global__ __launch_bounds__(256) void seed_stream_fast_kernel(SeedArgs a, int s
 		for (unsigned e = threadIdx.x; e < n_pairs; e += 256) {       // (two pairs per thread in flight, their loads issued together: 108 -> 124 ms
 			if (pr[e] == 0xffffu) continue;                            //  per 16 shapes -- the registers cost more wavefronts than the overlap returns)
 			const unsigned k = pr[e] >> 3;
-			filter_list(st_slot[k], st_head[k], st_count[k], wg_base + st_loc[k], pr[e] & 7u, 0x40000000u);
+			filter_list(st_slot[k], st_head[k], st_count[k], wg_base + st_loc[k], pr[e] & 7u, 0x40000000u, (MLR ? st_win[k] : SeedQueryWindow{ 0, 0 }));
 		}
 		__syncthreads();
 		PHASE_MARK(4);
@@ -822,7 +843,7 @@ __global__ __launch_bounds__(256) void seed_stream_fast_kernel(SeedArgs a, int s
 			const unsigned k = hv_k[h];
 			uint32_t count = st_count[k];
 			if (count == 0xffffu) count = a.slot(st_slot[k]).flags >> 8;
-			filter_list(st_slot[k], st_head[k], count, wg_base + st_loc[k], threadIdx.x, 256);
+			filter_list(st_slot[k], st_head[k], count, wg_base + st_loc[k], threadIdx.x, 256, (MLR ? st_win[k] : SeedQueryWindow{ 0, 0 }));
 		}
 		__syncthreads();
 		PHASE_MARK(5);
@@ -1141,6 +1162,7 @@ __device__ __forceinline__ void post_hamming(const SeedArgs& a, int sid, uint32_
 
 __device__ __forceinline__ void filter_pair(const SeedArgs& a, int sid, uint32_t slot, uint32_t slot_flags, int chunk, int64_t sloc, uint32_t x)
 {
+	if (a.qwin && !seed_window_holds(seed_window_at(a, sloc), x)) return;
 	if (fingerprint_id(a.qdata + a.q_begin + x, a.tdata + sloc) < a.params.hamming_filter_id) return;
 	post_hamming(a, sid, slot, slot_flags, chunk, sloc, x);
 }
@@ -1153,7 +1175,8 @@ __device__ __forceinline__ void filter_pair(const SeedArgs& a, int sid, uint32_t
 // place left most lanes of a wavefront waiting for the few that passed.
 // CHAIN (seed_chain.h): the shape's range of the shared lists comes from the counter block; a bounded grid walks it in tiles of
 // one workgroup (a workgroup-uniform trip count: the staging area is flushed per tile)
-template<bool CHAIN>
+// MLR (mutual-coverage search): the joined position's window of admissible query positions is looked up with its slot, once
+template<bool CHAIN, bool MLR>
 __global__ __launch_bounds__(128) void seed_pair_kernel(SeedArgs a, int sid, int64_t n_matched, SeedChain ch)
 {
 	constexpr uint32_t LIGHT = 8;
@@ -1167,7 +1190,8 @@ __global__ __launch_bounds__(128) void seed_pair_kernel(SeedArgs a, int sid, int
 		first = sid ? (int64_t)ch.ctr[sid - 1] : 0;
 		end = (int64_t)ch.ctr[sid];
 	}
-	auto filter = [&](uint32_t slot, int64_t sloc, uint32_t x) {
+	auto filter = [&](uint32_t slot, int64_t sloc, uint32_t x, SeedQueryWindow win) {
+		if (MLR && !seed_window_holds(win, x)) return;
 		if (fingerprint_id(a.qdata + a.q_begin + x, a.tdata + sloc) < a.params.hamming_filter_id) return;
 		const unsigned k = atomicAdd(&st_n, 1u);
 		if (k < STAGE) stage[k] = SeedSurvivor{ slot, x, sloc };
@@ -1183,23 +1207,27 @@ __global__ __launch_bounds__(128) void seed_pair_kernel(SeedArgs a, int sid, int
 		const int64_t m = tile + threadIdx.x;
 		uint32_t slot = 0, head = 0, count = 0;
 		int64_t sloc = 0;
+		SeedQueryWindow win{ 0, 0 };
 		if (m < end) {
 			slot = a.matched_slot[m];
 			const SeedSlot sl = a.slot(slot);                // key, list start, size and state of the seed in one 16-byte read
 			if (!(sl.flags & SLOT_ERASED)) {
 				head = sl.head; count = sl.flags >> 8;
 				sloc = a.matched_loc[m];
+				if (MLR) win = seed_window_at(a, sloc);
 			}
 		}
 		if (count <= LIGHT)
-			for (uint32_t i = 0; i < count; ++i) filter(slot, sloc, count == 1 ? head : a.qlist[head + i]);
+			for (uint32_t i = 0; i < count; ++i) filter(slot, sloc, count == 1 ? head : a.qlist[head + i], win);
 		unsigned long long heavy = __ballot(count > LIGHT);
 		while (heavy) {
 			const int src = __builtin_ctzll(heavy);
 			heavy &= heavy - 1;
 			const uint32_t h_slot = (uint32_t)__shfl((int)slot, src), h_head = (uint32_t)__shfl((int)head, src), h_count = (uint32_t)__shfl((int)count, src);
 			const int64_t h_sloc = (int64_t)__shfl((long long)sloc, src);
-			for (uint32_t i = (uint32_t)lane; i < h_count; i += 64) filter(h_slot, h_sloc, a.qlist[h_head + i]);
+			SeedQueryWindow h_win{ 0, 0 };
+			if (MLR) { h_win.first = (uint32_t)__shfl((int)win.first, src); h_win.end = (uint32_t)__shfl((int)win.end, src); }
+			for (uint32_t i = (uint32_t)lane; i < h_count; i += 64) filter(h_slot, h_sloc, a.qlist[h_head + i], h_win);
 		}
 		__syncthreads();
 		const unsigned n = st_n < STAGE ? st_n : STAGE;
@@ -1225,6 +1253,8 @@ __global__ __launch_bounds__(128) void seed_pair_kernel(SeedArgs a, int sid, int
 // Pairs that pass the Hamming filter are NOT scored in place: in a wavefront only the ~10 % passing lanes would run the long
 // stage-2 code while the others wait (measured: 3/4 of the kernel's time). They are staged in LDS, flushed to a compact
 // survivor list with one global atomic per flush, and scored by seed_post_kernel with all lanes busy.
+// MLR (mutual-coverage search): every thread holds its reference position's window of admissible query positions
+template<bool MLR>
 __global__ __launch_bounds__(256) void seed_pair_tiled_kernel(SeedArgs a, int sid, int64_t n_matched)
 {
 	constexpr uint32_t LIGHT = 8;
@@ -1241,6 +1271,7 @@ __global__ __launch_bounds__(256) void seed_pair_tiled_kernel(SeedArgs a, int si
 	const int64_t m = (int64_t)blockIdx.x * 256 + tid;
 	uint32_t slot = LIST_END, head = 0, count = 0;
 	int64_t sloc = 0;
+	SeedQueryWindow win{ 0, 0 };
 	uint32_t sw[12];
 #pragma unroll
 	for (int w = 0; w < 12; ++w) sw[w] = 0;
@@ -1251,6 +1282,7 @@ __global__ __launch_bounds__(256) void seed_pair_tiled_kernel(SeedArgs a, int si
 			head = sl.head; count = sl.flags >> 8;
 			sloc = a.matched_loc[m];
 			__builtin_memcpy(sw, a.tdata + sloc - 16, 48);
+			if (MLR) win = seed_window_at(a, sloc);
 		}
 	}
 	auto survive = [&](uint32_t x) {
@@ -1285,6 +1317,7 @@ __global__ __launch_bounds__(256) void seed_pair_tiled_kernel(SeedArgs a, int si
 	if (count > 0 && count <= LIGHT)
 		for (uint32_t i = 0; i < count; ++i) {
 			const uint32_t x = count == 1 ? head : a.qlist[head + i];
+			if (MLR && !seed_window_holds(win, x)) continue;
 			uint32_t qw[12];
 			__builtin_memcpy(qw, a.qdata + a.q_begin + x - 16, 48);
 			if (window_identity(sw, qw) >= a.params.hamming_filter_id) survive(x);
@@ -1306,7 +1339,7 @@ __global__ __launch_bounds__(256) void seed_pair_tiled_kernel(SeedArgs a, int si
 			__syncthreads();
 			if (heavy && slot == r_slot)
 				for (int w = 0; w < nt; ++w)
-					if (window_identity(sw, q_tile + 12 * w) >= a.params.hamming_filter_id) survive(q_x[w]);
+					if ((!MLR || seed_window_holds(win, q_x[w])) && window_identity(sw, q_tile + 12 * w) >= a.params.hamming_filter_id) survive(q_x[w]);
 			flush();
 		}
 	}
@@ -1646,6 +1679,10 @@ __global__ __launch_bounds__(256) void seed_collect_folded_kernel(SeedArgs a, in
 // One wavefront per deferred pair: the lanes share the scan over the tile of the seed's joined positions (up to tile_size
 // Hamming comparisons at random places of the reference -- as one thread's loop that was a 0.7 ms tail per shape for 10^4 pairs).
 // Same arithmetic as simd_batch_size_sorted (seed_core.h), which the CPU emulation of this kernel uses.
+// MLR (mutual-coverage search): the reference forms its batches behind the length test, so a joined position of the tile whose target
+// fails it against this query is no batch mate (the tiles are still cut over all joined positions of the seed). Deferred pairs are
+// few: the target of every mate is searched for here.
+template<bool MLR>
 __global__ __launch_bounds__(256) void seed_deferred_kernel(SeedArgs a, int sid, int64_t n_deferred)
 {
 	const int lane = threadIdx.x & 63;
@@ -1680,6 +1717,7 @@ __global__ __launch_bounds__(256) void seed_deferred_kernel(SeedArgs a, int sid,
 	if (T > 0 && n > T) { t_lo = rank / T * T; t_hi = t_lo + T < n ? t_lo + T : n; }
 	int L = 0, rr = 0;
 	for (int64_t k = t_lo + lane; k < t_hi; k += 64) {
+		if (MLR && !seed_window_holds(seed_window_at(a, (int64_t)(locs[k] & LOC)), r.x)) continue;
 		if (fingerprint_id(q, a.tdata + (int64_t)(locs[k] & LOC)) < a.params.hamming_filter_id) continue;
 		++L; rr += k < rank;
 	}
@@ -1713,6 +1751,26 @@ hipError_t launch_seed_qid(const int64_t* limits, int64_t n_seqs, uint32_t* qid_
 {
 	if (n_seqs == 0) return hipSuccess;
 	hipLaunchKernelGGL(seed_qid_kernel, dim3(blocks_for(n_seqs * 64, 256)), dim3(256), 0, st, limits, n_seqs, qid_of);
+	return hipGetLastError();
+}
+
+// Mutual-coverage search: one lane per target. Both blocks are length-sorted, so the queries whose length passes against the
+// target's are a range of query ids (length_window_of: two binary searches over length_ratio_passes itself) and their letters a
+// range of query positions.
+__global__ void seed_qwin_kernel(const int64_t* __restrict__ qlimits, int64_t n_queries, const int64_t* __restrict__ tlimits, int64_t n_targets, double mlr, SeedQueryWindow* __restrict__ qwin)
+{
+	const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (t >= n_targets) return;
+	int64_t first, end;
+	length_window_of(LengthsOfLimits{ qlimits }, n_queries, tlimits[t + 1] - tlimits[t] - 1, mlr, &first, &end);
+	const int64_t q_begin = qlimits[0];
+	qwin[t] = first < end ? SeedQueryWindow{ (uint32_t)(qlimits[first] - q_begin), (uint32_t)(qlimits[end] - q_begin) } : SeedQueryWindow{ 0, 0 };
+}
+
+hipError_t launch_seed_qwin(const int64_t* qlimits, int64_t n_queries, const int64_t* tlimits, int64_t n_targets, double min_length_ratio, SeedQueryWindow* qwin, hipStream_t st)
+{
+	if (n_targets == 0) return hipSuccess;
+	hipLaunchKernelGGL(seed_qwin_kernel, dim3(blocks_for(n_targets, 256)), dim3(256), 0, st, qlimits, n_queries, tlimits, n_targets, min_length_ratio, qwin);
 	return hipGetLastError();
 }
 
@@ -1926,6 +1984,11 @@ bool seed_stream_can_fuse(const SeedParams& c)
 template<bool LEVEL2, bool FUSED, bool BYCLASS>
 static void launch_stream_fast(const SeedArgs& a, int sid, dim3 grid, hipStream_t st, uint64_t lo, uint64_t hi, int64_t base, uint64_t care64)
 {
+	if (FUSED && a.qwin) {                               // mutual-coverage search: the instances with the length test
+		if (a.params.seed_encoding == SEED_HASHED) hipLaunchKernelGGL((seed_stream_fast_kernel<LEVEL2, true, FUSED, BYCLASS, FUSED>), grid, dim3(256), 0, st, a, sid, lo, hi, base, care64);
+		else hipLaunchKernelGGL((seed_stream_fast_kernel<LEVEL2, false, FUSED, BYCLASS, FUSED>), grid, dim3(256), 0, st, a, sid, lo, hi, base, care64);
+		return;
+	}
 	if (a.params.seed_encoding == SEED_HASHED) hipLaunchKernelGGL((seed_stream_fast_kernel<LEVEL2, true, FUSED, BYCLASS>), grid, dim3(256), 0, st, a, sid, lo, hi, base, care64);
 	else hipLaunchKernelGGL((seed_stream_fast_kernel<LEVEL2, false, FUSED, BYCLASS>), grid, dim3(256), 0, st, a, sid, lo, hi, base, care64);
 }
@@ -2080,14 +2143,16 @@ hipError_t launch_seed_mask(const SeedArgs& a, int sid, hipStream_t st, int64_t 
 hipError_t launch_seed_pairs(const SeedArgs& a, int sid, int64_t n_matched, hipStream_t st)
 {
 	if (n_matched == 0) return hipSuccess;
-	hipLaunchKernelGGL(seed_pair_kernel<false>, dim3(blocks_for(n_matched, 128)), dim3(128), 0, st, a, sid, n_matched, SeedChain{});
+	if (a.qwin) hipLaunchKernelGGL((seed_pair_kernel<false, true>), dim3(blocks_for(n_matched, 128)), dim3(128), 0, st, a, sid, n_matched, SeedChain{});
+	else hipLaunchKernelGGL((seed_pair_kernel<false, false>), dim3(blocks_for(n_matched, 128)), dim3(128), 0, st, a, sid, n_matched, SeedChain{});
 	return hipGetLastError();
 }
 
 hipError_t launch_seed_pairs_tiled(const SeedArgs& a, int sid, int64_t n_matched, hipStream_t st)
 {
 	if (n_matched == 0) return hipSuccess;
-	hipLaunchKernelGGL(seed_pair_tiled_kernel, dim3(blocks_for(n_matched, 256)), dim3(256), 0, st, a, sid, n_matched);
+	if (a.qwin) hipLaunchKernelGGL(seed_pair_tiled_kernel<true>, dim3(blocks_for(n_matched, 256)), dim3(256), 0, st, a, sid, n_matched);
+	else hipLaunchKernelGGL(seed_pair_tiled_kernel<false>, dim3(blocks_for(n_matched, 256)), dim3(256), 0, st, a, sid, n_matched);
 	return hipGetLastError();
 }
 
@@ -2338,7 +2403,8 @@ hipError_t launch_seed_chain_mask(const SeedArgs& a, const SeedChain& ch, int si
 
 hipError_t launch_seed_chain_shape(const SeedArgs& a, const SeedChain& ch, int sid, hipStream_t st)
 {
-	hipLaunchKernelGGL(seed_pair_kernel<true>, dim3(CHAIN_GRID), dim3(128), 0, st, a, sid, (int64_t)0, ch);
+	if (a.qwin) hipLaunchKernelGGL((seed_pair_kernel<true, true>), dim3(CHAIN_GRID), dim3(128), 0, st, a, sid, (int64_t)0, ch);
+	else hipLaunchKernelGGL((seed_pair_kernel<true, false>), dim3(CHAIN_GRID), dim3(128), 0, st, a, sid, (int64_t)0, ch);
 	hipLaunchKernelGGL(seed_score_kernel<true>, dim3(CHAIN_GRID / 2), dim3(POST_THREADS), 0, st, a, sid, (int64_t)0, ch);
 	// (a voided shape leaves the scored count zero: the left-most kernel reads it and leaves)
 	launch_leftmost(a, sid, dim3(CHAIN_GRID / 2), st);
@@ -2379,7 +2445,8 @@ hipError_t launch_seed_chain_sort(const SeedChain& ch, bool sorted, const dmnd_s
 hipError_t launch_seed_deferred(const SeedArgs& a, int sid, int64_t n_deferred, hipStream_t st)
 {
 	if (n_deferred == 0) return hipSuccess;
-	hipLaunchKernelGGL(seed_deferred_kernel, dim3(blocks_for(n_deferred * 64, 256)), dim3(256), 0, st, a, sid, n_deferred);
+	if (a.qwin) hipLaunchKernelGGL(seed_deferred_kernel<true>, dim3(blocks_for(n_deferred * 64, 256)), dim3(256), 0, st, a, sid, n_deferred);
+	else hipLaunchKernelGGL(seed_deferred_kernel<false>, dim3(blocks_for(n_deferred * 64, 256)), dim3(256), 0, st, a, sid, n_deferred);
 	return hipGetLastError();
 }
 

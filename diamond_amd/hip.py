@@ -86,7 +86,8 @@ EXPORTS = ["dmnd_abi_version", "dmnd_last_error", "dmnd_default_params", "dmnd_c
            "dmnd_seed_params_set_query_indexed", "dmnd_auto_query_indexed", "dmnd_set_motif_table", "dmnd_motif_table_size",
            "dmnd_soft_mask_block", "dmnd_download_block", "dmnd_seg_mask_block_device", "dmnd_seg_mask_sequences_device", "dmnd_seg_ranges_device", "dmnd_seg_device_stats", "dmnd_output_fields", "dmnd_format_fields", "dmnd_format_pairwise_intro", "dmnd_format_pairwise",
            "dmnd_format_paf", "dmnd_device_count", "dmnd_set_top_percent", "dmnd_join_blocks_top", "dmnd_set_filters", "dmnd_format_sam", "dmnd_set_query_source_lengths", "dmnd_format_fields_unaligned", "dmnd_format_fields_header", "dmnd_set_query_index_reuse", "dmnd_set_no_self_hits", "dmnd_matrix_params", "dmnd_masking_lambda", "dmnd_translate_opts", "dmnd_set_extension_mode", "dmnd_format_xml_header", "dmnd_format_xml_query_intro", "dmnd_format_xml", "dmnd_format_xml_query_epilog", "dmnd_format_daa_header", "dmnd_format_daa_query", "dmnd_format_daa_match", "dmnd_seg_ranges", "dmnd_seg_mask_block", "dmnd_seg_lnfact", "dmnd_daa_match_read", "dmnd_hsp_from_transcript", "dmnd_hsp_from_transcript_frames", "dmnd_set_format_flags", "dmnd_host_alloc", "dmnd_host_free", "dmnd_share_block", "dmnd_copy_block", "dmnd_init", "dmnd_seed_reserve", "dmnd_mask_sequences", "dmnd_set_max_hsps", "dmnd_rank_targets", "dmnd_rank_update", "dmnd_set_global_ranking", "dmnd_rank_targets_device", "dmnd_rank_device_stats", "dmnd_seed_hit_count", "dmnd_set_seed_hits_resident",
-           "dmnd_upload_matrices", "dmnd_frameshift_swipe", "dmnd_set_frameshift", "dmnd_set_context_motif_table", "dmnd_cbs_composition", "dmnd_cbs_rule", "dmnd_cbs_target_matrix", "dmnd_cbs_ideal_lambda", "dmnd_cbs_target_matrices_device", "dmnd_cbs_device_stats", "dmnd_join_blocks_range", "dmnd_join_blocks_device", "dmnd_join_blocks_device_host", "dmnd_join_ranks", "dmnd_join_ranks_plan", "dmnd_xdrop_ungapped"]
+           "dmnd_upload_matrices", "dmnd_frameshift_swipe", "dmnd_set_frameshift", "dmnd_set_context_motif_table", "dmnd_cbs_composition", "dmnd_cbs_rule", "dmnd_cbs_target_matrix", "dmnd_cbs_ideal_lambda", "dmnd_cbs_target_matrices_device", "dmnd_cbs_device_stats", "dmnd_join_blocks_range", "dmnd_join_blocks_device", "dmnd_join_blocks_device_host", "dmnd_join_ranks", "dmnd_join_ranks_plan", "dmnd_xdrop_ungapped",
+           "dmnd_set_min_length_ratio", "dmnd_length_sort_order", "dmnd_seed_query_windows"]
 
 
 def set_motif_table(codes):
@@ -409,6 +410,18 @@ def auto_query_indexed(p, qdata, qlimits, db_bytes):
     if lib.dmnd_auto_query_indexed(ctypes.byref(p), qd.ctypes.data, ql.ctypes.data, len(ql) - 1, int(db_bytes), ctypes.byref(out)) != 0:
         raise DiamondHipError(lib.dmnd_last_error().decode())
     return bool(out.value)
+
+
+def length_sort_order(limits):
+    """The reference's length sort of a block (dmnd_length_sort_order; Block::length_sorted): order[k] = index of the k-th
+    sequence of the sorted block, (length, index) descending. What a search with Context.set_min_length_ratio wants of both blocks."""
+    lib = load()
+    lim = np.ascontiguousarray(limits, dtype=np.int64)
+    order = np.zeros(max(len(lim) - 1, 0), np.int64)
+    lib.dmnd_length_sort_order.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
+    if lib.dmnd_length_sort_order(lim.ctypes.data, len(order), order.ctypes.data) != 0:
+        raise DiamondHipError(lib.dmnd_last_error().decode())
+    return order
 
 
 def join_blocks(records, max_target_seqs=25, copy=True):
@@ -938,6 +951,20 @@ class Context:
         """Keep the query seed index between seed_search calls on the same query block (one query block, many reference blocks)."""
         self.lib.dmnd_set_query_index_reuse.argtypes = [ctypes.c_void_p, ctypes.c_int]
         self._check(self.lib.dmnd_set_query_index_reuse(self.h, 1 if on else 0))
+
+    def set_min_length_ratio(self, ratio):
+        """--min-len-ratio (dmnd_set_min_length_ratio): seed_search compares a (query, target) pair only if the shorter length is
+        at least `ratio` times the longer one; both blocks must then be length-sorted (length_sort_order). 0 = off."""
+        self.lib.dmnd_set_min_length_ratio.argtypes = [ctypes.c_void_p, ctypes.c_double]
+        self._check(self.lib.dmnd_set_min_length_ratio(self.h, float(ratio)))
+
+    def seed_query_windows(self, n_targets):
+        """The per-target windows of admissible query positions that the last seed_search with a ratio built on the device:
+        uint32[n_targets, 2] = (first, end), counted from the query block's first limit; (0, 0) = no query passes."""
+        out = np.zeros((int(n_targets), 2), np.uint32)
+        self.lib.dmnd_seed_query_windows.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]
+        self._check(self.lib.dmnd_seed_query_windows(self.h, out.ctypes.data, int(n_targets)))
+        return out
 
     def set_top_percent(self, percent):
         """--top PERCENT (None or a negative value: off): targets within PERCENT of the best bit score instead of the first -k."""

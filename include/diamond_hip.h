@@ -292,6 +292,23 @@ int dmnd_seed_reserve(dmnd_ctx* ctx, const dmnd_seed_params* params, int64_t que
  * marks instead of indexing the queries again (the reference rebuilds its query seed arrays for every block pair). Off by default;
  * results are identical either way. */
 int dmnd_set_query_index_reuse(dmnd_ctx* ctx, int on);
+/* Mutual-coverage search (--min-len-ratio; what equal --query-cover / --subject-cover of 50 and more select,
+ * run/config.cpp:156-165): with a ratio > 0 the seed stage compares a (query, target) pair only if both
+ * (double)qlen / tlen >= ratio and (double)tlen / qlen >= ratio (search/hamming/kernel_mutual_cov.h); the SIMD batches of the
+ * stage-2 score are formed behind that test. 0 = off (the default); a value outside [0, 1] -> DMND_E_ARG.
+ * The reference replaces both blocks by their length-sorted copies then (Block::length_sorted), and so must the caller:
+ * dmnd_seed_search with a ratio > 0 wants one query context and both blocks in non-increasing length order and returns
+ * DMND_E_ARG otherwise, before anything is launched. The per-target windows are rebuilt by every search, so
+ * dmnd_set_query_index_reuse keeps working. Nothing behind the seed stage reads the ratio. */
+int dmnd_set_min_length_ratio(dmnd_ctx* ctx, double ratio);
+/* Host only: order[k] = index of the k-th sequence of the length-sorted block -- (length, index in the block as loaded)
+ * descending, the reference's order (data/block/block.cpp:229-255; ties come out in DEscending index order, not stably).
+ * limits: n + 1 block offsets as for dmnd_upload_block. */
+int dmnd_length_sort_order(const int64_t* limits, int64_t n, int64_t* order);
+/* For tests and diagnosis: the windows the last dmnd_seed_search with a ratio > 0 built on the device, per target of the reference
+ * block { first, end } = the query positions (counted from the query block's first limit) of the queries that pass against it;
+ * { 0, 0 }: none. out: 2 * n_targets words. DMND_E_ARG if the last search ran without a ratio. */
+int dmnd_seed_query_windows(dmnd_ctx* ctx, uint32_t* out, int64_t n_targets);
 /* Copies the hits of the last dmnd_seed_search to the caller, sorted by (query, subject, seed_offset)
  * (the reference sorts by query before extension, align/align.cpp:233). cap < n -> DMND_E_CAP. */
 int dmnd_seed_hits(dmnd_ctx* ctx, dmnd_seed_hit* out, int64_t cap);

@@ -162,8 +162,9 @@ __device__ __forceinline__ void scan_diags_profile(const int8_t* prof, int W, co
 }
 
 // One workgroup per unit = up to 64 consecutive hits of ONE query (units[u] = first hit, end). PROFILE: the query's profile is built
-// in LDS (32 rows of W = query length + 2 * GF_PAD bytes) and the scans read it; else the matrix path (queries longer than the LDS
-// budget). Same per-hit logic as gapped_filter_kernel.
+// in LDS (32 rows of W bytes, W = the width of the unit's class >= query length + 2 * GF_PAD; cell x of a row is query position
+// x - GF_PAD, and the scans read positions -127 .. query length + 126, all inside the row) and the scans read it; else the matrix
+// path (queries longer than the LDS budget). Same per-hit logic as gapped_filter_kernel.
 template<bool PROFILE>
 __global__ __launch_bounds__(256) void gapped_filter_unit_kernel(const GfArgs a, const int2* __restrict__ units, int n_units, int W)
 {

@@ -77,7 +77,8 @@ def test_query_length_classes_and_hit_order_against_oracle(ctx, monkeypatch):
     """The kernel builds a query's score profile in LDS for a unit of consecutive hits of that query, in one of three LDS sizes
     by query length (<= 512, <= 1024, <= 1792 letters), and keeps the matrix path for longer queries: queries on both sides of
     every boundary, hits in query order and shuffled (units of one hit), mask letters in both sequences, hits near the sequence
-    ends. Both filter values of every hit equal the oracle's; DMND_GF_PROFILE=0 (one wavefront per hit, matrix path) gives the same."""
+    ends. Both filter values and the flag of every hit equal the oracle's (cutoffs: the oracle's CutoffTable2D), on the profile path
+    and, with DMND_GF_PROFILE_TEST=0 (one wavefront per hit, matrix path), on the matrix path."""
     from diamond_amd import workload
     rng = np.random.default_rng(3)
     m8 = blosum62_matrix8()
@@ -117,24 +118,28 @@ def test_query_length_classes_and_hit_order_against_oracle(ctx, monkeypatch):
     ctx.upload_cbs(cbs)
     ctx.set_gapped_filter(1.0)
     flags, scores = ctx.gapped_filter(hits, use_cbs=True, with_scores=True)
-    n2 = 0
-    for x in range(0, len(hits), 3):
+    cut1, cut2 = orc.cutoff_table2d(2000.0), orc.cutoff_table2d(1.0)          # gapped_filter_evalue1, and set_gapped_filter(1.0)
+    want_flags, want = np.zeros(len(hits), np.uint8), np.full((len(hits), 2), -1, np.int32)
+    for x in range(len(hits)):                                    # every hit: both values and the flag, from the oracle alone
         qi = int(hits["query"][x])
         ti = int(np.searchsorted(tl, hits["subject"][x], side="right") - 1)
         q, t = qs[qi], ts[ti]
         c = cbs[ql[qi]:ql[qi] + len(q)]
         hi, hj = int(hits["seed_offset"][x]), int(hits["subject"][x] - tl[ti])
-        assert scores[x, 0] == orc.gapped_filter_hit(m8, q, c, t, hi, hj, 64, 100, 20), (qi, ti, hi, hj)
-        if scores[x, 1] >= 0:
-            assert scores[x, 1] == orc.gapped_filter_hit(m8, q, c, t, hi, hj, 128, 200, 20), (qi, ti, hi, hj)
-            n2 += 1
-    assert len(hits) > 300 and n2 > 30
+        b1, b2 = len(q).bit_length(), len(t).bit_length()
+        want[x, 0] = orc.gapped_filter_hit(m8, q, c, t, hi, hj, 64, 100, 20)
+        if want[x, 0] > cut1[b1, b2]:
+            want[x, 1] = orc.gapped_filter_hit(m8, q, c, t, hi, hj, 128, 200, 20)
+            want_flags[x] = want[x, 1] > cut2[b1, b2]
+        assert tuple(scores[x]) == tuple(want[x]) and flags[x] == want_flags[x], (qi, ti, hi, hj)
+    n2 = int((want[:, 1] >= 0).sum())
+    assert len(hits) > 300 and n2 > 30 and 0 < int(want_flags.sum()) < len(hits)
     perm = rng.permutation(len(hits))
     f2, s2 = ctx.gapped_filter(hits[perm], use_cbs=True, with_scores=True)
-    assert np.array_equal(f2, flags[perm]) and np.array_equal(s2, scores[perm])
+    assert np.array_equal(f2, want_flags[perm]) and np.array_equal(s2, want[perm])
     monkeypatch.setenv("DMND_GF_PROFILE_TEST", "0")               # read per call (the product's DMND_GF_PROFILE is read once)
     f3, s3 = ctx.gapped_filter(hits, use_cbs=True, with_scores=True)
-    assert np.array_equal(f3, flags) and np.array_equal(s3, scores)
+    assert np.array_equal(f3, want_flags) and np.array_equal(s3, want)        # the matrix path against the oracle, not against the profile path
 
 
 def test_filter_off_and_argument_errors(ctx):

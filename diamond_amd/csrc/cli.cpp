@@ -488,6 +488,7 @@ struct Options {
 	double min_id = 0, query_cover = 0, subject_cover = 0, min_score = 0;      // --id, --query-cover, --subject-cover, --min-score
 	double min_len_ratio = 0;       // --min-len-ratio: the mutual-coverage search's length-ratio cutoff in the seed stage (0 = not given)
 	double approx_id = 0; bool approx_id_given = false;      // --approx-id (config.approx_min_id)
+	bool linsearch = false;         // --linsearch: only consider seed hits against the longest target for identical seeds (basic/config.cpp:425)
 };
 
 Options parse(int argc, char** argv)
@@ -527,6 +528,7 @@ Options parse(int argc, char** argv)
 		else if (a == "--query-cover") o.query_cover = std::atof(need(i).c_str());
 		else if (a == "--subject-cover") o.subject_cover = std::atof(need(i).c_str());
 		else if (a == "--min-len-ratio") o.min_len_ratio = std::atof(need(i).c_str());
+		else if (a == "--linsearch") o.linsearch = true;
 		else if (a == "--min-score") o.min_score = std::atof(need(i).c_str());
 		else if (a == "--no-self-hits") o.no_self_hits = true;
 		else if (a == "--matrix") o.matrix = need(i);
@@ -756,6 +758,19 @@ int run_blastp(const Options& o)
 	if (mlr < 0.0 || mlr > 1.0) throw std::runtime_error("Invalid value for --min-len-ratio: a ratio lies in [0, 1].");
 	if (mlr > 0.0 && o.global_ranking > 0) throw std::runtime_error("--global-ranking together with a minimum length ratio (--min-len-ratio, or equal --query-cover and --subject-cover of 50 and more) is not part of this build.");
 	if (mlr > 0.0 && o.gpus > 1) throw std::runtime_error("--gpus above 1 together with a minimum length ratio (--min-len-ratio, or equal --query-cover and --subject-cover of 50 and more) is not part of this build.");
+	// The linearised search (--linsearch, cfg.lin_stage1_target; linsearch_core.h): every reference block is replaced by its length-sorted
+	// copy right after it is read (run/double_indexed.cpp:112-115; the query blocks stay as they are, :727) and the seed stage joins a
+	// seed's query positions to its first position in the block, i.e. to its longest target (dmnd_set_linsearch). The reference side
+	// reuses what the mutual-coverage search built: block ids back to database ordinals, the stand-in ordinals of the join over
+	// several reference blocks, --no-self-hits.
+	if (o.linsearch) {
+		if (o.command != "blastp") throw std::runtime_error("--linsearch is only part of this build for blastp.");
+		if (!o.sens.empty()) throw std::runtime_error("Linearization is only supported for seed shapes of weight >= 10.");      // search/setup.cpp:365-366: --fast and the default sensitivity remain
+		if (mlr > 0.0) throw std::runtime_error("--linsearch together with a minimum length ratio (--min-len-ratio, or equal --query-cover and --subject-cover of 50 and more) is not part of this build.");
+		if (o.global_ranking > 0) throw std::runtime_error("--linsearch together with --global-ranking is not part of this build.");
+		if (o.gpus > 1) throw std::runtime_error("--linsearch together with --gpus above 1 is not part of this build.");
+	}
+	const bool ref_sorted = mlr > 0.0 || o.linsearch;   // reference blocks are length-sorted: their ids are not database order
 	// basic/config.cpp:688, :822-825: frameshift alignment is for translated queries, range culling for frameshift alignment
 	if (o.global_ranking > 0 && (o.range_culling || o.frameshift > 0)) throw std::runtime_error("Global ranking is not supported in this mode.");
 	if (o.frameshift != 0 && o.command == "blastp") throw std::runtime_error("Frameshift alignments are only supported for translated searches.");
@@ -903,7 +918,11 @@ int run_blastp(const Options& o)
 	// (which query block a query falls into shows in the output of the mutual-coverage search alone, whose order is that of the
 	// length-sorted blocks: there the cut of a FASTA query file is the reference's, by bytes)
 	const bool q_by_bytes = mlr > 0.0 && q_all.rec_begin.size() == n_queries + 1 && n_queries > 0;
-	const std::vector<Range> q_blocks = q_by_bytes ? split_blocks_bytes(q_all.rec_begin, max_letters) : split_blocks(q_units, max_letters), t_blocks = split_blocks(t_units, t_max_letters);
+	// (... and which reference block a target falls into shows in the linearised search alone, whose first positions are per block:
+	// there the cut of a FASTA database is the reference's, by bytes)
+	const bool t_by_bytes = o.linsearch && !db.dmnd && db.all.rec_begin.size() == n_targets + 1 && n_targets > 0;
+	const std::vector<Range> q_blocks = q_by_bytes ? split_blocks_bytes(q_all.rec_begin, max_letters) : split_blocks(q_units, max_letters),
+		t_blocks = t_by_bytes ? split_blocks_bytes(db.all.rec_begin, t_max_letters) : split_blocks(t_units, t_max_letters);
 	// mutual-coverage search: every query block is replaced by its length-sorted copy before it is masked (run/double_indexed.cpp:727-731),
 	// and the records, --un and --al follow that order. The block cut above is the file's; from here on q_all IS the sorted file, and
 	// q_oid keeps every query's place in the file for the one format that prints it (XML).
@@ -918,8 +937,8 @@ int run_blastp(const Options& o)
 		}
 	}
 	// ... and so is every reference block, right after it was read (run/double_indexed.cpp:112-115): ord = block id -> database ordinal
-	auto sort_reference_block = [mlr](SeqBlock& b, const Range& tr, std::vector<uint32_t>& ord) {
-		if (mlr <= 0.0) return;
+	auto sort_reference_block = [ref_sorted](SeqBlock& b, const Range& tr, std::vector<uint32_t>& ord) {
+		if (!ref_sorted) return;
 		std::vector<int64_t> order;
 		length_sort_range(b, 0, tr.end - tr.begin, &order);
 		ord.resize(order.size());
@@ -971,6 +990,7 @@ int run_blastp(const Options& o)
 		chk(dmnd_set_filters(c, o.min_id, o.query_cover, o.subject_cover, o.min_score));
 		chk(dmnd_set_approx_id(c, std::max(0.0, o.approx_id)));      // (the reference reads a value <= 0 as off)
 		chk(dmnd_set_min_length_ratio(c, mlr));
+		chk(dmnd_set_linsearch(c, o.linsearch ? 1 : 0));
 		chk(dmnd_set_comp_based_stats(c, o.cbs));
 		chk(dmnd_set_query_contexts(c, blastx ? 6 : 1));
 		if (o.global_ranking > 0 && !rank_host) chk(dmnd_set_seed_hits_resident(c, 1));      // the device form ranks the hits in HBM: the seed search brings none back
@@ -978,7 +998,8 @@ int run_blastp(const Options& o)
 		chk(dmnd_set_sensitivity(c, sens));
 		// global ranking extends its targets over the full matrix (search/setup.cpp:377-389)
 		if (o.global_ranking > 0 && o.ext != DMND_EXT_DEFAULT && o.ext != DMND_EXT_FULL) throw std::runtime_error("Global ranking only supports full matrix extension.");
-		chk(dmnd_set_extension_mode(c, o.global_ranking > 0 ? DMND_EXT_FULL : o.ext));
+		// (a linearised search without --ext extends in full-matrix mode, search/setup.cpp:377-379)
+		chk(dmnd_set_extension_mode(c, o.global_ranking > 0 || (o.linsearch && o.ext == DMND_EXT_DEFAULT) ? DMND_EXT_FULL : o.ext));
 		chk(dmnd_set_global_ranking(c, o.global_ranking));
 		chk(dmnd_set_gapped_filter(c, gf_evalue));
 		// several reference blocks per GPU: the query seed index of a query block is built once and kept for all of them
@@ -1294,7 +1315,7 @@ int run_blastp(const Options& o)
 			t0 = std::chrono::steady_clock::now();
 			if (o.no_self_hits) {
 				if (blastx) throw std::runtime_error("--no-self-hits is not supported for blastx");      // basic/config.cpp:677
-				self_ctx[(size_t)g] = SelfCtx{ &qtitles, &db, qr.begin, tr.begin, mlr > 0.0 ? &held.ord : nullptr };
+				self_ctx[(size_t)g] = SelfCtx{ &qtitles, &db, qr.begin, tr.begin, ref_sorted ? &held.ord : nullptr };
 				chk(dmnd_set_no_self_hits(ctx, [](void* u, uint32_t q, uint32_t t) -> int {
 					const SelfCtx& s = *static_cast<const SelfCtx*>(u);
 					return (*s.qtitles)[s.q0 + q] == s.db->title(s.ordinals ? (size_t)(*s.ordinals)[t] : s.t0 + t) ? 1 : 0;
@@ -1331,12 +1352,12 @@ int run_blastp(const Options& o)
 			std::lock_guard<std::mutex> lock(merge_mutex);
 			for (const dmnd_seed_hit& h : hits) seeded[h.query / C] = 1;
 			for (dmnd_match& m : mine) {
-				m.query += (uint32_t)qr.begin; m.target = mlr > 0.0 ? held.ord[m.target] : m.target + (uint32_t)tr.begin;
+				m.query += (uint32_t)qr.begin; m.target = ref_sorted ? held.ord[m.target] : m.target + (uint32_t)tr.begin;
 				if (need_transcripts) m.hsp.transcript_off += (int64_t)arena.size();
 			}
 			joined.insert(joined.end(), mine.begin(), mine.end());
 			joined_gpu.insert(joined_gpu.end(), mine.size(), (uint8_t)g);
-			if (mlr > 0.0) joined_block.insert(joined_block.end(), mine.size(), (uint32_t)bi);
+			if (ref_sorted) joined_block.insert(joined_block.end(), mine.size(), (uint32_t)bi);
 			arena.insert(arena.end(), my_arena.begin(), my_arena.end());
 			ms_upload += up; ms_mask += mk; ms_seed += sd; ms_ext += ex;
 			total_hits += n_hits;
@@ -1416,7 +1437,7 @@ int run_blastp(const Options& o)
 		// DMND_CLI_RCCL=1 takes that path with one GPU too (RCCL with itself), =0 keeps the host join.
 		static const int rccl_env = [] { const char* e = std::getenv("DMND_CLI_RCCL"); return e ? std::atoi(e) : -1; }();
 		const bool rank_join = t_blocks.size() > 1 && o.global_ranking == 0 && o.max_hsps == 1 && !o.range_culling && !joined.empty()
-			&& mlr <= 0.0 && (rccl_env >= 0 ? rccl_env != 0 : n_gpus > 1);
+			&& !ref_sorted && (rccl_env >= 0 ? rccl_env != 0 : n_gpus > 1);
 		bool rank_joined = false;
 		if (rank_join) {
 			std::vector<std::vector<dmnd_match>> per_gpu((size_t)n_gpus);
@@ -1450,7 +1471,7 @@ int run_blastp(const Options& o)
 		// target leaves its list when the largest ordinal of the tied targets of that list up to it is the smallest head. The targets
 		// get their places in that order as stand-in ordinals for the join and their database ordinals back behind it.
 		std::vector<uint32_t> place_oid;
-		if (mlr > 0.0 && t_blocks.size() > 1 && !joined.empty()) {
+		if (ref_sorted && t_blocks.size() > 1 && !joined.empty()) {
 			const bool by_score = o.top >= 0.0;                 // --top: the merge runs on JoinRecord::cmp_score
 			struct Grp { size_t first, n; uint32_t key; };
 			std::vector<Grp> grp;
@@ -1952,6 +1973,7 @@ int main(int argc, char** argv)
 				"masking      --masking tantan|seg|none  --motif-masking 0|1\n"
 				"extension    --ext banded-fast|banded-slow|full\n"
 				"reporting    -k N  --max-hsps N  --global-ranking N  --top PCT  -e EVALUE  --min-score BITS  --id PCT  --approx-id PCT  --query-cover PCT  --subject-cover PCT  --min-len-ratio R  --no-self-hits\n"
+				"             --linsearch (blastp, --fast or default mode: join each seed to its longest target only)\n"
 				"             --unal 0|1  --un FILE  --al FILE  --header [simple|verbose]  --compress 1  --salltitles  --sallseqid\n"
 				"formats      -f 6 [FIELD...] | 0 (pairwise) | 5 (XML) | 100 (DAA) | 101 (SAM) | 103 (PAF)\n"
 				"translated   --strand both|plus|minus  --query-gencode N  --min-orf N\n"

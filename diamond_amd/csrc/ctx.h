@@ -211,6 +211,9 @@ struct dmnd_ctx {
 	double min_length_ratio = 0.0;             // dmnd_set_min_length_ratio (mutual-coverage search); 0 = off
 	int64_t seed_qwin_n = 0;                   // ... targets the windows of the last search were built for; 0: it ran without a ratio
 	dmnd::DevBuf seed_qwin;                    // ... per target of the reference block its window of admissible query positions (rebuilt by every search)
+	bool linsearch = false;                    // dmnd_set_linsearch (linearised search, linsearch_core.h)
+	uint64_t lin_sorted_generation = ~(uint64_t)0;      // ... the target_generation whose block was found length-sorted (a walk over all its limits: once per block, not per search)
+	dmnd::DevBuf seed_lin_first;               // ... per slot of a shape's table the first joined reference position (rebuilt per shape by the reduction in front of its pair filter)
 	uint64_t query_generation = 0;             // bumped whenever the query block or its masks change
 	uint64_t target_generation = 0;            // bumped whenever the reference block's letters, limits, soft-mask view or alias change
 	// sliced long-seed stream (seed_slices_core.h, seed_ref_state.h): what a block generation's searches keep of the reference side -- the

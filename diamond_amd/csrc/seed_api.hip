@@ -257,6 +257,13 @@ extern "C" int dmnd_set_min_length_ratio(dmnd_ctx* c, double ratio)
 	return DMND_OK;
 }
 
+extern "C" int dmnd_set_linsearch(dmnd_ctx* c, int on)
+{
+	if (!c) return fail(DMND_E_ARG, "dmnd_set_linsearch: ctx is NULL");
+	c->linsearch = on != 0;
+	return DMND_OK;
+}
+
 extern "C" int dmnd_length_sort_order(const int64_t* limits, int64_t n, int64_t* order)
 {
 	if (n < 0 || (n > 0 && (!limits || !order))) return fail(DMND_E_ARG, "dmnd_length_sort_order: bad argument");
@@ -572,6 +579,17 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 		if (!lengths_non_increasing(ql.data(), (int64_t)ql.size() - 1)) return fail(DMND_E_ARG, "dmnd_seed_search: with a minimum length ratio the query block must be length-sorted (dmnd_length_sort_order)");
 		if (!lengths_non_increasing(tl.data(), (int64_t)tl.size() - 1)) return fail(DMND_E_ARG, "dmnd_seed_search: with a minimum length ratio the reference block must be length-sorted (dmnd_length_sort_order)");
 	}
+	// linearised search (linsearch_core.h): the first position of a seed lies in its longest target only over a length-sorted reference block
+	const bool lin_on = c->linsearch;
+	if (lin_on) {
+		for (int i = 0; i < sp.n_shapes; ++i)
+			if (!lin_shape_weight_ok(sp.shape_weight[i])) return fail(DMND_E_ARG, "dmnd_seed_search: Linearization is only supported for seed shapes of weight >= 10.");
+		if (mlr_on) return fail(DMND_E_ARG, "dmnd_seed_search: the linearised search together with a minimum length ratio is not supported (dmnd_set_linsearch, dmnd_set_min_length_ratio)");
+		if (c->lin_sorted_generation != c->target_generation) {
+			if (!lengths_non_increasing(tl.data(), (int64_t)tl.size() - 1)) return fail(DMND_E_ARG, "dmnd_seed_search: the linearised search wants the reference block length-sorted (dmnd_length_sort_order)");
+			c->lin_sorted_generation = c->target_generation;
+		}
+	}
 	HIP_TRY(hipSetDevice(c->device));
 	hipStream_t st = c->stream;
 	const int64_t q_begin = ql.front(), q_end = ql.back(), t_begin = tl.front(), t_end = tl.back();
@@ -611,6 +629,10 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 	c->qindex_signature.clear();                         // set again when this call has built (or kept) a complete index
 	lap("parameters checked");
 	if (int rc = seed_reserve(c, sp, z, nq_pos, q_end, c->block_len[DMND_QUERY], false)) return rc;
+	if (lin_on) {                                         // (never cleared: the reduction initialises the slots it reads, seed_lin_first_kernel)
+		if (fused) return fail(DMND_E_ARG, "dmnd_seed_search: the linearised search has no form in the fused short-seed pipeline");
+		if (int rc = c->seed_lin_first.ensure((size_t)slots * sizeof(int64_t))) return rc;
+	}
 	lap("buffers ensured");
 	static const bool phases = getenv("DMND_SEED_PHASES") != nullptr;
 	const bool counters_new = c->counters.cap < (size_t)chain_ctr_words(S) * sizeof(unsigned long long);
@@ -668,6 +690,7 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 		a.qid_of = c->qid_of.as<uint32_t>(); a.mask_time = c->mask_time.as<uint8_t>();
 		a.tlimits = c->d_limits[DMND_TARGET].as<int64_t>(); a.n_targets = (int64_t)tl.size() - 1;
 		a.qwin = mlr_on ? c->seed_qwin.as<SeedQueryWindow>() : nullptr;
+		a.lin_first = lin_on ? c->seed_lin_first.as<int64_t>() : nullptr;
 		a.slots = reinterpret_cast<SeedSlot*>(c->seed_keys.as<char>() + (size_t)own * slot_bytes);
 		a.slot_shift = z.slot_shift;
 		a.qlist = c->seed_qlist.as<uint32_t>() + (size_t)own * nq_pos;

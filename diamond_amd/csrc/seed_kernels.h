@@ -7,6 +7,7 @@
 #include "seed_chain.h"
 #include "seed_slices_core.h"
 #include "length_ratio_core.h"
+#include "linsearch_core.h"
 
 namespace dmnd {
 
@@ -49,7 +50,11 @@ struct SeedArgs {
 	// and then every launch takes the kernel instance that holds no length test at all
 	const int64_t* tlimits; int64_t n_targets;
 	const SeedQueryWindow* qwin;
-	uint8_t* mask_time;                           // per query letter: (shape, chunk) time of its SEED_MASK bit
+	// linearised search (linsearch_core.h): per slot of the shape's table the smallest joined reference position (launch_seed_lin_first, one
+	// array for all shapes: a shape's reduction re-initialises the slots of its own records); NULL: switch off, and then every launch takes
+	// the kernel instance that holds no selection test
+	int64_t* lin_first;
+	uint8_t* mask_time;                          // per query letter: (shape, chunk) time of its SEED_MASK bit
 	// per-shape query seed table
 	SeedSlot* slots;              // 16-byte slots: key, list start (or the seed's one query position), state | list size
 	int slot_shift;               // log2 of the slot stride in bytes (4). Tried and dropped in round 3: 64-byte slots carrying the folded
@@ -151,6 +156,10 @@ hipError_t launch_seed_ref_hashes(const SeedParams& c, int sid, const uint64_t* 
 hipError_t launch_seed_stream_slices(const SeedArgs& a, int sid, const uint64_t* codes, const uint32_t* list, const uint32_t* hashes, const uint32_t* counts, int slice_bits, hipStream_t st);
 // n_matched >= 0: the number of joined positions in a.matched_* (few of them: the kernel walks that list instead of the table)
 hipError_t launch_seed_mask(const SeedArgs& a, int sid, hipStream_t st, int64_t n_matched = -1);
+// Linearised search: a.lin_first[slot] = the smallest of the n_matched positions in a.matched_* that carry `slot`, in two launches
+// (initialise the slots that occur, then a 64-bit minimum per record) -- whatever the order of the records. launch_seed_pairs,
+// launch_seed_pairs_tiled and launch_seed_chain_shape run it in front of their filter when a.lin_first is set.
+hipError_t launch_seed_lin_first(const SeedArgs& a, int64_t n_matched, hipStream_t st);
 hipError_t launch_seed_pairs(const SeedArgs& a, int sid, int64_t n_matched, hipStream_t st);
 hipError_t launch_seed_pairs_tiled(const SeedArgs& a, int sid, int64_t n_matched, hipStream_t st);      // a.matched_* sorted by slot; fills a.survivors
 hipError_t launch_seed_count_pairs(const SeedArgs& a, int64_t n_matched, unsigned long long* out, hipStream_t st);

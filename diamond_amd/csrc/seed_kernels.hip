@@ -1088,7 +1088,7 @@ __global__ void seed_mask_joined_kernel(SeedArgs a, int sid, int64_t n_matched, 
 __device__ __forceinline__ void finish_pair(const SeedArgs& a, int sid, int chunk, const uint8_t* qmt, const int8_t* q, const int8_t* s,
 	uint32_t qid, int seed_offset, int query_len, int64_t sloc, int score)
 {
-	if (!left_most_pair(a.params, q, qmt, s, seed_offset, sid, chunk, query_len)) return;
+	if (lin_applies_left_most(a.lin_first != nullptr) && !left_most_pair(a.params, q, qmt, s, seed_offset, sid, chunk, query_len)) return;
 	const unsigned long long idx = atomicAdd(a.hit_count, 1ull);
 	if (idx < (unsigned long long)a.hit_cap) {
 		dmnd_seed_hit h;
@@ -1115,8 +1115,9 @@ __device__ __forceinline__ int stage2_score(const SeedArgs& a, const int8_t* mat
 	clip_window(q - window, 2 * window, window, cb, ce);
 	const int window_left = window - cb;
 	const int score = ungapped_window_score(matrix, q - window_left, s - window_left, ce - cb);
-	if (score > 255) {
-		// saturation depends on the SIMD batch of the reference: second pass (seed_deferred_kernel)
+	if (lin_score_is_deferred(score, a.lin_first != nullptr)) {
+		// saturation depends on the SIMD batch of the reference: second pass (seed_deferred_kernel); a linearised search's batch of
+		// one keeps its scalar score (linsearch_core.h)
 		const unsigned long long d = atomicAdd(a.deferred_count, 1ull);
 		if (d < (unsigned long long)a.deferred_cap) a.deferred[d] = SeedDeferred{ sloc, slot, x, score, 0 };
 		atomicOr(&a.need_bits[slot >> 5], 1u << (slot & 31));
@@ -1142,7 +1143,7 @@ __device__ __forceinline__ void post_hamming(const SeedArgs& a, int sid, uint32_
 			clip_window(q - window, 2 * window, window, cb, ce);
 			const int window_left = window - cb;
 			score = ungapped_window_score(a.matrix, q - window_left, s - window_left, ce - cb);
-			if (score > 255) {
+			if (lin_score_is_deferred(score, a.lin_first != nullptr)) {
 				// saturation depends on the SIMD batch of the reference: second pass (seed_deferred_kernel)
 				const unsigned long long d = atomicAdd(a.deferred_count, 1ull);
 				if (d < (unsigned long long)a.deferred_cap) a.deferred[d] = SeedDeferred{ sloc, slot, x, score, 0 };
@@ -1167,6 +1168,34 @@ __device__ __forceinline__ void filter_pair(const SeedArgs& a, int sid, uint32_t
 	post_hamming(a, sid, slot, slot_flags, chunk, sloc, x);
 }
 
+// ---- linearised search (linsearch_core.h): the first joined reference position of every seed -----------------------------------
+// Two kernels over the shape's joined records, on the search's stream in front of the pair filter that reads their result:
+// STEP 0 writes LIN_NO_POSITION into lin_first[slot] of every slot that occurs (so the array needs no clear per search, per shape or
+// per repeated phase 1: a slot is only ever read through one of the records that initialised it in this very pass), STEP 1 takes
+// the 64-bit minimum of the positions per slot. Neither result depends on the order of the records. Erased seeds are reduced too
+// (one read less than testing the flag; their records stop at the pair filter as ever).
+// CHAIN (seed_chain.h): the shape's range of the shared lists comes from the counter block; the guard is seed_pair_kernel's.
+template<bool CHAIN, int STEP>
+__global__ __launch_bounds__(256) void seed_lin_first_kernel(SeedArgs a, int sid, int64_t n_matched, SeedChain ch)
+{
+	int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, end = n_matched;
+	if (CHAIN) {
+		if (ch.ctr[chain_ctr_status(ch.S)]) return;       // (incomplete lists among the reasons: nothing behind ctr[sid] is read)
+		m += sid ? (int64_t)ch.ctr[sid - 1] : 0;
+		end = (int64_t)ch.ctr[sid];
+	}
+	for (; m < end; m += (int64_t)gridDim.x * blockDim.x) {
+		const uint32_t slot = a.matched_slot[m];
+		if (STEP == 0) a.lin_first[slot] = LIN_NO_POSITION;
+		else {
+			// lin_first_update as one atomic: positions are non-negative, so the signed and the unsigned order agree
+			const int64_t pos = a.matched_loc[m];
+			if (lin_first_update(a.lin_first[slot], pos) == pos) atomicMin(reinterpret_cast<unsigned long long*>(&a.lin_first[slot]), (unsigned long long)pos);
+		}
+		if (!CHAIN) return;                               // (the host-sized grid covers the list)
+	}
+}
+
 // One thread per joined reference position; the seed's query positions are a contiguous list. Work per position is the
 // list length, which is heavily skewed (a frequent seed has thousands of query positions and thousands of joined reference
 // positions): lists longer than LIGHT are processed by the whole wavefront, 64 query positions at a time, so that no lane
@@ -1176,7 +1205,8 @@ __device__ __forceinline__ void filter_pair(const SeedArgs& a, int sid, uint32_t
 // CHAIN (seed_chain.h): the shape's range of the shared lists comes from the counter block; a bounded grid walks it in tiles of
 // one workgroup (a workgroup-uniform trip count: the staging area is flushed per tile)
 // MLR (mutual-coverage search): the joined position's window of admissible query positions is looked up with its slot, once
-template<bool CHAIN, bool MLR>
+// LIN (linearised search, linsearch_core.h): a joined position that is not the first of its seed has no pairs
+template<bool CHAIN, bool MLR, bool LIN = false>
 __global__ __launch_bounds__(128) void seed_pair_kernel(SeedArgs a, int sid, int64_t n_matched, SeedChain ch)
 {
 	constexpr uint32_t LIGHT = 8;
@@ -1215,6 +1245,7 @@ __global__ __launch_bounds__(128) void seed_pair_kernel(SeedArgs a, int sid, int
 				head = sl.head; count = sl.flags >> 8;
 				sloc = a.matched_loc[m];
 				if (MLR) win = seed_window_at(a, sloc);
+				if (LIN && !lin_record_selected(sloc, a.lin_first[slot])) count = 0;
 			}
 		}
 		if (count <= LIGHT)
@@ -1254,7 +1285,9 @@ __global__ __launch_bounds__(128) void seed_pair_kernel(SeedArgs a, int sid, int
 // stage-2 code while the others wait (measured: 3/4 of the kernel's time). They are staged in LDS, flushed to a compact
 // survivor list with one global atomic per flush, and scored by seed_post_kernel with all lanes busy.
 // MLR (mutual-coverage search): every thread holds its reference position's window of admissible query positions
-template<bool MLR>
+// LIN (linearised search, linsearch_core.h): a thread whose joined position is not the first of its seed holds an empty entry; the one
+// that is starts its seed's run wherever it stands among the entries of equal slot
+template<bool MLR, bool LIN = false>
 __global__ __launch_bounds__(256) void seed_pair_tiled_kernel(SeedArgs a, int sid, int64_t n_matched)
 {
 	constexpr uint32_t LIGHT = 8;
@@ -1283,6 +1316,7 @@ __global__ __launch_bounds__(256) void seed_pair_tiled_kernel(SeedArgs a, int si
 			sloc = a.matched_loc[m];
 			__builtin_memcpy(sw, a.tdata + sloc - 16, 48);
 			if (MLR) win = seed_window_at(a, sloc);
+			if (LIN && !lin_record_selected(sloc, a.lin_first[slot])) { slot = LIST_END; head = 0; count = 0; }
 		}
 	}
 	auto survive = [&](uint32_t x) {
@@ -1390,8 +1424,9 @@ __device__ __forceinline__ int stage2_score_regs(const SeedArgs& a, const int8_t
 		st = imax(st, 0);
 		score = imax(score, st);
 	}
-	if (score > 255) {
-		// saturation depends on the SIMD batch of the reference: second pass (seed_deferred_kernel)
+	if (lin_score_is_deferred(score, a.lin_first != nullptr)) {
+		// saturation depends on the SIMD batch of the reference: second pass (seed_deferred_kernel); a linearised search's batch of
+		// one keeps its scalar score (linsearch_core.h)
 		const unsigned long long d = atomicAdd(a.deferred_count, 1ull);
 		if (d < (unsigned long long)a.deferred_cap) a.deferred[d] = SeedDeferred{ sloc, slot, x, score, 0 };
 		atomicOr(&a.need_bits[slot >> 5], 1u << (slot & 31));
@@ -1534,7 +1569,8 @@ __global__ __launch_bounds__(256) void seed_leftmost_kernel(SeedArgs a, int sid,
 			qid = a.qid_of[qp];
 			seed_offset = (int)(qp - a.qlimits[qid]);
 			const int query_len = (int)(a.qlimits[qid + 1] - a.qlimits[qid] - 1);
-			keep = left_most_pair_t(LmWide{ map_lo, map_hi, reduction_ok }, a.params, a.qdata + qp, a.mask_time + qp, a.tdata + sc.sloc, seed_offset, sid, sc.chunk, query_len);
+			// (a linearised search skips the rule, linsearch_core.h: every scored pair is a hit)
+			keep = !lin_applies_left_most(a.lin_first != nullptr) || left_most_pair_t(LmWide{ map_lo, map_hi, reduction_ok }, a.params, a.qdata + qp, a.mask_time + qp, a.tdata + sc.sloc, seed_offset, sid, sc.chunk, query_len);
 		}
 		// one atomic on the hit counter per wavefront
 		const unsigned long long mask = __ballot(keep);
@@ -2140,10 +2176,23 @@ hipError_t launch_seed_mask(const SeedArgs& a, int sid, hipStream_t st, int64_t 
 	return hipGetLastError();
 }
 
+hipError_t launch_seed_lin_first(const SeedArgs& a, int64_t n_matched, hipStream_t st)
+{
+	if (n_matched == 0 || !a.lin_first) return hipSuccess;
+	hipLaunchKernelGGL((seed_lin_first_kernel<false, 0>), dim3(blocks_for(n_matched, 256)), dim3(256), 0, st, a, 0, n_matched, SeedChain{});
+	hipLaunchKernelGGL((seed_lin_first_kernel<false, 1>), dim3(blocks_for(n_matched, 256)), dim3(256), 0, st, a, 0, n_matched, SeedChain{});
+	return hipGetLastError();
+}
+
 hipError_t launch_seed_pairs(const SeedArgs& a, int sid, int64_t n_matched, hipStream_t st)
 {
 	if (n_matched == 0) return hipSuccess;
-	if (a.qwin) hipLaunchKernelGGL((seed_pair_kernel<false, true>), dim3(blocks_for(n_matched, 128)), dim3(128), 0, st, a, sid, n_matched, SeedChain{});
+	if (a.lin_first) {                                   // linearised search (never with a length ratio: dmnd_seed_search refuses the two together)
+		const hipError_t e = launch_seed_lin_first(a, n_matched, st);
+		if (e != hipSuccess) return e;
+		hipLaunchKernelGGL((seed_pair_kernel<false, false, true>), dim3(blocks_for(n_matched, 128)), dim3(128), 0, st, a, sid, n_matched, SeedChain{});
+	}
+	else if (a.qwin) hipLaunchKernelGGL((seed_pair_kernel<false, true>), dim3(blocks_for(n_matched, 128)), dim3(128), 0, st, a, sid, n_matched, SeedChain{});
 	else hipLaunchKernelGGL((seed_pair_kernel<false, false>), dim3(blocks_for(n_matched, 128)), dim3(128), 0, st, a, sid, n_matched, SeedChain{});
 	return hipGetLastError();
 }
@@ -2151,7 +2200,12 @@ hipError_t launch_seed_pairs(const SeedArgs& a, int sid, int64_t n_matched, hipS
 hipError_t launch_seed_pairs_tiled(const SeedArgs& a, int sid, int64_t n_matched, hipStream_t st)
 {
 	if (n_matched == 0) return hipSuccess;
-	if (a.qwin) hipLaunchKernelGGL(seed_pair_tiled_kernel<true>, dim3(blocks_for(n_matched, 256)), dim3(256), 0, st, a, sid, n_matched);
+	if (a.lin_first) {
+		const hipError_t e = launch_seed_lin_first(a, n_matched, st);
+		if (e != hipSuccess) return e;
+		hipLaunchKernelGGL((seed_pair_tiled_kernel<false, true>), dim3(blocks_for(n_matched, 256)), dim3(256), 0, st, a, sid, n_matched);
+	}
+	else if (a.qwin) hipLaunchKernelGGL(seed_pair_tiled_kernel<true>, dim3(blocks_for(n_matched, 256)), dim3(256), 0, st, a, sid, n_matched);
 	else hipLaunchKernelGGL(seed_pair_tiled_kernel<false>, dim3(blocks_for(n_matched, 256)), dim3(256), 0, st, a, sid, n_matched);
 	return hipGetLastError();
 }
@@ -2403,7 +2457,12 @@ hipError_t launch_seed_chain_mask(const SeedArgs& a, const SeedChain& ch, int si
 
 hipError_t launch_seed_chain_shape(const SeedArgs& a, const SeedChain& ch, int sid, hipStream_t st)
 {
-	if (a.qwin) hipLaunchKernelGGL((seed_pair_kernel<true, true>), dim3(CHAIN_GRID), dim3(128), 0, st, a, sid, (int64_t)0, ch);
+	if (a.lin_first) {                                   // the reduction over the shape's range of the counter block, then the filter that reads it
+		hipLaunchKernelGGL((seed_lin_first_kernel<true, 0>), dim3(CHAIN_GRID / 2), dim3(256), 0, st, a, sid, (int64_t)0, ch);
+		hipLaunchKernelGGL((seed_lin_first_kernel<true, 1>), dim3(CHAIN_GRID / 2), dim3(256), 0, st, a, sid, (int64_t)0, ch);
+		hipLaunchKernelGGL((seed_pair_kernel<true, false, true>), dim3(CHAIN_GRID), dim3(128), 0, st, a, sid, (int64_t)0, ch);
+	}
+	else if (a.qwin) hipLaunchKernelGGL((seed_pair_kernel<true, true>), dim3(CHAIN_GRID), dim3(128), 0, st, a, sid, (int64_t)0, ch);
 	else hipLaunchKernelGGL((seed_pair_kernel<true, false>), dim3(CHAIN_GRID), dim3(128), 0, st, a, sid, (int64_t)0, ch);
 	hipLaunchKernelGGL(seed_score_kernel<true>, dim3(CHAIN_GRID / 2), dim3(POST_THREADS), 0, st, a, sid, (int64_t)0, ch);
 	// (a voided shape leaves the scored count zero: the left-most kernel reads it and leaves)

@@ -305,6 +305,22 @@ int dmnd_set_min_length_ratio(dmnd_ctx* ctx, double ratio);
  * descending, the reference's order (data/block/block.cpp:229-255; ties come out in DEscending index order, not stably).
  * limits: n + 1 block offsets as for dmnd_upload_block. */
 int dmnd_length_sort_order(const int64_t* limits, int64_t n, int64_t* order);
+/* Linearised search (--linsearch, basic/config.cpp:425: "only consider seed hits against longest target for identical seeds").
+ * on != 0: per shape and seed, dmnd_seed_search compares the seed's query positions with ONE reference position only, the
+ * smallest position of the reference block that carries the seed -- s[0] of the reference's joined group, whose order is the
+ * block's (search/hamming/kernel_lin.h:132-153, stage1_target_lin; dispatch search/stage1_2.cpp:38-39,52;
+ * util/algo/hash_join.h:98-111,157-169). Every other reference position of the seed is dropped, later ones of the same target
+ * and ones whose pair would have passed where the first one fails included. Such a pair is a stage-2 batch of one subject
+ * (search/stage2.h:101,132): the left-most filter is skipped and a window score above 255 is kept as it is, never saturated.
+ * Masking of non-complex seeds is unchanged. The reference replaces every reference block by its length-sorted copy first
+ * (run/double_indexed.cpp:112-115; the query block is not sorted, :727), so that the first position lies in the longest target,
+ * and so must the caller (dmnd_length_sort_order). dmnd_seed_search with the switch on returns DMND_E_ARG, before anything is
+ * launched, if a shape has a weight below 10 (search/setup.cpp:365-366), if the reference block is not in non-increasing length
+ * order, or if a minimum length ratio is set as well. First positions are per reference block and are found again by every
+ * search, so dmnd_set_query_index_reuse keeps working. Off by default; off, the search runs the kernels it always ran.
+ * Nothing behind the seed stage reads the switch (the reference's command line defaults the extension to full-matrix mode,
+ * search/setup.cpp:377-379: dmnd_set_extension_mode). */
+int dmnd_set_linsearch(dmnd_ctx* ctx, int on);
 /* For tests and diagnosis: the windows the last dmnd_seed_search with a ratio > 0 built on the device, per target of the reference
  * block { first, end } = the query positions (counted from the query block's first limit) of the queries that pass against it;
  * { 0, 0 }: none. out: 2 * n_targets words. DMND_E_ARG if the last search ran without a ratio. */

@@ -72,6 +72,57 @@ inline ChainPlan chain_plan(unsigned long long status, unsigned long long done, 
 	return ChainPlan{ CHAIN_COMPLETE, 0 };
 }
 
+// What the host-driven code does behind a chain; as constructed, what it does without one (everything, keeping nothing)
+struct ChainResume {
+	bool hits_done = false;              // the sorted hits are in place: neither phase 2 nor the hit sort is left
+	bool phase1_again = true;            // phase 1 (index, stream and mask of every shape) is the host's ...
+	bool dirty = false;                  // ... behind an abandoned chain that has used the counters, tables and filters
+	int64_t cap_total = 0;               // capacity of the joined-position lists that phase 1 starts from
+	int p2_first = 0;                    // phase 2: first shape whose pair filter is the host's ...
+	bool p2_keep = false;                // ... the hits of the shapes before it are in seed_hits
+	int deferred_sid = -1;               // shape whose deferred pass comes before that (-1: none) ...
+	unsigned long long deferred_n = 0;   // ... and the deferred pairs the chain counted for it
+	// p2_keep: the capacities under which the kept hits and deferred pairs were written. Otherwise the least capacity phase 2 starts
+	// from: that of a list that overflowed, grown; 0 where phase 2's own starting capacity holds
+	int64_t hit_cap = 0, def_cap = 0;
+	bool discard_pairs_time = false;     // the chain's pair filters run again: their time does not count
+};
+
+// r: the counter block the chain left (r[S - 1] joined positions of all shapes, r[S] hits, r[S + 1] deferred pairs); cap_total,
+// hit_cap, def_cap: the capacities the chain ran with
+inline ChainResume chain_resume(const ChainPlan& plan, const unsigned long long* r, int S, int64_t cap_total, int64_t hit_cap, int64_t def_cap)
+{
+	ChainResume x;
+	x.phase1_again = false;
+	x.cap_total = cap_total;
+	switch (plan.point) {
+	case CHAIN_COMPLETE:
+		x.hits_done = true;
+		break;
+	case CHAIN_FROM_PHASE1:
+		x.phase1_again = x.dirty = x.discard_pairs_time = true;      // the abandoned attempt does not count
+		x.cap_total = (int64_t)r[S - 1] + (int64_t)r[S - 1] / 8 + 1024;
+		break;
+	case CHAIN_FROM_PAIRS:
+		x.p2_first = plan.shape; x.p2_keep = true;
+		break;
+	case CHAIN_FROM_DEFERRED:
+		x.deferred_n = r[S + 1];
+		if ((int64_t)x.deferred_n > def_cap) { x.def_cap = (int64_t)x.deferred_n + 1024; x.discard_pairs_time = true; return x; }      // an incomplete list: phase 2 again
+		x.deferred_sid = plan.shape; x.p2_first = plan.shape + 1; x.p2_keep = true;
+		break;
+	case CHAIN_FROM_PHASE2:
+		x.hit_cap = (int64_t)r[S] + 1024;
+		x.discard_pairs_time = true;
+		break;
+	case CHAIN_FROM_SORT:
+		x.p2_first = S; x.p2_keep = true;
+		break;
+	}
+	if (x.p2_keep) { x.hit_cap = hit_cap; x.def_cap = def_cap; }
+	return x;
+}
+
 // the DMND_TRACE summary's name of the path taken
 inline void chain_path_name(char* out, size_t n, const ChainPlan& p, unsigned long long status)
 {

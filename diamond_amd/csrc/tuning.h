@@ -2,9 +2,11 @@
 // None of them is part of the ABI; every one has a measured default and is read ONCE per process from the environment variable
 // named beside it (the sweeps that chose the defaults: DESIGN.md 6.4, 6.6, 4.17; tools/seed_modes.py).
 // Not here, on purpose: diagnostics (DMND_TRACE*, DMND_SEED_PHASES, DMND_CLI_TIMELINE), the tests' hooks that force a rare path
-// per call (buffer caps, DMND_SEED_TILED / _FUSED / _CLASSES_LONG / _SLICES / _SLICE_WORDS, DMND_TRACE_ARENA_MB, DMND_SWIPE32 ...) and the A/B switches that keep
-// the previous form of a stage alive as the second implementation parity tests compare with (DMND_EXTEND_DEVICE, _PLAN_GPU,
-// _XDROP_GPU, _KEEP_TRACE): DESIGN.md 9 lists them all.
+// per call (DMND_TRACE_ARENA_MB, DMND_SWIPE32 ...; those of the seed search -- DMND_SEED_CHAIN / _TILED / _CLASSES_LONG / _SLICES /
+// _SLICES_BUDGET_MB / _SLICES_MIN_LETTERS / _SLICE_WORDS, the buffer caps _MATCHED_CAP / _SURVIVOR_CAP / _HIT_CAP / _DEFERRED_CAP,
+// _SORT_CAP, _READBACK_BYTES -- are read once per call in their own ONE place, seed_api.hip seed_hooks; DMND_SEED_FUSED in seed_sizes)
+// and the A/B switches that keep the previous form of a stage alive as the second implementation parity tests compare with
+// (DMND_EXTEND_DEVICE, _PLAN_GPU, _XDROP_GPU, _KEEP_TRACE): DESIGN.md 9 lists them all.
 #pragma once
 #include <algorithm>
 #include <cstdlib>
@@ -30,10 +32,10 @@ struct Tuning {
 	// ---- seed stage geometry (seed_api.hip seed_sizes; 0 = the size-dependent default chosen there)
 	int seed_slots_x8 = 0;             // DMND_SEED_SLOTS_X8: table slots per query position x 8 (8 .. 64; default 32 fused / 16)
 	// ---- chain mode of the long-seed search (seed_chain.h)
-	// (values only: the environment variables of these two are the tests' per-call hooks, read in ONE place, seed_api.hip chain_sort_cap / chain_readback_bytes)
+	// (values only: the environment variables of these two are the tests' per-call hooks, read in ONE place, seed_api.hip seed_hooks)
 	int seed_readback_bytes = 1 << 20; // DMND_SEED_READBACK_BYTES: most bytes of sorted hits that come back with the chain's one copy
 	// ---- sliced long-seed stream (seed_slices_core.h)
-	// (values only, like the two above: their environment variables are per-call hooks read in seed_api.hip)
+	// (values only, like the two above: their environment variables are per-call hooks read in seed_api.hip seed_hooks)
 	int seed_slices_budget_mb = 3072;  // DMND_SEED_SLICES_BUDGET_MB: most MB of reference-side cache a context keeps. 8 bytes per reference letter and shape (list entry and hash) plus half a byte per letter: C2's 3.0e8-letter block takes 2 561 397 480 bytes (2443 MB) with one shape; with the two of the default sensitivity it would take 4742 MB, which is over the budget, and such a search takes the plain stream (before the hashes two shapes fit, at 2439 MB; the budget was not raised: nothing measured asks for it). Only what is kept counts: the build's scratch (two routing bytes per window, the flag words, the radix pass's: about 0.7 GB more for C2's block until the build is done) does not, and a context that cannot allocate it takes the plain stream
 	long long seed_slices_min_letters = 1 << 20;   // DMND_SEED_SLICES_MIN_LETTERS: reference block length from which on a repeated search takes the sliced stream (C2's query block: sliced / plain stream kernel 0.0179 / 0.0192 ms at 3e5 letters, 0.0189 / 0.0225 ms at 9e5, 0.287 / 0.453 ms at 9e7)
 	long long seed_slices_max_joined = 1 << 20;    // (no hook) joined reference positions of the context's last search above which the default rule leaves the sliced stream out: C2skew (over 1.6e6 per step) ran 28.7 ms per step with it, 26.8-27.4 without, C2 (9e4) 2.50 against 2.98

@@ -15,7 +15,7 @@ from test_gpu_seed import to_hip_params, GOLDEN
 
 pytestmark = pytest.mark.gpu
 
-HOOKS = ("DMND_SEED_CHAIN", "DMND_SEED_MATCHED_CAP", "DMND_SEED_SURVIVOR_CAP", "DMND_SEED_HIT_CAP", "DMND_SEED_TILED", "DMND_SEED_SORT_CAP",
+HOOKS = ("DMND_SEED_CHAIN", "DMND_SEED_MATCHED_CAP", "DMND_SEED_SURVIVOR_CAP", "DMND_SEED_HIT_CAP", "DMND_SEED_DEFERRED_CAP", "DMND_SEED_TILED", "DMND_SEED_SORT_CAP",
          "DMND_SEED_READBACK_BYTES", "DMND_SEED_FUSED", "DMND_SEED_CLASSES_LONG")
 
 
@@ -184,6 +184,18 @@ def test_deferred_pairs_in_an_early_shape_of_many(ctx, monkeypatch, capfd):
     assert first_deferred and first_deferred[0] < sp.n_shapes - 1
     _, path, _ = search(ctx, sp, monkeypatch, capfd, CHAIN=1, FUSED=0)
     assert path == "chain, then host from the deferred pass of shape %d" % first_deferred[0]
+
+
+def test_deferred_pairs_over_the_chains_capacity_run_phase_2_again(ctx, monkeypatch, capfd):
+    """The chain's deferred list one entry long (DMND_SEED_DEFERRED_CAP=1) on a tap whose first shape with deferred pairs has
+    more than one: the list the chain left is incomplete, so nothing of it is kept and the host runs phase 2 again for every
+    shape with a list that has grown to the count the chain read back."""
+    cfg, sp, ref = tap_of("ext_default.tap")
+    upload(ctx, cfg)
+    assert (ref["score"] > 255).any()
+    check(ctx, sp, ref, monkeypatch, capfd, lambda p: p.startswith("chain, then host from the deferred pass of shape"), DEFERRED_CAP=1)
+    first_deferred = [d for d in check.deferred if d]        # (counted by the host-driven path)
+    assert first_deferred and first_deferred[0] > 1
 
 
 def masked_query_block():

@@ -4,7 +4,9 @@ of 1 .. 200 letters in both directions around the multiples of 63 and 64, diagon
 by the matrix origin, by the score, at a running score of exactly 0 and by a gap, two gaps back to back, target letters 20 - 24 and
 bit 7, a random bias, matrices of the items' own (the 32-bit kernels' trace layouts at P <= 4), a saturating item, bands of the
 classes 8 / 16 / 32 and of several wavefronts, with score-0 and 1 x 1 items in between -- in every band class, rows off and on.
-Every number, every transcript byte and the terminator equal the oracle's; a failure names the case's tag."""
+Every number, every transcript byte and the terminator equal the oracle's; a failure names the case's tag. The same corpus rebuilt
+for BLOSUM80 25/2, PAM30 5/2 and PAM250 11/3 (traceback_cases.corpus(scheme)) on a context of that system, in every mode, rows off
+and on: the walk's own gap accounting under gap extend 2 and 3 and its stop rule over PAM30's cell scores."""
 import os
 import re
 import subprocess
@@ -13,6 +15,7 @@ import numpy as np
 import pytest
 import torch
 
+import scoring_schemes as ss
 import traceback_cases as tc
 from diamond_amd import hip, synth, workload
 from gpu_util import pack_records_m
@@ -115,6 +118,24 @@ def test_shuffled_order_and_exact_arena(ctx, c, ref, rows, monkeypatch):
     exact, etr = ctx.banded_swipe(items, hip.SWIPE_TRACEBACK, transcript_cap=cap)
     assert np.array_equal(exact, out) and np.array_equal(etr, tr)
     ctx.upload_matrices(np.zeros((0, 32, 32), np.int8))
+
+
+@pytest.fixture(scope="module", params=ss.TRACEBACK, ids=ss.scheme_id)
+def scheme_ctx(request):
+    """(corpus of the scheme, its oracle, a context on the scheme's params)"""
+    assert torch.cuda.is_available(), "GPU tests need a visible MI355X"
+    sc = tc.corpus(request.param)
+    x = hip.Context(params=sc.params)
+    yield sc, tc.oracle(sc), x
+    x.close()
+
+
+@pytest.mark.parametrize("rows", ["0", "1"])
+def test_scheme_corpus_equals_the_oracle_in_every_mode(scheme_ctx, rows, monkeypatch):
+    """test_corpus_equals_the_oracle_in_every_mode on the corpus of another scoring system"""
+    sc, sref, x = scheme_ctx
+    assert sc.scheme is not None and (x.params.gap_open, x.params.gap_extend) == (sc.gap_open, sc.gap_extend) != (tc.GAP_OPEN, tc.GAP_EXTEND)
+    test_corpus_equals_the_oracle_in_every_mode(x, sc, sref, rows, monkeypatch)
 
 
 def test_host_call_shape(ctx, c, ref):

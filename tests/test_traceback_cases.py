@@ -8,6 +8,7 @@ import pytest
 
 import emu_py as emu
 import oracle_py as orc
+import scoring_schemes as ss
 import traceback_cases as tc
 
 KEYS = "score q_begin q_end s_begin s_end length identities mismatches positives gap_openings gaps transcript_len".split()
@@ -187,12 +188,12 @@ def test_32_bit_lanes_and_statistics_equal_the_oracle(c, ref):
         for P in (1, 2, 4, 8):
             if P < P0 or (long_item and P != P0):
                 continue
-            rc, e, etr = emu.banded_swipe(rec["query"], rec["cbs"], t["seq"], t["d_begin"], t["d_end"], c.matrix_of(rec), 11, 1, 2, P)
+            rc, e, etr = emu.banded_swipe(rec["query"], rec["cbs"], t["seq"], t["d_begin"], t["d_end"], c.matrix_of(rec), c.gap_open, c.gap_extend, 2, P)
             assert rc == 0, rec["tag"]
             _same(rec, e, etr, o, otr, "32-bit class %d" % P)
             n[P] += 1
         if P0 <= 4:
-            rc, e = emu.swipe_stats(rec["query"], rec["cbs"], t["seq"], t["d_begin"], t["d_end"], c.matrix_of(rec), 11, 1)
+            rc, e = emu.swipe_stats(rec["query"], rec["cbs"], t["seq"], t["d_begin"], t["d_end"], c.matrix_of(rec), c.gap_open, c.gap_extend)
             assert rc == 0 and e["score"] == st["score"], rec["tag"]
             if st["score"] > 0:
                 for k in STAT_KEYS:
@@ -218,7 +219,7 @@ def test_packed_sweeps_equal_the_oracle_in_every_class(c, ref):
         w = max(c.width(c.recs[ka]), c.width(c.recs[kb]))
         classes = [P for P in (1, 2, 4) if 128 * P >= w] + ([3] if w <= 96 else []) + ([5] if w <= 160 else [])
         for P in classes:
-            rc, (ea, tra), (eb, trb) = emu.banded_swipe16(item(ka), item(kb), c.matrix_of(c.recs[ka]), 11, 1, True, P)
+            rc, (ea, tra), (eb, trb) = emu.banded_swipe16(item(ka), item(kb), c.matrix_of(c.recs[ka]), c.gap_open, c.gap_extend, True, P)
             assert rc == 0, (c.recs[ka]["tag"], P)
             _same(c.recs[ka], ea, tra, ref[ka][0], ref[ka][1], "packed class %d" % P)
             _same(c.recs[kb], eb, trb, ref[kb][0], ref[kb][1], "packed class %d" % P)
@@ -226,6 +227,108 @@ def test_packed_sweeps_equal_the_oracle_in_every_class(c, ref):
     assert all(v >= 50 for v in n.values()), n
     # the saturating item reports 32767 and leaves its partner alone
     sat = c.select(family="sat")[0]
-    rc, (ea, _), (eb, trb) = emu.banded_swipe16(item(sat), item(plain[0]), c.M, 11, 1, True, 0)
+    rc, (ea, _), (eb, trb) = emu.banded_swipe16(item(sat), item(plain[0]), c.M, c.gap_open, c.gap_extend, True, 0)
     assert rc == 0 and ea["score"] == 32767
     _same(c.recs[plain[0]], eb, trb, ref[plain[0]][0], ref[plain[0]][1], "next to a saturating item")
+
+
+# ---- the corpus under other scoring systems ------------------------------------------------------------------------------------------
+
+@pytest.fixture(scope="module", params=ss.TRACEBACK, ids=ss.scheme_id)
+def sc(request):
+    return tc.corpus(request.param)
+
+
+@pytest.fixture(scope="module")
+def sref(sc):
+    return tc.oracle(sc)
+
+
+def test_scheme_corpus_bands_and_classes(sc):
+    assert sc is not tc.corpus() and (sc.params.gap_open, sc.params.gap_extend) == sc.scheme[1:]
+    assert np.array_equal(sc.M, ss.matrix(sc.scheme[0]))
+    test_corpus_size_and_bands(sc)
+    test_every_band_class_per_family(sc)
+    x, y = sc.low_pair
+    assert int(sc.M[x, y]) == int(sc.M[:20, :20].min()) and -int(sc.M[x, y]) > 2 * sc.gap_extend
+    assert sc.adj_gap * (-int(sc.M[x, y])) >= 2 * (sc.gap_open + sc.adj_gap * sc.gap_extend) + sc.gap_open, sc.adj_gap       # two gaps win by a gap open and more
+
+
+def test_scheme_gaps_of_exactly_g_letters(sc, sref):
+    """one gap of exactly G letters although it costs up to go + 200 ge (611 under PAM250 11/3): both flanks outscore it"""
+    test_gaps_of_exactly_g_letters(sc, sref)
+    cost = sc.gap_open + 200 * sc.gap_extend
+    for rec, o, _ in _of(sc, sref, family="gap", G=200, variant="plain"):
+        flank = (len(rec["query"]) + len(rec["targets"][0]["seq"]) - 200) // 4
+        assert o["score"] >= 0.6 * cost and o["identities"] == 2 * flank, (rec["tag"], o, cost)
+
+
+def test_scheme_runs_of_exactly_n_columns_by_each_ender(sc, sref):
+    assert sc.zero_prefix is not None and 2 <= len(sc.zero_prefix) <= 5
+    first = int(sc.M[sc.zero_prefix[0][1], sc.zero_prefix[0][0]])
+    assert first == int(sc.M[tc.W, tc.W]) == int(sc.M[:20, :20].max())
+    seen = set()
+    for rec, o, tr in _of(sc, sref, family="run"):
+        N, form = rec["info"]["N"], rec["info"]["form"]
+        begin = {"origin": 0, "score": 7, "zero": len(sc.zero_prefix)}[form]
+        seen.add((N, form, rec["info"]["variant"]))
+        if (N, form) == (1, "zero"):
+            assert o["score"] >= first and o["s_begin"] == 0, (rec["tag"], o)          # (as under BLOSUM62: no column outscores W:W)
+            continue
+        assert (o["length"], o["q_begin"], o["s_begin"], o["gaps"]) == (N, begin, begin, 0), (rec["tag"], o)
+        assert (o["q_end"], o["s_end"]) == (begin + N, begin + N) and len(tr) == N, rec["tag"]
+        M, t = sc.matrix_of(rec), rec["targets"][0]["seq"]
+        if form == "zero":
+            assert rec["cbs"] is None or not rec["cbs"][:begin].any()
+            sums = np.cumsum([int(M[t[k] & 31, rec["query"][k] & 31]) for k in range(begin)])
+            assert sums[-1] == 0 and (sums[:-1] > 0).all(), (rec["tag"], sums)
+        if form == "score":
+            assert all(int(M[t[k], rec["query"][k]]) < 0 for k in range(7)), rec["tag"]
+    assert seen == {(N, f, v) for N in tc.RUNS for f in ("origin", "score", "zero") for v in ("plain", "bias", "own")}
+
+
+def test_scheme_runs_between_gaps_and_adjacent_gaps(sc, sref):
+    for rec, o, tr in _of(sc, sref, family="between"):
+        r, order = rec["info"]["r"], rec["info"]["order"]
+        runs = tc.gap_runs(tr)
+        want = [(INS, 5, r), (DEL, 5, r)] if order == "ID" else [(DEL, 5, r), (INS, 5, r)]
+        assert runs == want and o["length"] == 3 * r + 10 and o["q_begin"] == 0, (rec["tag"], runs, o)
+    n = 0
+    for rec, o, tr in _of(sc, sref, family="adjacent") + _of(sc, sref, family="wide", kind="adjacent"):
+        runs = tc.gap_runs(tr)
+        assert (o["gap_openings"], o["gaps"]) == (2, 2 * sc.adj_gap), (rec["tag"], o)
+        assert len(runs) == 2 and {runs[0][0], runs[1][0]} == {INS, DEL} and runs[0][1] == runs[1][1] == sc.adj_gap, (rec["tag"], runs)
+        assert runs[1][2] == 0, (rec["tag"], runs)
+        n += 1
+    assert n >= 2 * 3 + 4
+
+
+def test_scheme_letters_saturation_and_zero_scores(sc, sref):
+    assert len(sc.letter_columns) >= 4 and (sc.scheme != ("pam30", 5, 2) or sc.letter_columns == (20, 21, 22, 23))
+    for rec, o, tr in _of(sc, sref, family="letters"):
+        subs = {int(b) & 63 for b in tr if int(b) >> 6 == 3}
+        assert set(sc.letter_columns) <= subs, (rec["tag"], sorted(subs))
+        assert o["positives"] >= o["identities"] + 5 and o["mismatches"] >= 12, (rec["tag"], o)
+        t = rec["targets"][0]["seq"]
+        assert (rec["query"] < 0).sum() >= 5 and (t < 0).sum() >= 5
+        if rec["info"]["kind"] == "deletion":
+            dels = [int(b) & 63 for b in tr if int(b) >> 6 == DEL]
+            want = [20, 21, 22, 23, 24, 5, 20, 21]
+            at = [k for k in range(len(dels) - 7) if dels[k: k + 8] == want]
+            assert len(at) == 1, (rec["tag"], dels)
+            # (a letter that cannot stand in a column is deleted against an inserted query letter)
+            assert all(d not in sc.letter_columns and d >= 20 for d in dels[:at[0]] + dels[at[0] + 8:]), (rec["tag"], dels)
+    sat = _of(sc, sref, family="sat")
+    assert len(sat) == 2
+    for rec, o, tr in sat:
+        assert o["score"] >= 32767 and (o["gap_openings"], o["gaps"]) == (1, tc.SAT_GAP), (rec["tag"], o)
+    zeros, ones = _of(sc, sref, family="zero", kind="WxD"), _of(sc, sref, family="zero", kind="1x1")
+    assert len(zeros) >= 20 and len(ones) >= 20
+    assert all(o["score"] == 0 for _, o, _ in zeros)
+    assert all(o["score"] > 0 and o["length"] == 1 and len(r["query"]) == 1 for r, o, _ in ones)
+
+
+def test_scheme_corpus_through_the_emulators(sc, sref):
+    """the serial walk of swipe_core.h keeps its own gap accounting too: gaps of up to 200 letters under gap extend 2 and 3"""
+    test_32_bit_lanes_and_statistics_equal_the_oracle(sc, sref)
+    test_packed_sweeps_equal_the_oracle_in_every_class(sc, sref)

@@ -8,6 +8,7 @@ import pytest
 
 import oracle_py as orc
 import emu_py as emu
+import scoring_schemes as ss
 from tapfile import read_tap
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -196,3 +197,26 @@ def test_saturation_is_reported():
     assert eb["score"] == o["score"]
     rc, (eb2, _), (ea2, _) = emu.banded_swipe16(small, big, M, 11, 1, False)
     assert ea2["score"] == 32767 and eb2["score"] == o["score"]
+
+
+@pytest.mark.parametrize("name", ss.NAMES)
+def test_pairs_under_every_gap_row(name):
+    """Every (gap open, gap extend) row the library has for the matrix (tests/scoring_schemes.py): the 40 seeded items of the row
+    as 20 pairs, each pair in the class of its bands or a wider forced one, and in the row classes 3 and 5 where both bands fit."""
+    M = ss.matrix(name)
+    rows = ss.rows(name)
+    assert len(rows) >= 5
+    n = {0: 0, 1: 0, 2: 0, 4: 0, 3: 0, 5: 0}
+    for go, ge in rows:
+        items = ss.emulator_items(ss.row_seed(name, go, ge))
+        for k in range(0, len(items), 2):
+            a, b = items[k], items[k + 1]
+            width = max(a["d_end"] - a["d_begin"], b["d_end"] - b["d_begin"])
+            P = (0, 1, 2, 4)[(k // 2) % 4]
+            _check_pair(a, b, M, go, ge, force_p=P)
+            n[P] += 1
+            for R in (3, 5):
+                if width <= 32 * R:
+                    _check_pair(a, b, M, go, ge, force_p=R)
+                    n[R] += 1
+    assert all(v >= 2 * len(rows) for v in n.values()), n

@@ -7,6 +7,7 @@ import pytest
 
 import oracle_py as orc
 import emu_py as emu
+import scoring_schemes as ss
 from tapfile import read_tap
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -119,3 +120,26 @@ def test_emulated_wavefront_wide_classes_and_ties():
             continue
         cbs = rng.integers(-2, 2, len(q)).astype(np.int8) if it % 2 else None
         _compare(q, cbs, t, d0, d1, M, 11, 1, force_p=(1, 2, 4, 8)[it % 4])
+
+
+@pytest.mark.parametrize("name", ss.NAMES)
+def test_emulated_wavefront_under_every_gap_row(name):
+    """Every (gap open, gap extend) row the library has for the matrix (tests/scoring_schemes.py, 82 rows over the eight
+    matrices): 40 seeded items per row -- the mix of test_emulated_wavefront_random_geometry and related pairs with two indels --
+    in every mode, each in a forced class of its own (1, 2, 4, 8, never below the band's), and the statistics pass."""
+    M = ss.matrix(name)
+    rows = ss.rows(name)
+    assert len(rows) >= 5 and sum(len(ss.rows(n)) for n in ss.NAMES) == ss.N_ROWS
+    n = n_gapped = 0
+    for go, ge in rows:
+        for it, x in enumerate(ss.emulator_items(ss.row_seed(name, go, ge))):
+            _compare(x["query"], x["cbs"], x["target"], x["d_begin"], x["d_end"], M, go, ge, force_p=(1, 2, 4, 8)[it % 4])
+            rc, o = orc.swipe_stats(x["query"], x["cbs"], x["target"], x["d_begin"], x["d_end"], M, go, ge, 510)
+            rc2, e = emu.swipe_stats(x["query"], x["cbs"], x["target"], x["d_begin"], x["d_end"], M, go, ge)
+            assert rc == 0 and rc2 == 0 and e["score"] == o["score"], (name, go, ge, it)
+            if o["score"] > 0:
+                for k in STAT_KEYS:
+                    assert e[k] == o[k], (name, go, ge, it, k, e, o)
+                n_gapped += o["gaps"] > 0
+            n += 1
+    assert n == 40 * len(rows) and n_gapped >= 8 * len(rows), (n, n_gapped)

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import emu_py as emu
+import scoring_schemes as ss
 import xdrop_cases as xc
 
 
@@ -69,14 +70,14 @@ def test_every_cell_of_the_delimiter_grid_in_both_directions(c):
 
 
 def test_walks_cross_one_two_and_three_chunks(c):
-    ref = xc.reference(c, xc.DEFAULT_XDROP, False)
+    ref = xc.reference(c, c.default_xdrop, False)
     left, right = ref[:, 0], ref[:, 1] - ref[:, 0]
     for n in (16, 32, 48):
         assert int((left > n).sum()) >= 50 and int((right > n).sum()) >= 50, (n, int((left > n).sum()), int((right > n).sum()))
 
 
 def test_corners_and_delimiter_subjects(c):
-    ref = xc.reference(c, xc.DEFAULT_XDROP, False)
+    ref = xc.reference(c, c.default_xdrop, False)
     h = c.hits
     last_q, last_t = c.n_queries - 1, c.n_targets - 1
     tid = np.searchsorted(c.tl, h["subject"], side="right") - 1
@@ -103,7 +104,7 @@ def test_corners_and_delimiter_subjects(c):
 
 
 def test_both_endings_for_every_xdrop_and_sharp_boundary_triples(c):
-    for x in xc.XDROPS[:-1]:
+    for x in c.xdrops[:-1]:
         ends = _ends(c, x)
         by_x = sum(e[0][0] == "x" for e in ends) + sum(e[1][0] == "x" for e in ends)
         by_d = sum(e[0][0] == "d" for e in ends) + sum(e[1][0] == "d" for e in ends)
@@ -129,7 +130,7 @@ def test_both_endings_for_every_xdrop_and_sharp_boundary_triples(c):
 
 
 def test_bias_and_xdrop_change_segments(c):
-    plain, biased = xc.reference(c, xc.DEFAULT_XDROP, False), xc.reference(c, xc.DEFAULT_XDROP, True)
+    plain, biased = xc.reference(c, c.default_xdrop, False), xc.reference(c, c.default_xdrop, True)
     assert int((plain != biased).any(axis=1).sum()) >= 100
     narrow = xc.reference(c, 7, False)
     assert int((plain != narrow).any(axis=1).sum()) >= 100
@@ -151,7 +152,7 @@ def test_letters_of_the_corpus(c):
 
 
 def test_every_tie_has_a_later_equal_maximum_left_alone(c):
-    ref = xc.reference(c, xc.DEFAULT_XDROP, False)
+    ref = xc.reference(c, c.default_xdrop, False)
     Md, q, _, t = c._plain[False]
     n = 0
     for k, i in enumerate(c.info):
@@ -169,3 +170,45 @@ def test_every_tie_has_a_later_equal_maximum_left_alone(c):
         assert max(sums + [0]) == score and any(s == score for s in sums[reach:]), (c.tags[k], sums, reach, score)
         n += 1
     assert n == len([i for i in c.info if i[0] == "tie"]) >= 600
+
+
+# ---- the corpus on other matrices --------------------------------------------------------------------------------------------------
+
+@pytest.fixture(scope="module", params=ss.XDROP, ids=ss.scheme_id)
+def sc(request):
+    return xc.corpus(ss.params(request.param))
+
+
+def test_scheme_corpus_is_built_around_its_own_default(sc):
+    want = int(np.ceil((12.3 * np.log(2.0) + np.log(sc.params.K)) / sc.params.lambda_))
+    assert sc.default_xdrop == want != xc.DEFAULT_XDROP and want in sc.xdrops and set(xc.XDROPS) <= set(sc.xdrops)
+    assert sc is not xc.corpus() and not np.array_equal(sc.M, xc.corpus().M) and sc is xc.corpus(sc.params)
+    assert len(sc.tie_ks) == 4 and all(k in sc.M[:20, :20] and -k in sc.M[:20, :20] for k in sc.tie_ks)
+    assert {i[3] for i in sc.info if i[0] == "tie"} == set(sc.tie_ks)
+    assert {i[2] for i in sc.info if i[0] == "boundary"} == set(sc.xdrops[:-1])
+
+
+@pytest.mark.parametrize("use_bias", [False, True])
+def test_scheme_shared_walk_equals_the_reference_function(sc, use_bias):
+    for xdrop in sc.xdrops:
+        test_shared_walk_equals_the_reference_function(sc, xdrop, use_bias)
+
+
+def test_scheme_corpus_properties(sc):
+    """every property of the BLOSUM62 corpus, from the reference function on this matrix"""
+    test_corpus_size_and_order(sc)
+    test_every_cell_of_the_delimiter_grid_in_both_directions(sc)
+    test_walks_cross_one_two_and_three_chunks(sc)
+    test_corners_and_delimiter_subjects(sc)
+    test_bias_and_xdrop_change_segments(sc)
+    test_letters_of_the_corpus(sc)
+    test_every_tie_has_a_later_equal_maximum_left_alone(sc)
+
+
+def test_scheme_both_endings_and_sharp_boundary_triples(sc):
+    test_both_endings_for_every_xdrop_and_sharp_boundary_triples(sc)
+    # the default differs from its neighbours on the triples built around it: xdrop = 0 read as 20, or as one more or less, shows
+    x = sc.default_xdrop
+    at = np.array([i[0] == "boundary" and i[2] == x for i in sc.info])
+    for other in (x - 1, x + 1, xc.DEFAULT_XDROP):
+        assert int((xc.reference(sc, x, False)[at] != xc.reference(sc, other, False)[at]).any(axis=1).sum()) >= 100, other

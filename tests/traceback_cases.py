@@ -2,8 +2,10 @@
 items laid at the places where traceback_walk_wave (csrc/swipe_kernels.hip) can leave the serial walk traceback_walk (swipe_core.h)
 -- it scores 64 diagonal steps per round trip, ends a run by a ballot, applies the stop rule `sc < best` by a wave prefix sum, cuts
 insertion counts at 63, writes deletions in a lane-strided loop and moves the transcript 64 bytes per pass. Letters 0 - 19 unless
-said otherwise, BLOSUM62 with gap open 11 / extend 1 (the context's matrix, hip.matrix_of), records in the shape pack_records /
-pack_records_m take. Diagonals are query position - target position: extra letters in the query are an insertion (towards +G).
+said otherwise, the context's matrix (hip.matrix_of) and gap costs, records in the shape pack_records / pack_records_m take.
+corpus() is built for BLOSUM62 with gap open 11 / extend 1; corpus(scheme), scheme = (matrix name, gap open, gap extend), rebuilds
+the families for another scoring system (see "Other scoring systems" below). Diagonals are query position - target position: extra
+letters in the query are an insertion (towards +G).
 
 Every record carries rec["tag"] = family/.../variant/band class and rec["info"], a dict with "family", "variant" and the property
 the case is meant to have (test_traceback_cases.py asserts it from the oracle):
@@ -25,7 +27,25 @@ the case is meant to have (test_traceback_cases.py asserts it from the oracle):
 
 Variants: "plain"; "bias" (gap and run again with a random bias of -3 .. +1 per query letter); "own" (again with a perturbed
 matrix of the item's own and no bias: such items are swept by the 32-bit kernels). Every case is present once per band class
-(widths of up to 96 / 128 / 160 / 256 / 512) that can hold its diagonals, the band widened around the case inside the matrix."""
+(widths of up to 96 / 128 / 160 / 256 / 512) that can hold its diagonals, the band widened around the case inside the matrix.
+
+Other scoring systems. What the families above take from BLOSUM62 11/1 comes from the scheme's own numbers instead (_Costs):
+ * flanks are as long as it takes for a flank of identical pairs to score twice the case's largest gap cost, go + G ge, with a
+   bias of -1 per letter allowed for (and never shorter than for BLOSUM62); the builder asserts 1.3 times the cost per flank;
+ * W and D become the letter pair with the matrix's lowest score (x : y), "adjacent" takes 3 go / (|x : y| - 2 ge) letters of each
+   (30 at least), so that two gaps beat the mismatch columns by a margin that grows with the run;
+ * run letters have a diagonal entry of 4 or more, so a column stays positive under a bias of -3 and a perturbation of -2;
+ * the four flank letters on either side of a gap are the four letters with the largest diagonal entries, and the letters inside
+   a gap are taken from the other sixteen. A gap then cannot slide along a repeated letter, and under a cheap gap open with a
+   bias (PAM30 5/2: a bias difference of 4 on two letters outweighs an open of 5) it cannot split in two around letters that
+   pair with the flank's end as well as the flank's own;
+ * the "zero" prefix is found by search: the matrix's W:W, then up to four pairs with negative scores whose running sum stays
+   positive and ends at exactly 0. A matrix without such a prefix of five pairs or fewer gets no run/zero cases (all eight
+   standard matrices have one);
+ * "letters" faces each target letter 20 - 24 with the query letter it scores best against; a letter whose best score is still
+   below two one-letter gaps, -2 (go + ge), cannot stand in a column (PAM30 5/2: the stop, -17 against -14) and is then only
+   present inside the deletion. Corpus.letter_columns lists the letters that can.
+A scheme whose lowest score does not exceed two gap extensions has no "adjacent" case and is refused (BLOSUM50 9/3)."""
 import functools
 
 import numpy as np
@@ -44,6 +64,69 @@ ZERO_PREFIX = ((W, W), (W, D), (W, D), (A, R), (G_, W))    # (query, target): +1
 GAP_OPEN, GAP_EXTEND = 11, 1
 
 
+class _Costs:
+    """What the families take from the scoring system. scheme None: BLOSUM62 11/1 with the constants above."""
+
+    def __init__(self, M, scheme):
+        self.scheme, self.M = scheme, M
+        if scheme is None:
+            self.go, self.ge = GAP_OPEN, GAP_EXTEND
+            self.x, self.y, self.zero_prefix, self.adj_gap = W, D, ZERO_PREFIX, ADJ_GAP
+            self.solid, self.letter_columns = np.arange(20, dtype=np.int8), (20, 21, 22, 23, 24)
+            return
+        _, self.go, self.ge = scheme
+        m = M[:20, :20].astype(int)
+        self.x, self.y = (int(v) for v in np.unravel_index(m.argmin(), m.shape))
+        low = -int(m[self.x, self.y])
+        assert low > 2 * self.ge, scheme
+        self.adj_gap = max(ADJ_GAP, -(-3 * self.go // (low - 2 * self.ge)))
+        self.solid = np.array([a for a in range(20) if m[a, a] >= 4], np.int8)
+        order = np.argsort(-np.diag(m), kind="stable")
+        self.junction, self.filler = order[:4].astype(np.int8), np.sort(order[4:]).astype(np.int8)
+        self.mean_diag = float(np.diag(m).mean())
+        self.zero_prefix = self._find_zero_prefix(m)
+        self.best_against = {L: int(M[L, :20].astype(int).argmax()) for L in range(20, 25)}                 # query letter per target letter
+        self.letter_columns = tuple(L for L in range(20, 25) if int(M[L, self.best_against[L]]) > -2 * (self.go + self.ge))
+
+    def gap_cost(self, G):
+        return self.go + G * self.ge
+
+    def flank(self, cost, least):
+        """letters per flank around gaps that cost `cost` together"""
+        if self.scheme is None:
+            return least
+        return max(least, int(-(-2 * cost // (self.mean_diag - 1))))
+
+    def check_flank(self, letters, cost):
+        if self.scheme is not None:
+            score = int(sum(int(self.M[a, a]) for a in letters)) - len(letters)
+            assert score >= 1.3 * cost, (self.scheme, score, cost)
+
+    @staticmethod
+    def _find_zero_prefix(m):
+        """((query, target), ...): W:W, then pairs of negative scores, the running sum positive until it ends at 0; five pairs at most"""
+        by_score = {}
+        for a in range(20):
+            for b in range(20):
+                if m[a, b] < 0 and W not in (a, b):             # (a second W could pair with the first column's)
+                    by_score.setdefault(int(m[a, b]), (a, b))
+
+        def search(left, room):
+            if left == 0:
+                return []
+            if room == 0:
+                return None
+            for sc in sorted(by_score):                    # the large losses first: short prefixes
+                if -sc <= left:
+                    rest = search(left + sc, room - 1)
+                    if rest is not None:
+                        return [by_score[sc]] + rest
+            return None
+
+        rest = search(int(m[W, W]), 4)
+        return None if rest is None else ((W, W),) + tuple(rest)
+
+
 def width_class(width):
     """The narrowest of CLASS_WIDTHS that takes a band of `width` diagonals (None: wider than all of them)"""
     for w in CLASS_WIDTHS:
@@ -53,10 +136,31 @@ def width_class(width):
 
 
 class _Builder:
-    def __init__(self, M, seed):
+    def __init__(self, M, seed, costs):
         self.M = M
+        self.c = costs
         self.rng = np.random.default_rng(seed)
         self.recs = []
+
+    def gap_letters(self, n):
+        """the letters inside a gap"""
+        if self.c.scheme is None:
+            return self.letters(n)
+        return self.c.filler[self.rng.integers(0, len(self.c.filler), int(n))]
+
+    def flank_letters(self, n, left=False, right=False):
+        """a flank; left / right: a gap lies on that side"""
+        a = self.letters(n)
+        if self.c.scheme is not None:
+            if left:
+                a[:4] = self.c.junction[self.rng.integers(0, 4, min(4, len(a)))][:len(a[:4])]
+            if right:
+                a[-4:] = self.c.junction[self.rng.integers(0, 4, min(4, len(a)))][:len(a[-4:])]
+        return a
+
+    def run_letters(self, n):
+        """letters whose identical pair stays positive under any bias and perturbation the variants apply"""
+        return self.c.solid[self.rng.integers(0, len(self.c.solid), int(n))]
 
     def letters(self, n):
         return self.rng.integers(0, 20, int(n)).astype(np.int8)
@@ -66,7 +170,7 @@ class _Builder:
         keep their scores"""
         m = self.M.copy()
         m[:24, :24] = np.clip(m[:24, :24].astype(int) + self.rng.integers(-2, 3, (24, 24)), -128, 127).astype(np.int8)
-        for a, b in ZERO_PREFIX:
+        for a, b in self.c.zero_prefix or ():
             m[a, b], m[b, a] = self.M[a, b], self.M[b, a]
         return m
 
@@ -102,33 +206,38 @@ class _Builder:
 
     # ---- families ----------------------------------------------------------------------------------------------------------
     def gap_pair(self, G, direction, flank):
-        a, b, x = self.letters(flank), self.letters(flank), self.letters(G)
+        a, b, x = self.flank_letters(flank, right=True), self.flank_letters(flank, left=True), self.gap_letters(G)
+        self.c.check_flank(a, self.c.gap_cost(G))
+        self.c.check_flank(b, self.c.gap_cost(G))
         longer, shorter = np.concatenate([a, x, b]), np.concatenate([a, b])
         return (longer, shorter, -8, G + 9) if direction == "ins" else (shorter, longer, -G - 8, 9)
 
     def gaps(self):
         for G in GAPS:
             for direction in ("ins", "del"):
-                q, t, lo, hi = self.gap_pair(G, direction, FLANK)
+                q, t, lo, hi = self.gap_pair(G, direction, self.c.flank(self.c.gap_cost(G), FLANK))
                 self.per_class(q, t, lo, hi, {"family": "gap", "dir": direction, "G": G}, ("plain", "bias", "own"))
 
     def runs(self):
         for N in RUNS:
-            x = self.letters(N)
+            x = self.run_letters(N)
             for form in ("origin", "score", "zero"):
                 if form == "origin":
                     pq, pt = [], []
                 elif form == "score":
-                    pq, pt = [W] * 7, [D] * 7
+                    pq, pt = [self.c.x] * 7, [self.c.y] * 7
+                elif self.c.zero_prefix is None:
+                    continue
                 else:
-                    pq, pt = [p[0] for p in ZERO_PREFIX], [p[1] for p in ZERO_PREFIX]
+                    pq, pt = [p[0] for p in self.c.zero_prefix], [p[1] for p in self.c.zero_prefix]
                 q, t = np.concatenate([np.array(pq, np.int8), x]), np.concatenate([np.array(pt, np.int8), x])
                 self.per_class(q, t, 0, 1, {"family": "run", "form": form, "N": N}, ("plain", "bias", "own"), bias_free=len(pq))
 
     def between(self):
         for r in BETWEEN:
             for order in ("ID", "DI"):
-                a, b, c, x, y = self.letters(r), self.letters(r), self.letters(r), self.letters(5), self.letters(5)
+                a, b, c = self.flank_letters(r, right=True), self.flank_letters(r, True, True), self.flank_letters(r, left=True)
+                x, y = self.gap_letters(5), self.gap_letters(5)
                 if order == "ID":                                    # M r . I5 . M r . D5 . M r
                     q, t, lo, hi = np.concatenate([a, x, b, c]), np.concatenate([a, b, y, c]), -8, 14
                 else:
@@ -137,15 +246,18 @@ class _Builder:
 
     def adjacent_pair(self, flank):
         a, b = self.letters(flank), self.letters(flank)
-        a[-1] = b[0] = A                     # (a W or D next to the run could pair with the run's first or last letter between the gaps)
-        return np.concatenate([a, np.full(ADJ_GAP, W, np.int8), b]), np.concatenate([a, np.full(ADJ_GAP, D, np.int8), b])
+        n, x, y = self.c.adj_gap, self.c.x, self.c.y
+        a[-1] = b[0] = [k for k in (A, R, G_) if k not in (x, y)][0]      # (a W or D next to the run could pair with the run's first or last letter between the gaps)
+        self.c.check_flank(a, 2 * self.c.gap_cost(n))
+        self.c.check_flank(b, 2 * self.c.gap_cost(n))
+        return np.concatenate([a, np.full(n, x, np.int8), b]), np.concatenate([a, np.full(n, y, np.int8), b])
 
     def adjacent(self):
         for order in ("WD", "DW"):
-            q, t = self.adjacent_pair(ADJ_FLANK)
+            q, t = self.adjacent_pair(self.c.flank(2 * self.c.gap_cost(self.c.adj_gap), ADJ_FLANK))
             if order == "DW":
                 q, t = t, q
-            self.per_class(q, t, -ADJ_GAP - 8, ADJ_GAP + 9, {"family": "adjacent", "order": order})
+            self.per_class(q, t, -self.c.adj_gap - 8, self.c.adj_gap + 9, {"family": "adjacent", "order": order})
 
     def letter_cases(self):
         positive = [(a, b) for a in range(20) for b in range(20) if a != b and self.M[a, b] > 0]
@@ -155,6 +267,8 @@ class _Builder:
             for k, p in enumerate(range(6, 144, 6)):
                 if k % 2 == 0:
                     t[p] = 20 + (k // 2) % 5                             # B J Z X * in the target: the substitution byte carries it
+                    if self.c.scheme is not None:
+                        q[p] = self.c.best_against[int(t[p])]
                 else:
                     q[p], t[p] = positive[int(self.rng.integers(0, len(positive)))]
             lo, hi = -8, 9
@@ -178,16 +292,16 @@ class _Builder:
         for k, band in enumerate(WIDE_BANDS):
             direction = ("ins", "del")[k % 2]
             flank = -(-(band - 199) // 4) + 8                        # 4 flank + 199 diagonals >= band
-            q, t, lo, hi = self.gap_pair(200, direction, flank)
+            q, t, lo, hi = self.gap_pair(200, direction, self.c.flank(self.c.gap_cost(200), flank))
             d0 = -(len(t) - 1) + (len(q) + len(t) - 1 - band) // 2
             assert d0 <= lo and hi <= d0 + band
             self.put(q, t, lo, hi, {"family": "wide", "kind": "gap", "dir": direction, "G": 200, "variant": "plain"}, None, None, d0, d0 + band, band)
             flank = -(-(band - 2 * ADJ_GAP + 1) // 4) + 8
-            q, t = self.adjacent_pair(flank)
+            q, t = self.adjacent_pair(self.c.flank(2 * self.c.gap_cost(self.c.adj_gap), flank))
             if k % 2:
                 q, t = t, q
             d0 = -(len(t) - 1) + (len(q) + len(t) - 1 - band) // 2
-            self.put(q, t, -ADJ_GAP - 8, ADJ_GAP + 9, {"family": "wide", "kind": "adjacent", "order": ("WD", "DW")[k % 2], "variant": "plain"}, None, None, d0, d0 + band, band)
+            self.put(q, t, -self.c.adj_gap - 8, self.c.adj_gap + 9, {"family": "wide", "kind": "adjacent", "order": ("WD", "DW")[k % 2], "variant": "plain"}, None, None, d0, d0 + band, band)
 
     def neighbours(self, every=9):
         """items of score 0 and 1 x 1 items between the others"""
@@ -198,7 +312,7 @@ class _Builder:
             if n % every == every - 1:
                 if k % 2 == 0:
                     n_q, n_t = int(self.rng.integers(1, 90)), int(self.rng.integers(1, 90))
-                    self.put(np.full(n_q, W, np.int8), np.full(n_t, D, np.int8), -(n_t - 1), n_q, {"family": "zero", "kind": "WxD", "n": k, "variant": "plain"},
+                    self.put(np.full(n_q, self.c.x, np.int8), np.full(n_t, self.c.y, np.int8), -(n_t - 1), n_q, {"family": "zero", "kind": "WxD", "n": k, "variant": "plain"},
                              cbs=None if k % 4 else np.zeros(n_q, np.int8), klass=width_class(n_q + n_t - 1))
                 else:
                     x = self.letters(1)
@@ -210,7 +324,8 @@ class _Builder:
 
 class Corpus:
     """recs: the records in construction order (a long case next to short neighbours); shuffled: a permutation of them; M: the
-    context's matrix; params."""
+    context's matrix; params; scheme (None: BLOSUM62 11/1), gap_open, gap_extend; what the families took from the scheme: adj_gap,
+    zero_prefix (None: no run/zero cases), low_pair (the letters that stand for W and D), letter_columns."""
 
     def matrix_of(self, rec):
         m = rec["targets"][0]["matrix"]
@@ -227,11 +342,18 @@ class Corpus:
         return [k for k, r in enumerate(self.recs) if all(r["info"].get(a) == b for a, b in want.items())]
 
 
+def corpus(scheme=None):
+    """The corpus under BLOSUM62 11/1, or rebuilt for scheme = (matrix name, gap open, gap extend); one object per scheme"""
+    return _corpus_cached(None if scheme is None else tuple(scheme))
+
+
 @functools.lru_cache(maxsize=None)
-def corpus():
-    params = hip.default_params()
+def _corpus_cached(scheme):
+    params = hip.default_params() if scheme is None else hip.matrix_params(*scheme)
     M = hip.matrix_of(params)
-    b = _Builder(M, 6364)
+    costs = _Costs(M, scheme)
+    assert (params.gap_open, params.gap_extend) == (costs.go, costs.ge)
+    b = _Builder(M, 6364, costs)
     b.gaps()
     b.runs()
     b.between()
@@ -242,21 +364,23 @@ def corpus():
     b.neighbours()
     c = Corpus()
     c.params, c.M, c.recs = params, M, b.recs
+    c.scheme, c.gap_open, c.gap_extend = scheme, costs.go, costs.ge
+    c.adj_gap, c.zero_prefix, c.low_pair, c.letter_columns = costs.adj_gap, costs.zero_prefix, (costs.x, costs.y), costs.letter_columns
     c.shuffled = np.random.default_rng(99).permutation(len(c.recs))
     return c
 
 
 @functools.lru_cache(maxsize=None)
-def _oracle_cached():
+def _oracle_cached(scheme):
     import oracle_py as orc
-    c = corpus()
+    c = corpus(scheme)
     out = []
     for rec in c.recs:
         t = rec["targets"][0]
         m = c.matrix_of(rec)
-        rc, o, tr = orc.banded_swipe(rec["query"], rec["cbs"], t["seq"], t["d_begin"], t["d_end"], m, GAP_OPEN, GAP_EXTEND, orc.TRACEBACK)
+        rc, o, tr = orc.banded_swipe(rec["query"], rec["cbs"], t["seq"], t["d_begin"], t["d_end"], m, c.gap_open, c.gap_extend, orc.TRACEBACK)
         assert rc == 0, rec["tag"]
-        rc, st = orc.swipe_stats(rec["query"], rec["cbs"], t["seq"], t["d_begin"], t["d_end"], m, GAP_OPEN, GAP_EXTEND, 510)
+        rc, st = orc.swipe_stats(rec["query"], rec["cbs"], t["seq"], t["d_begin"], t["d_end"], m, c.gap_open, c.gap_extend, 510)
         assert rc == 0, rec["tag"]
         tr.setflags(write=False)
         out.append((o, tr, st))
@@ -265,8 +389,8 @@ def _oracle_cached():
 
 def oracle(c):
     """(hsp dict, transcript bytes, statistics dict) of oracle/banded_swipe.c for every record, computed once"""
-    assert c is corpus()
-    return _oracle_cached()
+    assert c is corpus(c.scheme)
+    return _oracle_cached(c.scheme)
 
 
 def gap_runs(tr):

@@ -1,7 +1,11 @@
 """Test data of the x-drop edge tests (tests/test_xdrop_cases.py, tests/test_gpu_xdrop_edges.py): one seeded block pair and a list
 of seed hits laid at the places where xdrop_seg_kernel (csrc/bias_kernels.hip) can leave the per-letter walk of xdrop_core.h -- it
 fetches sixteen letters at a time in either direction and leans on the blocks' 256-byte perimeter. Letter pairs are chosen from a
-wanted score series with the context's matrix (BLOSUM62), so every family is exact by construction and not by luck.
+wanted score series with the context's matrix, so every family is exact by construction and not by luck. corpus() is built on
+BLOSUM62 11/1; corpus(params) builds the same families on another system's matrix (hip.matrix_params): where that matrix has no
+letter pair of a wanted score the nearest score it has stands in (the larger of two equally near ones: PAM30 has no 3, 4, 5, its
+strong matches score 6), the ties use the four smallest k for which it has both -k and +k (PAM30: 1, 2, 6, 7), and the boundary
+family is built once more around the system's own x-drop default, Corpus.default_xdrop = ceil((12.3 ln 2 + ln K) / lambda).
 
 A hit's family is the first word of its tag; Corpus.info holds the same as a tuple.
 
@@ -21,6 +25,7 @@ A hit's family is the first word of its tag; Corpus.info holds the same as a tup
            of the letters, with B J Z X * in both sequences, and with a low-complexity query (first half one residue).
 """
 import functools
+import math
 
 import numpy as np
 
@@ -34,6 +39,11 @@ OFFSETS = (0, 1, 14, 15, 16, 17)
 LAUNCH_SIZES = (1, 255, 256, 257)
 CORNER_LEN = 48
 GRID_VARIANTS, BOUNDARY_VARIANTS, TIE_VARIANTS, HOMOLOG_PAIRS, SEEDS_PER_PAIR = 6, 80, 2, 400, 12
+
+
+def default_xdrop(params):
+    """config.raw_ungapped_xdrop: the raw score of 12.3 bits, what xdrop = 0 means"""
+    return int(math.ceil((12.3 * math.log(2.0) + math.log(params.K)) / params.lambda_))
 
 
 def _reference_xdrop(M, q, cbs, t, qa, sa, xdrop):
@@ -89,7 +99,8 @@ def diagonal_sums(M, q, t, qa, sa, direction, start=0):
 
 class Corpus:
     """qd, ql, td, tl: the two blocks (workload.sequence_set); hits: SEED_HIT_DTYPE; tags / info: one per hit; cbs: the host's
-    Hauser bias of the query block (hip.extend_plan); M: the matrix; params."""
+    Hauser bias of the query block (hip.extend_plan); M: the matrix; params; default_xdrop: what xdrop = 0 means under params;
+    xdrops: XDROPS and default_xdrop, the values the boundary family is built around and the tests run; tie_ks."""
 
     def qa(self, k):
         return int(self.ql[self.hits["query"][k]]) + int(self.hits["seed_offset"][k])
@@ -104,14 +115,20 @@ class Corpus:
 
 
 class _Builder:
-    def __init__(self, M, seed):
+    def __init__(self, M, seed, boundary_xdrops):
         self.M = M
         self.rng = np.random.default_rng(seed)
         self.qs, self.ts, self.rows, self.tags, self.info = [], [], [], [], []
+        self.boundary_xdrops = boundary_xdrops
         self.by_score = {}
         for a in range(20):
             for b in range(20):
                 self.by_score.setdefault(int(M[a, b]), []).append((a, b))
+        have = sorted(self.by_score)
+        # a wanted score the matrix does not have: the nearest it has, of two equally near ones the larger in magnitude
+        self.nearest = {s: s if s in self.by_score else min(have, key=lambda c: (abs(c - s), -abs(c))) for s in range(-8, 9)}
+        self.tie_ks = tuple(k for k in range(1, 20) if k in self.by_score and -k in self.by_score)[:4]
+        assert len(self.tie_ks) == 4 and all(self.nearest[s] * s > 0 for s in (-4, -3, 4, 5, 6)) and all(-y in self.by_score for y in range(5))
 
     def letters(self, n):
         return self.rng.integers(0, 20, int(n)).astype(np.int8)
@@ -120,7 +137,7 @@ class _Builder:
         """Query and target letters whose pairwise scores are `scores`."""
         q, t = np.zeros(len(scores), np.int8), np.zeros(len(scores), np.int8)
         for k, s in enumerate(scores):
-            c = self.by_score[int(s)]
+            c = self.by_score[self.nearest.get(int(s), int(s))]
             q[k], t[k] = c[int(self.rng.integers(0, len(c)))]
         return q, t
 
@@ -192,7 +209,7 @@ class _Builder:
     def boundary(self):
         for v in range(BOUNDARY_VARIANTS):
             for direction in ("left", "right"):
-                for x in XDROPS[:-1]:
+                for x in self.boundary_xdrops:
                     for o in OFFSETS:
                         for d in (-1, 0, 1):
                             s, w = self.boundary_series(x, d, o)
@@ -209,7 +226,7 @@ class _Builder:
         for v in range(TIE_VARIANTS):
             for direction in ("left", "right"):
                 for L in range(0, 21):
-                    for k in (1, 2, 3, 4):
+                    for k in self.tie_ks:
                         for end in ("delimiter", "loss"):
                             s = self.strong(L) + [-k, k] + ([] if end == "delimiter" else [-4, -4, -3, -4, -4, -4])
                             wq, wt = self.series(s)
@@ -273,11 +290,19 @@ class _Builder:
         self.hit(qx, 20, tx, 20, ("delim", "walks", "run", "run"))
 
 
+def corpus(params=None):
+    """The corpus on BLOSUM62 11/1, or on the matrix of `params` (hip.matrix_params); one object per system"""
+    return _corpus_cached(None if params is None else bytes(params))
+
+
 @functools.lru_cache(maxsize=None)
-def corpus():
-    params = hip.default_params()
+def _corpus_cached(key):
+    params = hip.default_params() if key is None else hip.Params.from_buffer_copy(key)
     M = hip.matrix_of(params)
-    b = _Builder(M, 20240)
+    x0 = default_xdrop(params)
+    assert key is not None or x0 == DEFAULT_XDROP
+    xdrops = XDROPS if x0 in XDROPS else tuple(sorted(XDROPS + (x0,)))
+    b = _Builder(M, 20240, xdrops[:-1])
     S = b.letters(CORNER_LEN)
     first = b.add(S, S)
     b.grid()
@@ -299,7 +324,8 @@ def corpus():
         return workload.sequence_set(np.concatenate(seqs).astype(np.int8), off)
 
     c = Corpus()
-    c.params, c.M = params, M
+    c.params, c.M, c.key = params, M, key
+    c.default_xdrop, c.xdrops, c.tie_ks = x0, xdrops, b.tie_ks
     c.qd, c.ql = block(qs)
     c.td, c.tl = block(ts)
     hits = np.zeros(len(b.rows), dtype=hip.SEED_HIT_DTYPE)
@@ -314,8 +340,8 @@ def corpus():
 
 
 @functools.lru_cache(maxsize=None)
-def _reference_cached(xdrop, use_bias):
-    c = corpus()
+def _reference_cached(key, xdrop, use_bias):
+    c = _corpus_cached(key)
     Md, q, cbs, t = c._plain[bool(use_bias)]
     out = np.zeros((len(c.hits), 3), np.int64)
     qa = c.ql[c.hits["query"]] + c.hits["seed_offset"]
@@ -327,8 +353,8 @@ def _reference_cached(xdrop, use_bias):
 
 def reference(c, xdrop, use_bias):
     """(delta, len, score) of _reference_xdrop for every hit of the corpus, computed once per setting"""
-    assert c is corpus()
-    return _reference_cached(int(xdrop), bool(use_bias))
+    assert c is _corpus_cached(c.key)
+    return _reference_cached(c.key, int(xdrop), bool(use_bias))
 
 
 def family_counts(c):

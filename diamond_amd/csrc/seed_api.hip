@@ -380,7 +380,8 @@ static SeedSizes seed_sizes(const dmnd_ctx* c, const SeedParams& sp, int64_t nq_
 	// 3 MB and three bits per seed. Measured on C2 (3e6 query seeds): the stream kernel takes the same
 	// 1.45 ms as with 2 MB / two bits -- its bound is the rate at which the L2s serve 4-byte probes, not the misses behind
 	// them -- but the false positives drop from 9.7 % to 3.1 %, and with them the level-2 / table lines fetched over the fabric
-	// (4 MB: 1.53 ms, 8 MB: 2.56 ms -- the filter has to fit an XCD's 4 MB L2 beside the stream)
+	// (4 MB: 1.53 ms, 8 MB: 2.56 ms -- the PLAIN stream's filter has to fit an XCD's 4 MB L2 beside the stream. The sliced stream
+	// probes from LDS and is not bound by L2: a search that takes it sizes its filter by seed_sizes_sliced below.)
 	const bool long_seeds = !seed_stream_can_fuse(sp);
 	if (long_seeds && bm1_log2 == 24 && bm_words >= 3 * bm1_words / 2) {
 		bm1_words = 3 * bm1_words / 2;
@@ -406,11 +407,28 @@ static SeedSizes seed_sizes(const dmnd_ctx* c, const SeedParams& sp, int64_t nq_
 	return z;
 }
 
+// The geometry of the same search on the sliced stream (seed_slices_filter_words: a level-1 filter sized for LDS slices, not for L2),
+// or z itself where the search keeps seed_sizes' filter on either stream: the fused pipeline, hashed seeds, a query block above
+// 2^24 positions (seed_sizes' own larger filters, probed by key class), a kept query index (one index serves reference blocks that
+// may take different streams), a size that finds no slice count. slice_words / forced_words: SeedHooks.
+static SeedSizes seed_sizes_sliced(const dmnd_ctx* c, const SeedParams& sp, int64_t nq_pos, const SeedSizes& z, uint32_t slice_words, uint64_t forced_words)
+{
+	if (z.fused || seed_stream_can_fuse(sp) || sp.seed_encoding != SEED_SPACED || nq_pos > ((int64_t)1 << 24) || c->reuse_query_index) return z;
+	int slot_bits = 0;
+	while (((uint64_t)1 << slot_bits) < z.slots) ++slot_bits;
+	SeedSizes s = z;
+	s.bm1_words = seed_slices_filter_words((uint64_t)nq_pos, slot_bits, z.bm_words, z.bm1_words, slice_words, forced_words, &s.bm1_k3);
+	s.bm_total = (size_t)s.SB * (s.bm_words + s.bm1_words) * sizeof(uint32_t);
+	return s;
+}
+
 // The buffers a search of this geometry needs before its first kernel. generous: also the buffers whose size depends on what the
 // search finds, at their starting capacities (dmnd_seed_reserve; the search itself grows them where they overflow)
-static int seed_reserve(dmnd_ctx* c, const SeedParams& sp, const SeedSizes& z, int64_t nq_pos, int64_t q_end, int64_t q_block_len, bool generous)
+// bitmap_bytes: the filters of the geometry or of its sliced form (seed_sizes_sliced), whichever are larger -- the searches of one
+// reference block take either
+static int seed_reserve(dmnd_ctx* c, const SeedParams& sp, const SeedSizes& z, size_t bitmap_bytes, int64_t nq_pos, int64_t q_end, int64_t q_block_len, bool generous)
 {
-	if (int rc = c->seed_bitmap.ensure(z.bm_total)) return rc;
+	if (int rc = c->seed_bitmap.ensure(std::max(z.bm_total, bitmap_bytes))) return rc;
 	{
 		const size_t held = c->qid_of.cap;
 		if (int rc = c->qid_of.ensure((size_t)q_end * sizeof(uint32_t))) return rc;
@@ -461,7 +479,9 @@ extern "C" int dmnd_seed_reserve(dmnd_ctx* c, const dmnd_seed_params* params, in
 	if (sp.n_shapes < 1 || sp.n_shapes > SEED_MAX_SHAPES) return fail(DMND_E_ARG, "dmnd_seed_reserve: unsupported seed configuration");
 	HIP_TRY(hipSetDevice(c->device));
 	const int64_t nq_pos = query_block_len - 512;             // a SequenceSet block: 256 padding letters on either side
-	return seed_reserve(c, sp, seed_sizes(c, sp, nq_pos), nq_pos, query_block_len - 256, query_block_len, true);
+	const SeedSizes z = seed_sizes(c, sp, nq_pos);
+	// (the per-call hooks of a search are not a reservation's: the search itself ensures what they ask for)
+	return seed_reserve(c, sp, z, seed_sizes_sliced(c, sp, nq_pos, z, SEED_SLICE_MAX_WORDS, 0).bm_total, nq_pos, query_block_len - 256, query_block_len, true);
 }
 
 namespace {
@@ -477,6 +497,8 @@ struct SeedHooks {
 	uint64_t slices_budget;           // DMND_SEED_SLICES_BUDGET_MB, in bytes, and ...
 	int64_t slices_min_letters;       // ... DMND_SEED_SLICES_MIN_LETTERS stand in for the tuning values
 	uint32_t slice_words;             // DMND_SEED_SLICE_WORDS: most words of a slice (tests: many slices of a small filter)
+	bool slices_alloc_fail;           // DMND_SEED_SLICES_ALLOC_FAIL: the reference cache's allocations count as failed (tests: the fallback to the plain stream)
+	uint64_t slices_filter_words;     // DMND_SEED_SLICES_FILTER_WORDS: words of the level-1 filter a sliced search builds (tests on small blocks, size sweeps; 0: seed_slices_filter_words' rule)
 	int64_t matched_cap, survivor_cap, hit_cap, deferred_cap;      // DMND_SEED_MATCHED_CAP, _SURVIVOR_CAP, _HIT_CAP, _DEFERRED_CAP force the overflow / retry paths: the capacity a buffer starts from, instead of the one computed (0: unset; cap_or)
 	int64_t sort_cap, readback_bytes; // the chain's two sizes: the tuning values (csrc/tuning.h), or what DMND_SEED_SORT_CAP / DMND_SEED_READBACK_BYTES say
 };
@@ -492,6 +514,8 @@ SeedHooks seed_hooks()
 	h.slices_budget = (uint64_t)std::max<long long>(0, num("DMND_SEED_SLICES_BUDGET_MB", tuning().seed_slices_budget_mb)) << 20;
 	h.slices_min_letters = num("DMND_SEED_SLICES_MIN_LETTERS", tuning().seed_slices_min_letters);
 	h.slice_words = (uint32_t)std::min<long long>(SEED_SLICE_MAX_WORDS, std::max<long long>(64, num("DMND_SEED_SLICE_WORDS", SEED_SLICE_MAX_WORDS)));
+	h.slices_alloc_fail = forced("DMND_SEED_SLICES_ALLOC_FAIL") == 1;
+	h.slices_filter_words = (uint64_t)std::max<long long>(0, num("DMND_SEED_SLICES_FILTER_WORDS", 0));
 	h.matched_cap = cap("DMND_SEED_MATCHED_CAP"); h.survivor_cap = cap("DMND_SEED_SURVIVOR_CAP");
 	h.hit_cap = cap("DMND_SEED_HIT_CAP"); h.deferred_cap = cap("DMND_SEED_DEFERRED_CAP");
 	const int64_t sort_cap = cap("DMND_SEED_SORT_CAP");
@@ -510,7 +534,7 @@ struct PostState {
 // the hit list of the fused pipeline: every survivor gives at most one hit
 struct FusedHits { int64_t cap = 0, bound = 0; };
 
-// One search: what is fixed once it is set up (check_blocks, geometry, ref_cache), its running state, and its phases in their order
+// One search: what is fixed once it is set up (check_blocks, geometry, ref_decide, ref_cache), its running state, and its phases in their order
 struct SeedRun {
 	dmnd_ctx* c;
 	SeedHooks hooks;
@@ -518,7 +542,7 @@ struct SeedRun {
 	hipStream_t st;
 	int64_t q_begin = 0, q_end = 0, t_begin = 0, t_end = 0, nq_pos = 0, n_targets = 0;
 	int S = 0;
-	SeedSizes z;
+	SeedSizes z, z_sliced;            // the geometry in use; what it is (or would be) on the sliced stream (seed_sizes_sliced) -- z from ref_decide on
 	int slot_bits = 0, bm_log2 = 0;   // log2(slots): the sort key of the build (SeedArgs::order) and of the tiled filter's sort; log2 of the level-2 filter's words
 	size_t slot_bytes = 0;            // one shape's table
 	bool nibble_shapes = true, classes_long = false;
@@ -541,6 +565,7 @@ struct SeedRun {
 	SeedRun(dmnd_ctx* ctx, const SeedHooks& h) : c(ctx), hooks(h), st(ctx->stream), tm(ctx->stream) {}
 	int check_blocks();
 	int geometry();
+	void ref_decide();
 	int prepare();
 	int ref_cache();
 	int fused();
@@ -701,6 +726,7 @@ int SeedRun::geometry()
 	if (nq_pos >= 0xffffffffLL) return fail(DMND_E_ARG, "dmnd_seed_search: query block larger than 4G letters");
 	S = sp.n_shapes;
 	z = seed_sizes(c, sp, nq_pos);
+	z_sliced = seed_sizes_sliced(c, sp, nq_pos, z, hooks.slice_words, hooks.slices_filter_words);
 	if (z.slots > ((uint64_t)1 << 31)) return fail(DMND_E_ARG, "dmnd_seed_search: query block too large for 32-bit slot numbers (more than 1.7 G seed positions): cut it into smaller blocks");
 	slot_bytes = (size_t)z.slots << z.slot_shift;
 	while (((uint64_t)1 << slot_bits) < z.slots) ++slot_bits;
@@ -715,7 +741,7 @@ int SeedRun::geometry()
 	if (z.fused && !classes) return fail(DMND_E_ARG, "dmnd_seed_search: fused seed search without key classes (table or level-1 filter too small for eighths)");
 	if (z.reuse) {
 		signature.assign(reinterpret_cast<const char*>(&sp), sizeof(sp));
-		const uint64_t extra[7] = { c->query_generation, (uint64_t)nq_pos, z.slots, z.bm_words, z.bm1_words, (uint64_t)z.fused + 2 * (uint64_t)classes, (uint64_t)z.slot_shift * 2 + z.bm1_k3 };
+		const uint64_t extra[7] = { c->query_generation, (uint64_t)nq_pos, z.slots, z.bm_words, z.bm1_words, (uint64_t)z.fused + 2 * (uint64_t)classes, (uint64_t)z.slot_shift * 4 + z.bm1_k3 };
 		signature.append(reinterpret_cast<const char*>(extra), sizeof(extra));
 	}
 	index_ready = z.reuse && c->qindex_signature == signature && !signature.empty();
@@ -732,7 +758,7 @@ int SeedRun::geometry()
 // the buffers of the geometry, and everything a search starts from enqueued: the one clear, query windows, query ids, folds, codes
 int SeedRun::prepare()
 {
-	if (int rc = seed_reserve(c, sp, z, nq_pos, q_end, c->block_len[DMND_QUERY], false)) return rc;
+	if (int rc = seed_reserve(c, sp, z, z_sliced.bm_total, nq_pos, q_end, c->block_len[DMND_QUERY], false)) return rc;
 	if (lin_on) {                                       // (never cleared: the reduction initialises the slots it reads, seed_lin_first_kernel)
 		if (z.fused) return fail(DMND_E_ARG, "dmnd_seed_search: the linearised search has no form in the fused short-seed pipeline");
 		if (int rc = c->seed_lin_first.ensure((size_t)z.slots * sizeof(int64_t))) return rc;
@@ -787,11 +813,15 @@ int SeedRun::prepare()
 // The first search of a block generation takes the plain kernel and builds nothing (a block searched once pays nothing), the second
 // one with the same key builds, later ones keep. DMND_SEED_SLICES=0/1 forces never / always (always: built by the first search),
 // DMND_SEED_SLICES_BUDGET_MB and DMND_SEED_SLICES_MIN_LETTERS stand in for the tuning values (SeedHooks).
-// Decides (ref_use, slice_bits, ref_windows) and builds the reference-side cache where the decision is to build.
-int SeedRun::ref_cache()
+// ref_decide decides (ref_use, slice_bits, ref_windows) and with them the geometry, before anything is reserved or cleared for it:
+// a search on the sliced stream takes z_sliced, whose level-1 filter is sized for LDS slices (C2: 64 x 128 KB instead of 3 MB),
+// every other search seed_sizes' geometry. The cache's key holds the slice count of z_sliced whatever stream this search takes, so
+// that the plain first search of a block and the sliced ones behind it agree on it. ref_cache builds the reference-side cache
+// where the decision is to build.
+void SeedRun::ref_decide()
 {
 	ref_windows = seed_ref_windows(t_begin, t_end);
-	slice_bits = seed_slice_bits(z.bm1_words, slot_bits, hooks.slice_words);
+	slice_bits = seed_slice_bits(z_sliced.bm1_words, slot_bits, hooks.slice_words);
 	// The default rule takes the sliced stream where it was measured to win: a sparse level-1 filter -- at least four bits per query
 	// position, C2's 3 % positives: what the slices save is the probe that ends at level 1; C4's filter (1e7
 	// query seeds, a third of the probes positive) took 4.29 ms by slices against 3.52 -- and few joins in the context's last search
@@ -803,7 +833,13 @@ int SeedRun::ref_cache()
 	bool drop = false;
 	ref_use = seed_ref_decide(c->seed_ref, seed_ref_key_of(c->target_generation, tseed, t_begin, t_end, sp, slice_bits), hooks.slices, eligible, seed_ref_cache_bytes(t_begin, t_end, S) + seed_ref_hash_bytes(t_begin, t_end, S), hooks.slices_budget, &drop);
 	if (drop) c->release_seed_ref_buffers();            // (nothing on the stream reads them: the last search has been waited for; the state is seed_ref_decide's)
+	if (ref_use != SEED_REF_NONE) z = z_sliced;
+}
+
+int SeedRun::ref_cache()
+{
 	if (ref_use != SEED_REF_BUILT) return DMND_OK;
+	const int8_t* tseed = c->soft_valid[DMND_TARGET] ? c->soft[DMND_TARGET].as<int8_t>() : c->block[DMND_TARGET].as<int8_t>();
 	// class nibbles (kept), flags and routing bytes (scratch of the build), then per shape one radix pass into its lists.
 	// An allocation that fails leaves the search on the plain kernel.
 	const int64_t n_groups = seed_code_groups(t_begin, t_end);
@@ -816,7 +852,7 @@ int SeedRun::ref_cache()
 		b.cap = bytes;
 		return true;
 	};
-	const bool ok = exact(c->seed_ref_codes, (size_t)n_groups * sizeof(uint64_t)) && c->seed_tflags.ensure((size_t)n_groups * sizeof(uint32_t)) == DMND_OK
+	const bool ok = !hooks.slices_alloc_fail && exact(c->seed_ref_codes, (size_t)n_groups * sizeof(uint64_t)) && c->seed_tflags.ensure((size_t)n_groups * sizeof(uint32_t)) == DMND_OK
 		&& exact(c->seed_ref_lists, (size_t)S * (size_t)ref_windows * sizeof(uint32_t)) && exact(c->seed_ref_hashes, (size_t)S * (size_t)ref_windows * sizeof(uint32_t))
 		&& exact(c->seed_ref_counts, (size_t)S * 64 * sizeof(uint32_t))
 		&& exact(route[0], (size_t)ref_windows) && exact(route[1], (size_t)ref_windows);
@@ -835,7 +871,20 @@ int SeedRun::ref_cache()
 	}
 	route[0].release(); route[1].release();
 	seed_ref_built(c->seed_ref, ok);
-	if (!ok) { c->release_seed_ref(); ref_use = SEED_REF_NONE; }
+	if (!ok) {
+		// the plain stream after all, with its own geometry: the query side is not built yet. Where the geometry differs, the filters
+		// (reserved for either one) are cleared again where this one has them; where it is the same -- always with a kept query
+		// index, whose filters prepare() left as they are -- nothing is touched
+		c->release_seed_ref(); ref_use = SEED_REF_NONE;
+		const SeedSizes plain = seed_sizes(c, sp, nq_pos);
+		const bool moved = plain.bm1_words != z.bm1_words || plain.bm1_k3 != z.bm1_k3;
+		z = plain;
+		if (moved && !index_ready) {
+			SeedClear clr;
+			clr.add(c->seed_bitmap.p, z.bm_total, 0);
+			HIP_TRY(launch_seed_clear(clr, st));
+		}
+	}
 	lap("reference cache built");
 	return DMND_OK;
 }
@@ -1327,6 +1376,7 @@ extern "C" int dmnd_seed_search(dmnd_ctx* c, const dmnd_seed_params* params, int
 	r.nq_pos = r.q_end - r.q_begin; r.n_targets = (int64_t)tl.size() - 1;
 	if (r.nq_pos <= 0 || r.t_end <= r.t_begin) return DMND_OK;
 	if (int rc = r.geometry()) return rc;
+	r.ref_decide();
 	if (int rc = r.prepare()) return rc;
 	if (int rc = r.ref_cache()) return rc;
 	if (c->soft_valid[DMND_QUERY]) HIP_TRY(launch_seed_soft_time(r.args_for(0, 0, 0), r.st));

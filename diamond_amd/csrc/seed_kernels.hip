@@ -872,17 +872,20 @@ __global__ __launch_bounds__(256) void seed_stream_fast_kernel(SeedArgs a, int s
 // The plain stream sends one 4-byte level-1 probe per window to L2, each lane's its own request, and runs at the rate the L2s accept
 // requests. Here a workgroup loads ONE slice of the filter into LDS and walks the list of the windows whose keys fall into that
 // slice (the routing, built once per uploaded reference block: seed_route_kernel + one stable radix pass): the probe is an LDS read,
-// and what goes to L2 is a coalesced stream -- per window the list entry and hash a of the window's key (seed_ref_hash_kernel: without
-// key classes word and bits of the probe are functions of that hash alone), 16 bytes per lane and load each. The class nibbles are
-// gathered for the level-1 positives only, which need the key for level 2 and the table.
+// and what goes to L2 is a coalesced stream -- per window hash a of the window's key (seed_ref_hash_kernel: without key classes word
+// and bits of the probe are functions of that hash alone), 16 bytes per lane and load. List entry and class nibbles are read for the
+// level-1 positives only, which need the key for level 2 and the table: with the filter sized for the slices (seed_slices_filter_words,
+// C2: 8 MB, 0.6 % positives) a positive's line of the list costs less than the list as a second stream. A sliced
+// search that keeps seed_sizes' filter (a kept query index, a slice hook under which the larger size finds no slice count; C2's
+// 3 MB: 3.1 % positives) fetches the same bytes either way -- 1.2 GB less stream, 1.2 GB of on-demand lines -- and ran 0.699 against 0.696 ms.
 // Workgroup w serves slice w mod 2^b and the (w >> b)-th share of its list; no workgroup waits for another.
 // One workgroup of 16 wavefronts fits a CU beside the slice, so nothing in the loop may make a wavefront wait for the others: behind
 // the slice load there is no workgroup barrier (a barrier also drains the loads a wavefront has requested ahead). Every wavefront
 // keeps its own queue of level-1 positives and its own staging area in LDS, addressed with ballots instead of atomics:
-//  * list entries and hashes are requested SEED_SLICE_DEPTH rounds ahead of the round that is probed (C2's blocks, kernel alone: 0.709 ms
+//  * hashes are requested SEED_SLICE_DEPTH rounds ahead of the round that is probed (C2's blocks, kernel alone: 0.709 ms
 //    at 2 rounds, 0.696 at 4, 0.697 at 8);
-//  * level-1 positives (3.1 % of the windows with C2's 3 MB filter and three bits per seed, 9.7 % with 2 MB and two: seed_sizes) are queued by
-//    their window offsets, and 64 of them at a time form their keys from the nibbles and take the plain kernel's path -- level-2 bitmap,
+//  * level-1 positives (3.1 % of the windows with the plain stream's 3 MB filter, seed_sizes) are queued by their list
+//    indices, and 64 of them at a time read their list entries, form their keys from the nibbles and take the plain kernel's path -- level-2 bitmap,
 //    table, SLOT_JOINED -- with all lanes busy, instead of a chain of dependent reads in the few lanes that found one;
 //  * joins are staged and go out with one matched_count atomic per flush; direct append when the staging area is full.
 // Spaced seeds only (hashed seeds stay on the plain kernel: their windows with a mask / stop letter are keyed from the raw letters).
@@ -965,22 +968,19 @@ __global__ __launch_bounds__(SEED_SLICE_THREADS) void seed_stream_slices_kernel(
 	typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 	static_assert(B == 4, "one 16-byte load per round");
 	const uint64_t stride = (uint64_t)B * blockDim.x, first = (lo & ~(uint64_t)(B - 1)) + (uint64_t)B * threadIdx.x;
-	u32x4 hv[DEPTH], ov[DEPTH];
-	auto request = [&](uint64_t k, u32x4& h, u32x4& o) {
-		h = 0; o = 0;
-		if (k < hi) {
-			h = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(hashes + k));
-			o = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(list + k));
-		}
+	u32x4 hv[DEPTH];
+	auto request = [&](uint64_t k, u32x4& h) {
+		h = 0;
+		if (k < hi) h = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(hashes + k));
 	};
 #pragma unroll
-	for (int d = 0; d < DEPTH; ++d) request(first + (uint64_t)d * stride, hv[d], ov[d]);
+	for (int d = 0; d < DEPTH; ++d) request(first + (uint64_t)d * stride, hv[d]);
 	for (uint64_t k0 = first; k0 < hi + (uint64_t)B * threadIdx.x; k0 += (uint64_t)DEPTH * stride) {      // (workgroup-uniform trip count: k0 - B * threadIdx.x < hi)
 #pragma unroll
 		for (int d = 0; d < DEPTH; ++d) {
-			const u32x4 h4 = hv[d], o4 = ov[d];
+			const u32x4 h4 = hv[d];
 			const uint64_t k = k0 + (uint64_t)d * stride;
-			request(k + (uint64_t)DEPTH * stride, hv[d], ov[d]);
+			request(k + (uint64_t)DEPTH * stride, hv[d]);
 #pragma unroll
 			for (int j = 0; j < B; ++j) {
 				const uint32_t h = h4[j];
@@ -991,21 +991,21 @@ __global__ __launch_bounds__(SEED_SLICE_THREADS) void seed_stream_slices_kernel(
 				const bool pass = k + j >= lo && k + j < hi && (bw & need) == need;
 				const unsigned long long pb = __ballot(pass);
 				if (pb) {
-					if (pass) q_off[wave][qn + rank_in(pb)] = o4[j];
+					if (pass) q_off[wave][qn + rank_in(pb)] = (uint32_t)(k + j);      // (list index: the cache holds fewer than 2^31 windows)
 					qn += (unsigned)__builtin_popcountll(pb);
 					if (qn >= 64) {                                      // (wavefront-uniform)
 						wave_sync();
 						qn -= 64;
-						const uint32_t e = q_off[wave][qn + lane];
+						const uint32_t at = q_off[wave][qn + lane];
 						wave_sync();
-						probe_queued(true, e);
+						probe_queued(true, list[at]);
 					}
 				}
 			}
 		}
 	}
 	wave_sync();
-	probe_queued(lane < qn, lane < qn ? q_off[wave][lane] : 0u);
+	probe_queued(lane < qn, lane < qn ? list[q_off[wave][lane]] : 0u);
 	if (sn) flush();
 }
 

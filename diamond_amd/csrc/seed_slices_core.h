@@ -1,7 +1,7 @@
 // seed_slices_core.h -- the sliced long-seed reference stream: what the kernels, the host bookkeeping in
 // seed_api.hip and the CPU tests (tests/emu) share. No HIP in here.
 //
-// The level-1 filter of a long-seed search (3 MB for C2) does not fit a CU's LDS; a slice of it does. Without key classes the word of
+// The level-1 filter of a long-seed search (3 MB for C2 on the plain stream, 8 MB on this one) does not fit a CU's LDS; a slice of it does. Without key classes the word of
 // a key is bm1_word(h & hmask, W) = ((h & hmask) * W) >> 32 with h = seed_hash_a(key): when 2^b divides W and hmask keeps the top b
 // bits of h (slot_bits >= b), a key whose top b bits of h are s probes a word of [s W / 2^b, (s + 1) W / 2^b) -- slice s. The key is
 // a function of the reference window and the shape alone, so the slice of every window is a reference-side fact: it is computed
@@ -30,13 +30,36 @@ DMND_HD int seed_slice_bits(uint64_t words, int slot_bits, uint32_t max_words)
 	return -1;
 }
 
+// Words of the level-1 filter that a search on the sliced stream builds. The plain stream's filter is sized to stay in an XCD's L2
+// beside the stream (seed_sizes); the sliced stream probes from LDS, where only the slice count bounds the filter: the largest
+// power of two that SEED_SLICE_MAX_BITS slices of SEED_SLICE_MAX_WORDS words hold, and no more than the level-2 filter (bm_words).
+// It stands in for default_words (seed_sizes' size) only where it is larger and seed_slice_bits finds it a slice count; otherwise
+// the result is default_words. forced_words (DMND_SEED_SLICES_FILTER_WORDS; 0: none) replaces the rule's size, bound by the slice
+// count alone. *k3 (bm1_bits) is written only where the result is not default_words: three bits per seed from four filter bits per
+// query position up, seed_sizes' own bound, and two bits otherwise. The three bits are k3 = 2, the third bit from below the word
+// index, for a power of two of words (the rule's sizes; at most 2^21 by the slice count), and the plain stream's k3 = 1 for a
+// forced size that is none: its word index reaches below bit 11.
+DMND_HD uint64_t seed_slices_filter_words(uint64_t nq_pos, int slot_bits, uint64_t bm_words, uint64_t default_words, uint32_t max_slice_words, uint64_t forced_words, uint32_t* k3)
+{
+	uint64_t w = forced_words;
+	if (w == 0) {
+		uint64_t most = (uint64_t)SEED_SLICE_MAX_WORDS << SEED_SLICE_MAX_BITS;
+		if (bm_words < most) most = bm_words;
+		for (w = 1; w * 2 <= most; w *= 2) {}
+		if (w <= default_words) return default_words;
+	}
+	if (w == default_words || seed_slice_bits(w, slot_bits, max_slice_words) < 0) return default_words;
+	if (k3) *k3 = nq_pos * 4 > w * 32 ? 0u : (w & (w - 1)) == 0 ? 2u : 1u;
+	return w;
+}
+
 // slice of a key's hash a
 DMND_HD uint32_t seed_slice_of(uint32_t h, int slice_bits) { return slice_bits ? h >> (32 - slice_bits) : 0u; }
 
 // Without key classes the level-1 probe of a window is a function of h = seed_hash_a(key) alone -- the word below (bm1_word_of_key
 // for classes = 0) and bm1_bits(h, k3) -- and h is a reference-side fact as the slice is: the cache keeps it beside every list entry
-// (seed_ref_hash_entry), and the stream reads list entry and hash instead of gathering the window's nibbles. Only a window that passes
-// level 1 needs its key again (level-2 word, table): seed_window_key from the kept nibbles.
+// (seed_ref_hash_entry), and the stream reads the hash instead of gathering the window's nibbles. Only a window that passes
+// level 1 needs its list entry and its key again (level-2 word, table): seed_window_key from the kept nibbles.
 DMND_HD uint32_t seed_slice_word(uint32_t h, uint32_t hmask, uint32_t words) { return bm1_word(h & hmask, words); }
 // table key of the window that starts at nibble `at` (0..15) of c0, c0 / c1 the class nibbles of its group of 16 letters and the next
 DMND_HD uint64_t seed_window_key(uint64_t c0, uint64_t c1, uint32_t at, uint64_t care64)

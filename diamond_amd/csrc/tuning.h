@@ -36,6 +36,9 @@ struct Tuning {
 	int seed_readback_bytes = 1 << 20; // DMND_SEED_READBACK_BYTES: most bytes of sorted hits that come back with the chain's one copy
 	// ---- sliced long-seed stream (seed_slices_core.h)
 	// (values only, like the two above: their environment variables are per-call hooks read in seed_api.hip seed_hooks)
+	// (no value for the size of the level-1 filter: a search on the sliced stream takes the largest the slices hold -- seed_slices_filter_words,
+	// C2: 8 MB in 64 slices of 128 KB instead of the plain stream's L2-bound 3 MB; stream kernel 0.72 / 0.64 / 0.59 ms at 3 / 4 / 8 MB --,
+	// DMND_SEED_SLICES_FILTER_WORDS is the per-call hook of tests and size sweeps)
 	int seed_slices_budget_mb = 3072;  // DMND_SEED_SLICES_BUDGET_MB: most MB of reference-side cache a context keeps. 8 bytes per reference letter and shape (list entry and hash) plus half a byte per letter: C2's 3.0e8-letter block takes 2 561 397 480 bytes (2443 MB) with one shape; with the two of the default sensitivity it would take 4742 MB, which is over the budget, and such a search takes the plain stream (before the hashes two shapes fit, at 2439 MB; the budget was not raised: nothing measured asks for it). Only what is kept counts: the build's scratch (two routing bytes per window, the flag words, the radix pass's: about 0.7 GB more for C2's block until the build is done) does not, and a context that cannot allocate it takes the plain stream
 	long long seed_slices_min_letters = 1 << 20;   // DMND_SEED_SLICES_MIN_LETTERS: reference block length from which on a repeated search takes the sliced stream (C2's query block: sliced / plain stream kernel 0.0179 / 0.0192 ms at 3e5 letters, 0.0189 / 0.0225 ms at 9e5, 0.287 / 0.453 ms at 9e7)
 	long long seed_slices_max_joined = 1 << 20;    // (no hook) joined reference positions of the context's last search above which the default rule leaves the sliced stream out: C2skew (over 1.6e6 per step) ran 28.7 ms per step with it, 26.8-27.4 without, C2 (9e4) 2.50 against 2.98
